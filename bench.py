@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — forgetting-step images/sec of the GS-LoRA step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config 2|4|5]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config 2|4|5] [--dump-outputs DIR]
 
 N > 1: one process per GPU over RCCL. Either the driver launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or, when WORLD_SIZE is not set,
@@ -191,6 +191,9 @@ class StubWorkload:
             dist.all_reduce(self.w)
         return self.w.reshape(-1)[:8].clone()
 
+    def outputs(self, pack):
+        return {"meters": pack, "w": self.w}
+
     def profile(self):
         return {}
 
@@ -229,6 +232,17 @@ class GsLoraWorkload:
 
     def step(self, eager=False):
         return (self.eager if eager else self.stepper)(self.x_r, self.y_r, self.x_f, self.y_f, **self.kw)
+
+    def outputs(self, pack):
+        """What a caller of the step receives: the 8 meters it returns, and in place the updated trainable (LoRA) parameters and the
+        gradients the update was computed from."""
+        out = {"meters": pack}
+        for n, p in self.model.named_parameters():
+            if p.requires_grad:
+                out["param." + n] = p
+                if p.grad is not None:
+                    out["grad." + n] = p.grad
+        return out
 
     def eval_leg(self, n_batches):
         """engine_cl.eval_data (reference engine_cl.py:318-346) on a synthetic test loader shaped like the reference's: batches of
@@ -289,6 +303,21 @@ def kernel_roofline(name, what, recs, flops_of, bytes_of):
             "hbm_gbs": round(gbs, 1), "hbm_frac_of_peak": round(gbs / PEAK_HBM_GBS, 4), "arithmetic_intensity_flop_per_byte": round(fl / by, 1)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32. Copied to the host at once: later steps overwrite the step's outputs."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_MAX_BYTES}")
+    os.makedirs(d, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -306,7 +335,11 @@ def main():
     ap.add_argument("--eval-batches", type=int, default=3)
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary leg (N = 1, config 2, --dtype fp16 only: the same step on bf16 operands = BASELINE configs[1] as written, 3 warm-up + 10 timed steps after the timed region)")
     ap.add_argument("--no-mem-kernels", action="store_true", help="skip the two extra steps after the timed region that time the LayerNorm / attention launches (roofline.memory_bound_kernels); the profiling scripts pass it so that a trace holds warmup + steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (its 8 meters, "
+                    "the updated LoRA parameters and their gradients) as DIR/<name>.npy in float32, on rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     C = CONFIGS[args.config]
     args.batch = C["batch"] if args.batch is None else args.batch
     args.dropout = C["dropout"] if args.dropout is None else args.dropout
@@ -381,6 +414,8 @@ def main():
             marks[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs(pack))
     prof = {}
     per_step = [0.0]
     prof_source = "HIP events around every launch inside the timed region"

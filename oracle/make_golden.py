@@ -1,5 +1,6 @@
 """Generate tests/golden/*.npz by running the REAL reference (imported, unmodified,
-from /root/reference) on the deterministic recipe of oracle/recipe.py.
+from /root/reference) on the deterministic recipe of oracle/recipe.py; tests/golden/engine_signatures.json
+holds the engines' train_one_epoch parameter lists, read from the reference's source.
 
 Runs only in the build container (the reference does not travel to the GPU box).
 Usage:  python oracle/make_golden.py
@@ -268,6 +269,21 @@ def host_kats(out):
     print("[golden] host_kats")
 
 
+def engine_signatures(out):
+    """Parameter names of the reference engines' train_one_epoch, read from their source (test_host_logic pins the drop-ins to them)."""
+    import ast
+    import json
+    sig = {}
+    for mod in ("engine_cl", "engine"):
+        tree = ast.parse(open(os.path.join(REF, mod + ".py")).read())
+        f = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "train_one_epoch")
+        sig[mod + ".train_one_epoch"] = [a.arg for a in f.args.args]
+    with open(os.path.join(out, "engine_signatures.json"), "w") as fh:
+        json.dump(sig, fh, indent=1)
+        fh.write("\n")
+    print("[golden] engine_signatures")
+
+
 def main():
     install_shims()
     torch.manual_seed(0)
@@ -282,6 +298,8 @@ def main():
             run_case(tag, cfg, b, out, HYPER)
     if not only or "host_kats" in only:
         host_kats(out)
+    if not only or "engine_signatures" in only:
+        engine_signatures(out)
 
 
 if __name__ == "__main__":

@@ -107,7 +107,23 @@ def test_full_three_steps_match_reference_engine(golden_dir):
             for k, v in grads.items():
                 r = g[f"grad1::{k}"]
                 assert np.abs(v.numpy() - r).max() < 2e-5 * max(1.0, np.abs(r).max()), k
-        if s in (0, 2):
+        if s == 0:
+            # Adam's first step moves a weight by lr * g / (|g| + eps): where the reference's |g| is below 1e-6 that is set by the
+            # ~1e-8 rounding of the f32 gradient, which differs between CPU kernels (AVX-512 vs AVX2 BLAS flips the sign of a
+            # 1e-9 gradient). Those weights are held to Adam's step bound; every other one to 5e-5.
+            ill = total = 0
+            for k in grads:
+                d = np.abs(new_st[k].numpy() - g[f"param1::{k}"])
+                noise = np.abs(g[f"grad1::{k}"]) < 1e-6
+                assert d[~noise].max() < 5e-5, (s, k)
+                assert (d[noise] <= 2 * HYPER["lr"]).all(), (s, k)
+                ill, total = ill + int(noise.sum()), total + d.size
+            assert ill < 2e-3 * total, (ill, total)
+            # steps 2 and 3 continue from the reference's step-1 weights, so that the weights step 1 leaves to rounding do not
+            # steer the comparison after step 3
+            st_np = {k: g[f"param1::{k}"] if k in grads else v.numpy() for k, v in new_st.items()}
+            continue
+        if s == 2:
             for k in grads:
                 r = g[f"param{s + 1}::{k}"]
                 assert np.abs(new_st[k].numpy() - r).max() < 5e-5, (s, k)   # Adam's m/sqrt(v) amplifies 1e-7 grad noise
