@@ -1,10 +1,14 @@
 // head.hip — the two ends of the network and the scalar losses:
 //   K1  patch gather (einops rearrange, vit_pytorch_face/vit_face.py:530)
-//   K10 cls-pool + LayerNorm + CosFace margin head (vit_face.py:540-546, 171-208) fwd / bwd
+//   K10 cls-pool + LayerNorm + CosFace / ArcFace margin head (vit_face.py:540-546, 171-208, 72-143) fwd / bwd
+//       ArcFace departs from the reference in one place: sine = sqrt(max(1 - cos^2, 0)) and its derivative divides by max(sine, 1e-6),
+//       where the reference's sqrt returns NaN at |cos| > 1 (rounding) and an infinite gradient at |cos| = 1.
 //   K11 mean cross-entropy + top-1 (engine_cl.py:65-78, util/utils.py:354-368) fwd / bwd
 //   K13 prototype KL (engine_cl.py:571-603) fwd / bwd
 // All are tiny next to the GEMMs; they exist so that a step needs no host sync and no [B,C]-sized
 // PyTorch elementwise chain. Upstream gradient scalars arrive as DEVICE pointers (coef).
+#include <cmath>
+
 #include "gsl_common.h"
 
 using namespace gsl;
@@ -62,14 +66,37 @@ extern "C" int gsl_cosface_prep(const float* W, float* Wn, int C, int D, gsl_str
 
 constexpr int HEAD_MAXD = 1024;
 
-// X: element type of the residual stream x (f32, or bf16 in speed mode)
-template <typename X>
+// head kinds of the margin entry points, a template argument of both kernels: the margin code of a kind exists only in its own
+// instantiations. HEAD_COSFACE also covers the plain linear head (runtime flag `linear`, as in gsl_head_fwd / gsl_head_bwd).
+constexpr int HEAD_COSFACE = 0, HEAD_ARCFACE = 1;
+// ArcFace constants (vit_face.py:98-101), computed on the host in double and passed as float
+struct ArcMargin {
+  float cos_m, sin_m, th, mm;
+  int easy;
+};
+// phi(cos) of the label column (vit_face.py:127-132)
+__device__ __forceinline__ float arc_phi(float c, const ArcMargin& a) {
+  const float sine = sqrtf(fmaxf(1.0f - c * c, 0.0f));
+  const float phi = c * a.cos_m - sine * a.sin_m;
+  return a.easy ? (c > 0.0f ? phi : c) : (c > a.th ? phi : c - a.mm);
+}
+// d phi / d cos at the cosine the forward saw: the same comparison picks the branch
+__device__ __forceinline__ float arc_dphi(float c, const ArcMargin& a) {
+  if (!(a.easy ? c > 0.0f : c > a.th)) return 1.0f;
+  const float sine = fmaxf(sqrtf(fmaxf(1.0f - c * c, 0.0f)), 1e-6f);
+  return a.cos_m + a.sin_m * c / sine;
+}
+
+// X: element type of the residual stream x (f32, or bf16 in speed mode). KIND: HEAD_COSFACE / HEAD_ARCFACE; arc / cos_y are read
+// by HEAD_ARCFACE only (cos_y [B]: the label column's cosine before the margin, for the backward)
+template <typename X, int KIND>
 __global__ __launch_bounds__(1024) void head_fwd_kernel(const X* __restrict__ x, int T, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, float eps, const float* __restrict__ Wn,
                                                        const int64_t* __restrict__ label, float* __restrict__ emb,
                                                        float* __restrict__ mean, float* __restrict__ rstd,
                                                        float* __restrict__ logits, int D, int C, float cs, float cm,
-                                                       const float* __restrict__ hbias, int linear, int pool_mean) {
+                                                       const float* __restrict__ hbias, int linear, int pool_mean, ArcMargin arc,
+                                                       float* __restrict__ cos_y) {
   fp16_sat_on();
   __shared__ float e[HEAD_MAXD];
   __shared__ float sm[16];
@@ -121,10 +148,30 @@ __global__ __launch_bounds__(1024) void head_fwd_kernel(const X* __restrict__ x,
       float dk = wave_sum(dot[k]);
       if (lane == 0 && c < C) {
         if (linear) logits[(size_t)b * C + c] = dk + (hbias ? hbias[c] : 0.f);     // plain nn.Linear head (modified_VIT.py:34-36)
-        else { dk *= inv; logits[(size_t)b * C + c] = cs * ((c == lab) ? (dk - cm) : dk); }
+        else if constexpr (KIND == HEAD_ARCFACE) {
+          dk *= inv;
+          if (c == lab) { cos_y[b] = dk; dk = arc_phi(dk, arc); }
+          logits[(size_t)b * C + c] = cs * dk;
+        } else { dk *= inv; logits[(size_t)b * C + c] = cs * ((c == lab) ? (dk - cm) : dk); }
       }
     }
   }
+}
+
+template <int KIND>
+static void head_fwd_launch(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
+                            const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C, float cos_s,
+                            float cos_m, const float* head_bias, int linear_head, int pool_mean, ArcMargin arc, float* cos_y, gsl_stream_t s) {
+  const int nthr = B <= 128 ? 1024 : 256;      // one workgroup per image: with few images give each one 16 waves (100 class rows in two rounds)
+  if (x_dtype == GSL_F16)
+    hipLaunchKernelGGL((head_fwd_kernel<f16_t, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const f16_t*)x, T, gamma, beta, eps, Wn, label,
+                       emb, mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean, arc, cos_y);
+  else if (x_dtype == GSL_BF16)
+    hipLaunchKernelGGL((head_fwd_kernel<bf16_t, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const bf16_t*)x, T, gamma, beta, eps, Wn, label,
+                       emb, mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean, arc, cos_y);
+  else
+    hipLaunchKernelGGL((head_fwd_kernel<float, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const float*)x, T, gamma, beta, eps, Wn, label,
+                       emb, mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean, arc, cos_y);
 }
 
 extern "C" int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
@@ -134,23 +181,43 @@ extern "C" int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamm
   GSL_CHECK_ARG(x && gamma && beta && emb && mean && rstd && B > 0 && T > 0, "null/size");
   GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");
   GSL_CHECK_ARG(!logits || (Wn && C > 0), "Wn required for logits");
-  const int nthr = B <= 128 ? 1024 : 256;      // one workgroup per image: with few images give each one 16 waves (100 class rows in two rounds)
-  if (x_dtype == GSL_F16)
-    hipLaunchKernelGGL(head_fwd_kernel<f16_t>, dim3(B), dim3(nthr), 0, as_stream(s), (const f16_t*)x, T, gamma, beta, eps, Wn, label, emb,
-                       mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean);
-  else if (x_dtype == GSL_BF16)
-    hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(B), dim3(nthr), 0, as_stream(s), (const bf16_t*)x, T, gamma, beta, eps, Wn, label, emb,
-                       mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean);
-  else
-    hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(B), dim3(nthr), 0, as_stream(s), (const float*)x, T, gamma, beta, eps, Wn, label, emb,
-                       mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean);
+  head_fwd_launch<HEAD_COSFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
+                                linear_head, pool_mean, ArcMargin{}, nullptr, s);
   return check_launch("gsl_head_fwd");
+}
+
+// ArcFace constants of margin m (vit_face.py:98-101): math.cos / math.sin in double, as the reference computes them, then float
+static ArcMargin arc_margin(double m, int easy_margin) {
+  const double pi = 3.14159265358979323846;      // math.pi
+  return ArcMargin{(float)std::cos(m), (float)std::sin(m), (float)std::cos(pi - m), (float)(std::sin(pi - m) * m), easy_margin ? 1 : 0};
+}
+
+extern "C" int gsl_head_fwd_margin(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
+                                   const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C,
+                                   float cos_s, float cos_m, const float* head_bias, int linear_head, int pool_mean, int head_kind,
+                                   double m, int easy_margin, float* cos_y, gsl_stream_t s) {
+  GSL_CHECK_ARG(head_kind == HEAD_COSFACE || head_kind == HEAD_ARCFACE, "head_kind: 0 (CosFace) or 1 (ArcFace)");
+  GSL_CHECK_ARG(x_dtype == GSL_F32 || x_dtype == GSL_BF16 || x_dtype == GSL_F16, "x dtype");
+  GSL_CHECK_ARG(x && gamma && beta && emb && mean && rstd && B > 0 && T > 0, "null/size");
+  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");
+  GSL_CHECK_ARG(!logits || (Wn && C > 0), "Wn required for logits");
+  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !linear_head, "ArcFace is a cosine head (linear_head = 0)");
+  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !logits || (label && cos_y), "ArcFace logits need label and cos_y [B]");
+  if (head_kind == HEAD_ARCFACE)
+    head_fwd_launch<HEAD_ARCFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
+                                  linear_head, pool_mean, arc_margin(m, easy_margin), cos_y, s);
+  else
+    head_fwd_launch<HEAD_COSFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
+                                  linear_head, pool_mean, ArcMargin{}, nullptr, s);
+  return check_launch("gsl_head_fwd_margin");
 }
 
 // compact != 0 (pool = 'cls' only): dx / dxb are [B, D] — the gradient of the cls rows alone; the stream gradient of every other token is
 // exactly zero and is neither written here nor read by the consumers (the cls-row-only backward of the last block, gsl_layernorm_bwd's
 // dres_cls_T). The dropout counter of element (b, d) stays that of the dense tensor, (b*Tn)*D + d: same masks in both forms.
-template <typename T, typename S, typename X>
+// KIND = HEAD_ARCFACE: the label column of dlogits is multiplied by d phi / d cos at cos_y [B] (written by the forward) before
+// the sum over the classes; everything after that is the CosFace code.
+template <typename T, typename S, typename X, int KIND>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ demb_in,
                                                        const X* __restrict__ x, int Tn, const float* __restrict__ gamma,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -158,7 +225,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                                                        S* __restrict__ dx, T* __restrict__ dxb, int D, int C, float cs,
                                                        DropCfg drop, int linear, int pool_mean, int compact,
                                                        float* __restrict__ amax_out, const float* __restrict__ amax_in, int n_amax,
-                                                       float* __restrict__ gscale_out, int target_exp) {
+                                                       float* __restrict__ gscale_out, int target_exp, ArcMargin arc,
+                                                       const float* __restrict__ cos_y, const int64_t* __restrict__ label) {
   fp16_sat_on();
   resolve_drop(drop);
   // fp16 operands (round 5): the backward runs on gradients multiplied by a power of two S chosen from the largest stream gradient
@@ -218,6 +286,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   const float nrm = fmaxf(sqrtf(block_sum(nn, sm)), 1e-12f);
   if (dlogits) {
     for (int c = tid; c < C; c += 256) dl[c] = cs * dlogits[(size_t)b * C + c];
+    if constexpr (KIND == HEAD_ARCFACE) {      // the thread that stored dl[y] rescales it: no barrier needed in between
+      const long y = (long)label[b];
+      if (y >= 0 && y < C && tid == (int)(y & 255)) dl[y] *= arc_dphi(cos_y[b], arc);
+    }
   }
   __syncthreads();
   float dotp = 0.f;
@@ -284,30 +356,20 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // tools/emu_operand_precision.py): the largest gradient operand anywhere in the backward is 1.2x the head's, so the chain peaks near 2.5e3
 // (26x below fp16's 65504; stores saturate, they never produce Inf), and the LoRA-gradient error is flat for S between 2^6 and 2^20.
 constexpr int GSL_GRAD_TARGET_EXP = 11;
-extern "C" int gsl_head_bwd(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
-                            const float* mean, const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb,
-                            int B, int D, int C, float cos_s, int dtype, int stream_dtype, float p_drop, uint64_t seed, uint32_t site,
-                            int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int target_exp, gsl_stream_t s) {
-  GSL_CHECK_ARG(x && gamma && mean && rstd && emb && dx && B > 0 && T >= 1, "null/size");
-  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0 && C <= 1024, "D <= 1024, D%4==0, C <= 1024");
-  GSL_CHECK_ARG(!dlogits || Wn, "Wn required with dlogits");
-  GSL_CHECK_ARG(!(compact && pool_mean), "compact cls-row gradients need pool = 'cls'");
-  GSL_CHECK_ARG(!gscale || amax_ws, "gscale (loss-scaled gradients) needs amax_ws [B]");
-  GSL_CHECK_ARG(target_exp == 0 || (target_exp >= 4 && target_exp <= 15), "target_exp: 0 (default 11) or 4 .. 15");
-  const int texp = target_exp ? target_exp : GSL_GRAD_TARGET_EXP;
-  const DropCfg drop = make_drop(p_drop, seed, site);
-  GSL_CHECK_ARG(stream_dtype == GSL_F32 || (stream_dtype == dtype && dtype != GSL_F32), "stream dtype (f32, or the operand format of a 16-bit mode)");
-  GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16),
-                "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)");
+template <int KIND>
+static void head_bwd_launch(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma, const float* mean,
+                            const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb, int B, int D, int C, float cos_s, int dtype,
+                            int stream_dtype, DropCfg drop, int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int texp,
+                            ArcMargin arc, const float* cos_y, const int64_t* label, gsl_stream_t s) {
 #define GSL_HB(T_, S_, X_)                                                                                                          \
   do {                                                                                                                              \
     if (gscale)                                                                                                                     \
-      hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma, mean, \
-                         rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, amax_ws, (const float*)nullptr, 0, \
-                         gscale, texp);                                                                                             \
-    hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma, mean, \
-                       rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, (float*)nullptr,       \
-                       (const float*)(gscale ? amax_ws : nullptr), B, gscale, texp);                                 \
+      hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma, \
+                         mean, rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, amax_ws,        \
+                         (const float*)nullptr, 0, gscale, texp, arc, cos_y, label);                                                 \
+    hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma,   \
+                       mean, rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, (float*)nullptr,   \
+                       (const float*)(gscale ? amax_ws : nullptr), B, gscale, texp, arc, cos_y, label);                              \
   } while (0)
   if (dtype == GSL_F16 && stream_dtype == GSL_F16 && x_dtype == GSL_F16) GSL_HB(f16_t, f16_t, f16_t);
   else if (dtype == GSL_F16 && stream_dtype == GSL_F16) GSL_HB(f16_t, f16_t, float);
@@ -319,11 +381,55 @@ extern "C" int gsl_head_bwd(const float* dlogits, const float* demb, const void*
   else if (dtype == GSL_BF16 && stream_dtype == GSL_BF16) GSL_HB(bf16_t, bf16_t, float);
   else if (dtype == GSL_BF16 && x_dtype == GSL_BF16) GSL_HB(bf16_t, float, bf16_t);
   else if (dtype == GSL_BF16) GSL_HB(bf16_t, float, float);
-  else if (dtype == GSL_F32) GSL_HB(float, float, float);
-  else return fail(GSL_ERR_ARG, "gsl_head_bwd: bad dtype%s %ld", "", dtype);
+  else GSL_HB(float, float, float);      // GSL_F32 (the callers reject any other dtype)
 #undef GSL_HB
+}
+
+// the argument checks of both backward entry points (a macro: GSL_CHECK_ARG reports the caller's name)
+#define GSL_HEAD_BWD_CHECKS()                                                                                                        \
+  GSL_CHECK_ARG(x && gamma && mean && rstd && emb && dx && B > 0 && T >= 1, "null/size");                                          \
+  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0 && C <= 1024, "D <= 1024, D%4==0, C <= 1024");                               \
+  GSL_CHECK_ARG(!dlogits || Wn, "Wn required with dlogits");                                                                         \
+  GSL_CHECK_ARG(!(compact && pool_mean), "compact cls-row gradients need pool = 'cls'");                                            \
+  GSL_CHECK_ARG(!gscale || amax_ws, "gscale (loss-scaled gradients) needs amax_ws [B]");                                            \
+  GSL_CHECK_ARG(target_exp == 0 || (target_exp >= 4 && target_exp <= 15), "target_exp: 0 (default 11) or 4 .. 15");                \
+  GSL_CHECK_ARG(stream_dtype == GSL_F32 || (stream_dtype == dtype && dtype != GSL_F32), "stream dtype (f32, or the operand format of a 16-bit mode)"); \
+  GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16), \
+                "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)")
+
+extern "C" int gsl_head_bwd(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
+                            const float* mean, const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb,
+                            int B, int D, int C, float cos_s, int dtype, int stream_dtype, float p_drop, uint64_t seed, uint32_t site,
+                            int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int target_exp, gsl_stream_t s) {
+  GSL_HEAD_BWD_CHECKS();
+  if (dtype != GSL_F16 && dtype != GSL_BF16 && dtype != GSL_F32) return fail(GSL_ERR_ARG, "gsl_head_bwd: bad dtype%s %ld", "", dtype);
+  head_bwd_launch<HEAD_COSFACE>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, Wn, dx, dxb, B, D, C, cos_s, dtype, stream_dtype,
+                                make_drop(p_drop, seed, site), linear_head, pool_mean, compact, gscale, amax_ws,
+                                target_exp ? target_exp : GSL_GRAD_TARGET_EXP, ArcMargin{}, nullptr, nullptr, s);
   return check_launch("gsl_head_bwd");
 }
+
+extern "C" int gsl_head_bwd_margin(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
+                                   const float* mean, const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb,
+                                   int B, int D, int C, float cos_s, int dtype, int stream_dtype, float p_drop, uint64_t seed, uint32_t site,
+                                   int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int target_exp, int head_kind,
+                                   double m, int easy_margin, const float* cos_y, const int64_t* label, gsl_stream_t s) {
+  GSL_CHECK_ARG(head_kind == HEAD_COSFACE || head_kind == HEAD_ARCFACE, "head_kind: 0 (CosFace) or 1 (ArcFace)");
+  GSL_HEAD_BWD_CHECKS();
+  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !linear_head, "ArcFace is a cosine head (linear_head = 0)");
+  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !dlogits || (label && cos_y), "ArcFace dlogits need label and cos_y [B]");
+  if (dtype != GSL_F16 && dtype != GSL_BF16 && dtype != GSL_F32) return fail(GSL_ERR_ARG, "gsl_head_bwd_margin: bad dtype%s %ld", "", dtype);
+  const int texp = target_exp ? target_exp : GSL_GRAD_TARGET_EXP;
+  const DropCfg drop = make_drop(p_drop, seed, site);
+  if (head_kind == HEAD_ARCFACE)
+    head_bwd_launch<HEAD_ARCFACE>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, Wn, dx, dxb, B, D, C, cos_s, dtype, stream_dtype, drop,
+                                  linear_head, pool_mean, compact, gscale, amax_ws, texp, arc_margin(m, easy_margin), cos_y, label, s);
+  else
+    head_bwd_launch<HEAD_COSFACE>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, Wn, dx, dxb, B, D, C, cos_s, dtype, stream_dtype, drop,
+                                  linear_head, pool_mean, compact, gscale, amax_ws, texp, ArcMargin{}, nullptr, nullptr, s);
+  return check_launch("gsl_head_bwd_margin");
+}
+#undef GSL_HEAD_BWD_CHECKS
 
 // ------------------------------------------------------------------ K11 cross entropy
 // wave-per-row log-softmax; one block so the batch sum is a fixed-order (deterministic) reduction.

@@ -78,6 +78,8 @@ def get_args(argv=None):
     p.add_argument("--dropout", type=float, default=0.1)
     p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 (16-bit MFMA operands) | fp32 (parity mode)")
     p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
+    p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"],
+                   help="classification head of ViT_face (config.py -head; SFaceLoss is not implemented)")
     p.add_argument("--outdir", default=None)
     p.add_argument("--seed", type=int, default=1337)
     p.add_argument("--average_weight", default=False, action="store_true", help="EMA model of the reference (:502-507, :1058-1098)")
@@ -205,7 +207,7 @@ def main(argv=None):
     order = list(range(args.num_class))                       # reference :198-204
     random.seed(args.seed)
     random.shuffle(order)
-    model = ViT_face(loss_type="CosFace", GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout,
+    model = ViT_face(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout,
                      lora_rank=args.lora_rank, **geo)
     lora.mark_only_lora_as_trainable(model)                   # :314-317
     print("trainable parameters:", count_trainable_parameters(model))

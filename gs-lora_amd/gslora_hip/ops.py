@@ -404,6 +404,51 @@ def head_bwd(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype
     return dx, dxb
 
 
+HEAD_KINDS = {"cosface": 0, "arcface": 1}      # head_kind of gsl_head_fwd_margin / gsl_head_bwd_margin
+
+
+def head_fwd_margin(x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_kind, m=0.5, easy_margin=False, head_bias=None,
+                    linear=False, pool_mean=False):
+    """head_fwd with the margin head chosen by head_kind ("cosface" | "arcface"; gsl_head_fwd_margin). m / easy_margin: the ArcFace
+    margin (cos_m is CosFace's). Returns (logits, emb, mean, rstd, cos_y): cos_y [B] is the label column's cosine before the margin
+    (ArcFace with labels; None otherwise), which head_bwd_margin needs."""
+    _need(x, gamma, beta, Wn, label, head_bias)
+    kind = HEAD_KINDS[head_kind]
+    dev = x.device
+    emb = torch.empty(B, D, device=dev, dtype=torch.float32)
+    mean = torch.empty(B, device=dev, dtype=torch.float32)
+    rstd = torch.empty(B, device=dev, dtype=torch.float32)
+    C = Wn.shape[0] if Wn is not None else 0
+    logits = torch.empty(B, C, device=dev, dtype=torch.float32) if (label is not None or linear) else None
+    cos_y = torch.empty(B, device=dev, dtype=torch.float32) if (kind and logits is not None) else None
+    L.check(L.load().gsl_head_fwd_margin(_p(x), code(x.dtype), T, _p(gamma), _p(beta), float(eps), _p(Wn), _p(label), _p(emb), _p(mean),
+                                         _p(rstd), _p(logits), B, D, C, float(cos_s), float(cos_m), _p(head_bias), 1 if linear else 0,
+                                         1 if pool_mean else 0, kind, float(m), 1 if easy_margin else 0, _p(cos_y), _stream()),
+            "gsl_head_fwd_margin")
+    return logits, emb, mean, rstd, cos_y
+
+
+def head_bwd_margin(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype, head_kind, m=0.5, easy_margin=False, cos_y=None,
+                    label=None, p_drop=0.0, seed=0, site=0, linear=False, pool_mean=False, stream_dtype=torch.float32, compact=False,
+                    gscale=None, target_exp=0):
+    """head_bwd with the margin head chosen by head_kind (gsl_head_bwd_margin). ArcFace with dlogits needs the forward's cos_y and the
+    labels; everything else as head_bwd."""
+    _need(dlogits, demb, x, gamma, mean, rstd, emb, Wn, gscale, cos_y, label)
+    if gscale is not None and (gscale.numel() < 4 or gscale.dtype != torch.float32):
+        raise RuntimeError("head_bwd_margin: gscale must be a float32 tensor of 4 elements {S, 1/S, seen maximum, exponent}")
+    amax_ws = torch.empty(B, device=x.device, dtype=torch.float32) if gscale is not None else None
+    rows = B if compact else B * T
+    dx = torch.empty(rows, D, device=x.device, dtype=stream_dtype)
+    dxb = torch.empty(rows, D, device=x.device, dtype=dtype)
+    C = Wn.shape[0] if Wn is not None else 0
+    L.check(L.load().gsl_head_bwd_margin(_p(dlogits), _p(demb), _p(x), code(x.dtype), T, _p(gamma), _p(mean), _p(rstd), _p(emb), _p(Wn),
+                                         _p(dx), _p(dxb), B, D, C, float(cos_s), code(dtype), code(stream_dtype), float(p_drop), int(seed),
+                                         int(site), 1 if linear else 0, 1 if pool_mean else 0, 1 if compact else 0, _p(gscale), _p(amax_ws),
+                                         int(target_exp), HEAD_KINDS[head_kind], float(m), 1 if easy_margin else 0, _p(cos_y), _p(label),
+                                         _stream()),
+            "gsl_head_bwd_margin")
+    return dx, dxb
+
 def ce_fwd(logits, labels):
     _need(logits, labels)
     out = torch.empty(2, device=logits.device, dtype=torch.float32)

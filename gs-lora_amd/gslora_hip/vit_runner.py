@@ -88,18 +88,25 @@ class BlockSpec:
         return (self.l1.lora_A, self.l1.lora_B, self.l2.lora_A, self.l2.lora_B)
 
 
+# head kinds that run the plain linear classifier of gsl_head_fwd / gsl_head_bwd (no normalisation, no margin)
+LINEAR_HEADS = ("linear", "softmax")
+
+
 class ModelSpec:
     """Geometry + parameter handles of one model family. Built by the model's `hip_spec()` on every forward (attribute
     look-ups only), so module surgery between calls — replace_ffn_with_lora, modify_head, load_state_dict — is picked up.
       ViT_face      (vit_pytorch_face/vit_face.py:449-548): Linear patch embedding, bias-free QKV, LN eps 1e-5,
-                    scale dim^-0.5, CosFace head (s 64, m 0.35).
+                    scale dim^-0.5, margin head chosen by loss_type: "cosface" (s 64, m 0.35), "arcface" (s 64, m 0.5,
+                    easy_margin; reference :72-143) — cos_s / cos_m are the head's s and m — or "softmax" (nn.Linear with bias,
+                    reference :14-52: logits only when a label is passed, the label itself is ignored).
       ModifiedViT   (vit_pytorch_face/modified_VIT.py:5-45 over torchvision vit_b_16): conv16 patch embedding, QKV bias,
                     LN eps 1e-6, scale head_dim^-0.5, nn.Linear head with bias, the label argument is ignored."""
     __slots__ = ("patch_size", "num_tokens", "dim", "heads", "attn_scale", "ln_eps", "dropout_p", "emb_dropout_p", "lora_rank",
                  "patch_w", "patch_is_conv", "patch_b", "cls", "pos", "blocks", "final_ln", "head_kind", "head_w", "head_b",
-                 "cos_s", "cos_m", "lora_site", "pool")
+                 "cos_s", "cos_m", "easy_margin", "lora_site", "pool")
 
     def __init__(self, **kw):
+        kw.setdefault("easy_margin", False)    # ArcFace only
         kw.setdefault("lora_site", "ffn")      # "ffn" (GS-LoRA) or "attention" (--lora_pos Attention ablation)
         kw.setdefault("pool", "cls")           # "cls" (token 0) or "mean" (mean over the tokens, vit_face.py:540)
         for k in self.__slots__:
@@ -408,8 +415,8 @@ class ViTRunner:
         L.load()
         sp = m.hip_spec()
         dt = m.compute_dtype
-        linear_head = sp.head_kind == "linear"
-        if linear_head:
+        linear_head = sp.head_kind in LINEAR_HEADS
+        if sp.head_kind == "linear":
             label = None                       # modified_VIT.py:23-24: "label is not used in this model"
         elif label is not None:
             label = label.to(device=img.device, dtype=torch.int64).contiguous()
@@ -562,10 +569,11 @@ class ViTRunner:
             x = x2
         hn = sp.final_ln
         Th = x.shape[0] // B      # rows per image of the stream that reaches the head: T, or 1 after a cls-row-only last block
-        if linear_head:      # plain classifier: logits for every call, no normalisation, no margin
-            Wn = sp.head_w.detach().contiguous()
+        cos_y = None
+        if linear_head:      # plain classifier, no normalisation, no margin: logits for every call (ModifiedViT) / with a label (Softmax)
+            Wn = sp.head_w.detach().contiguous() if (sp.head_kind == "linear" or label is not None) else None
             logits, emb, meanh, rstdh = ops.head_fwd(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, None, 1.0, 0.0,
-                                                     head_bias=sp.head_b.detach(), linear=True)
+                                                     head_bias=sp.head_b.detach(), linear=Wn is not None, pool_mean=(sp.pool == "mean"))
         else:
             if label is None:
                 Wn = None
@@ -573,15 +581,29 @@ class ViTRunner:
                 Wn = ops.cosface_prep(sp.head_w.detach().contiguous())
             else:      # frozen head (GS-LoRA trains the adapters only): the row-normalised weight is computed once per weight version
                 Wn = self._cached(self._wcache, ("cosface_wn",), sp.head_w, lambda p: ops.cosface_prep(p.contiguous()))
-            logits, emb, meanh, rstdh = ops.head_fwd(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, label,
-                                                     sp.cos_s, sp.cos_m, pool_mean=(sp.pool == "mean"))
+            if sp.head_kind == "arcface":      # cos_y: the label column's cosine before the margin, for the backward's branch
+                logits, emb, meanh, rstdh, cos_y = ops.head_fwd_margin(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, label,
+                                                                       sp.cos_s, 0.0, "arcface", m=sp.cos_m, easy_margin=sp.easy_margin,
+                                                                       pool_mean=(sp.pool == "mean"))
+            else:
+                logits, emb, meanh, rstdh = ops.head_fwd(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, label,
+                                                         sp.cos_s, sp.cos_m, pool_mean=(sp.pool == "mean"))
         saved = None
         if save:
             saved = dict(layers=stash, x_last=x, Th=Th, meanh=meanh, rstdh=rstdh, emb=emb, Wn=Wn, B=B, seed=seed, sflag=sflag, p_drop=p_drop,
-                         dt=dt, spec=sp)
+                         dt=dt, spec=sp, cos_y=cos_y, label=label)
         return logits, emb, saved
 
     # ------------------------------------------------------------------ backward
+    @staticmethod
+    def _head_bwd(saved, *args, **kw):
+        """ops.head_bwd, or its margin form for the ArcFace head (with the label column's cosine and the labels the forward saved)."""
+        sp = saved["spec"]
+        if sp.head_kind == "arcface":
+            return ops.head_bwd_margin(*args, head_kind="arcface", m=sp.cos_m, easy_margin=sp.easy_margin, cos_y=saved["cos_y"],
+                                       label=saved["label"], **kw)
+        return ops.head_bwd(*args, **kw)
+
     def backward(self, saved, dlogits, demb):
         """Accumulates d(loss)/d(LoRA) into the flat gradient bucket (views are the params' .grad)."""
         sp = saved["spec"]
@@ -598,7 +620,7 @@ class ViTRunner:
         s_lora = 1.0 / r
         nl = len(saved["layers"])
         hn = sp.final_ln
-        linear_head = sp.head_kind == "linear"
+        linear_head = sp.head_kind in LINEAR_HEADS
         if dlogits is not None:
             dlogits = dlogits.contiguous().float()
         if demb is not None:
@@ -610,7 +632,7 @@ class ViTRunner:
         gscale = self._loss_scale_state(saved["x_last"].device) if dt == torch.float16 else None
         self._guard_on = gscale is not None
         gmax = gscale[2:] if gscale is not None else None      # the overflow guard: raised by every LayerNorm backward below
-        dx, dxb = ops.head_bwd(dlogits, demb, saved["x_last"], B, saved["Th"], D, hn.weight.detach(), saved["meanh"], saved["rstdh"],
+        dx, dxb = self._head_bwd(saved, dlogits, demb, saved["x_last"], B, saved["Th"], D, hn.weight.detach(), saved["meanh"], saved["rstdh"],
                                saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=p_drop, seed=seed,
                                site=(4 * (nl - 1) + 2) | sflag, linear=linear_head, pool_mean=(sp.pool == "mean"),
                                stream_dtype=dt if (dt in OP16 and GRAD_STREAM_BF16) else torch.float32,
@@ -748,7 +770,7 @@ class ViTRunner:
         s_lora = 1.0 / r
         nl = len(saved["layers"])
         hn = sp.final_ln
-        linear_head = sp.head_kind == "linear"
+        linear_head = sp.head_kind in LINEAR_HEADS
         if dlogits is not None:
             dlogits = dlogits.contiguous().float()
         if demb is not None:
@@ -760,7 +782,7 @@ class ViTRunner:
         gscale = self._loss_scale_state(saved["x_last"].device) if dt == torch.float16 else None
         self._guard_on = gscale is not None
         gmax = gscale[2:] if gscale is not None else None      # the overflow guard: raised by every LayerNorm backward below
-        dx, dxb = ops.head_bwd(dlogits, demb, saved["x_last"], B, saved["Th"], D, hn.weight.detach(), saved["meanh"], saved["rstdh"],
+        dx, dxb = self._head_bwd(saved, dlogits, demb, saved["x_last"], B, saved["Th"], D, hn.weight.detach(), saved["meanh"], saved["rstdh"],
                                saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=p_drop, seed=seed,
                                site=(4 * (nl - 1) + 2) | sflag, linear=linear_head, pool_mean=(sp.pool == "mean"),
                                stream_dtype=dt if (dt in OP16 and GRAD_STREAM_BF16) else torch.float32,

@@ -1,6 +1,7 @@
 """ViT-Face with rank-r LoRA on the two FFN linears — MI355X-native drop-in for the reference
 `vit_pytorch_face/vit_face.py` (ViT_face :449-548, Transformer :382-446, Attention :341-379,
-FeedForward :326-338, PreNorm :316-323, Residual :307-313, CosFace :146-223).
+FeedForward :326-338, PreNorm :316-323, Residual :307-313, CosFace :146-223, ArcFace :72-143,
+Softmax :14-69).
 
 The module tree, parameter names and shapes are exactly the reference's (state_dict compatible:
 `transformer.layers.{i}.1.fn.fn.net.{0,3}.lora_{A,B}` ...), the parameters are real
@@ -10,6 +11,7 @@ computes anything in PyTorch. `ViT_face.forward` hands the whole network to
 one `torch.autograd.Function`, the hand-derived backward that fills `lora_*.grad`.
 There is no CPU fallback: calling the model on CPU tensors raises.
 """
+import math
 import os
 
 import torch
@@ -50,6 +52,53 @@ class CosFace(nn.Module):
 
     def extra_repr(self):
         return f"in_features={self.in_features}, out_features={self.out_features}, s={self.s}, m={self.m}"
+
+
+class ArcFace(nn.Module):
+    """Parameter holder for the ArcFace head (s=64, m=0.5, easy_margin=False; reference :72-143): the label column's logit is
+    s * phi(cos), phi = cos(theta + m) above the threshold th = cos(pi - m), cos - mm below it (easy_margin: phi above 0, cos below).
+    Same attributes as the reference; the arithmetic lives in gsl_head_fwd_margin / gsl_head_bwd_margin, which take s and m from here."""
+
+    def __init__(self, in_features, out_features, device_id, s=64.0, m=0.50, easy_margin=False):
+        super().__init__()
+        self.in_features, self.out_features, self.device_id, self.s, self.m = in_features, out_features, device_id, s, m
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        nn.init.xavier_uniform_(self.weight)
+        self.easy_margin = easy_margin
+        self.cos_m = math.cos(m)
+        self.sin_m = math.sin(m)
+        self.th = math.cos(math.pi - m)
+        self.mm = math.sin(math.pi - m) * m
+
+    def forward(self, emb, label):
+        raise RuntimeError("ArcFace is evaluated inside ViT_face.forward (fused HIP head kernel)")
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, out_features={self.out_features}, s={self.s}, m={self.m}, "
+                f"easy_margin={self.easy_margin}")
+
+
+class Softmax(nn.Module):
+    """Parameter holder for the plain classification head (reference :14-69): logits = emb W^T + b, computed when a label is passed
+    (the label itself is ignored), by the linear path of gsl_head_fwd / gsl_head_bwd."""
+
+    def __init__(self, in_features, out_features, device_id):
+        super().__init__()
+        self.in_features, self.out_features, self.device_id = in_features, out_features, device_id
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        self.bias = nn.Parameter(torch.empty(out_features))
+        nn.init.xavier_uniform_(self.weight)
+        nn.init.zeros_(self.bias)
+
+    def forward(self, emb, label):
+        raise RuntimeError("Softmax is evaluated inside ViT_face.forward (fused HIP head kernel)")
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, out_features={self.out_features}"
+
+
+# loss_type -> (holder class, ModelSpec.head_kind)
+_HEADS = {"CosFace": (CosFace, "cosface"), "ArcFace": (ArcFace, "arcface"), "Softmax": (Softmax, "softmax")}
 
 
 class _Holder(nn.Module):
@@ -215,10 +264,14 @@ class ViT_face(HipModelMixin, nn.Module):
         self.GPU_ID = GPU_ID
         if loss_type == "None":
             print("no loss for vit_face")
-        elif loss_type == "CosFace":
-            self.loss = CosFace(in_features=dim, out_features=num_class, device_id=GPU_ID)
+        elif loss_type in _HEADS:
+            self.loss = _HEADS[loss_type][0](in_features=dim, out_features=num_class, device_id=GPU_ID)
+        elif loss_type == "SFace":
+            raise NotImplementedError(
+                "gs-lora_amd does not implement the SFace head: the reference's training CLI cannot build it (config.py accepts "
+                "'SFaceLoss' while ViT_face checks 'SFace'), and its forward returns a 6-tuple that the GS-LoRA engines cannot consume")
         else:
-            raise NotImplementedError(f"gs-lora_amd implements the CosFace head (all GS-LoRA scripts use it), not {loss_type}")
+            raise NotImplementedError(f"gs-lora_amd implements the heads {sorted(_HEADS)}, not {loss_type}")
         # geometry consumed by the runner
         self.dim, self.depth, self.heads, self.mlp_dim = dim, depth, heads, mlp_dim
         self.num_tokens = num_patches + 1
@@ -245,13 +298,17 @@ class ViT_face(HipModelMixin, nn.Module):
             a, f = attn.fn, ff.fn
             blocks.append(BlockSpec(a.norm, a.fn.to_qkv.weight, None, a.fn.to_out[0], f.norm, f.fn.net[0], f.fn.net[3],
                                     qkv_lora=a.fn.to_qkv if self.lora_pos == "Attention" and self.lora_rank > 0 else None))
-        has_loss = self.loss_type == "CosFace"
+        has_loss = self.loss_type in _HEADS
+        kind = _HEADS[self.loss_type][1] if has_loss else "cosface"
         return ModelSpec(patch_size=self.patch_size, num_tokens=self.num_tokens, dim=self.dim, heads=self.heads,
                          attn_scale=self.attn_scale, ln_eps=1e-5, dropout_p=self.dropout_p, emb_dropout_p=self.emb_dropout_p,
                          lora_rank=self.lora_rank, patch_w=self.patch_to_embedding.weight, patch_is_conv=False,
                          patch_b=self.patch_to_embedding.bias, cls=self.cls_token, pos=self.pos_embedding, blocks=blocks,
-                         final_ln=self.mlp_head[0], head_kind="cosface", head_w=self.loss.weight if has_loss else None,
-                         head_b=None, cos_s=self.loss.s if has_loss else 64.0, cos_m=self.loss.m if has_loss else 0.35,
+                         final_ln=self.mlp_head[0], head_kind=kind, head_w=self.loss.weight if has_loss else None,
+                         head_b=self.loss.bias if kind == "softmax" else None,
+                         cos_s=self.loss.s if has_loss and kind != "softmax" else 64.0,
+                         cos_m=self.loss.m if has_loss and kind != "softmax" else 0.35,
+                         easy_margin=bool(self.loss.easy_margin) if kind == "arcface" else False,
                          lora_site="attention" if self.lora_pos == "Attention" else "ffn", pool=self.pool)
 
     # ---- reference API ---------------------------------------------------------------------------

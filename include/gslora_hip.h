@@ -198,7 +198,7 @@ GSL_API long gsl_lora_grad_batch_ws_elems(const gsl_lgrad_desc* descs, int n);
 GSL_API int gsl_lora_grad_batch(const gsl_lgrad_desc* descs, int n, float* ws, int dtype, const float* gscale, gsl_stream_t s);
 
 
-/* ---- K10 head: cls pool + LayerNorm + CosFace (vit_face.py:540-546, 171-208; s=64, m=0.35).
+/* ---- K10 head: cls pool + LayerNorm + CosFace (vit_face.py:540-546, 171-208; s=64, m=0.35); ArcFace through the margin pair below.
  * linear_head != 0 selects the ViT-B/16 path instead (modified_VIT.py:32-38): logits = emb * W^T + head_bias, with Wn = W
  * un-normalised and cos_s = 1 on the backward side. */
 GSL_API int gsl_cosface_prep(const float* W, float* Wn, int C, int D, gsl_stream_t s);   /* Wn = F.normalize(W) */
@@ -227,6 +227,28 @@ GSL_API int gsl_head_bwd(const float* dlogits, const float* demb, const void* x,
                  void* dx, void* dxb, int B, int D, int C, float cos_s, int dtype, int stream_dtype,
                  float p_drop, uint64_t seed, uint32_t site, int linear_head, int pool_mean, int compact,
                  float* gscale, float* amax_ws, int target_exp, gsl_stream_t s);
+/* The margin pair: gsl_head_fwd / gsl_head_bwd with the head chosen by head_kind.
+ *   head_kind 0 = CosFace: the kernels of gsl_head_fwd / gsl_head_bwd, bit for bit (cos_m is the margin; m, easy_margin, cos_y and
+ *                 label are not read).
+ *   head_kind 1 = ArcFace (vit_face.py:72-143; s=64, m=0.5, easy_margin=0): the label column of the logits is
+ *                 s * phi(cos), phi = cos*cos(m) - sqrt(1 - cos^2)*sin(m) if cos > cos(pi - m) (easy_margin: cos > 0), else
+ *                 cos - sin(pi - m)*m (easy_margin: cos); cos_m is not read, linear_head must be 0. The constants are computed
+ *                 from the double m as the reference's math.* does, then rounded to float. The forward writes cos_y [B] = the
+ *                 label column's cosine before the margin; the backward reads it (and label) to take the same branch and scales
+ *                 dlogits[y] by d phi / d cos. One departure: 1 - cos^2 is clamped at 0 and the derivative divides by
+ *                 max(sine, 1e-6) (the reference gives NaN for |cos| > 1 and an infinite gradient at |cos| = 1).
+ * Every other argument means what it means for gsl_head_fwd / gsl_head_bwd. */
+GSL_API int gsl_head_fwd_margin(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps,
+                 const float* Wn, const int64_t* label, float* emb, float* mean, float* rstd,
+                 float* logits, int B, int D, int C, float cos_s, float cos_m,
+                 const float* head_bias, int linear_head, int pool_mean, int head_kind, double m, int easy_margin,
+                 float* cos_y, gsl_stream_t s);
+GSL_API int gsl_head_bwd_margin(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
+                 const float* mean, const float* rstd, const float* emb, const float* Wn,
+                 void* dx, void* dxb, int B, int D, int C, float cos_s, int dtype, int stream_dtype,
+                 float p_drop, uint64_t seed, uint32_t site, int linear_head, int pool_mean, int compact,
+                 float* gscale, float* amax_ws, int target_exp, int head_kind, double m, int easy_margin,
+                 const float* cos_y, const int64_t* label, gsl_stream_t s);
 
 /* ---- K11 cross entropy (mean) + top-1 (engine_cl.py:65-78, util/utils.py:354-368).
  * out2 f32 [2] = { sum_i CE_i , #correct }; row_ws f32 [2*B] scratch (per-row loss / hit, summed in a fixed order). */
