@@ -1,5 +1,5 @@
 // head.hip — the two ends of the network and the scalar losses:
-//   K1  patch gather (einops rearrange, vit_pytorch_face/vit_face.py:530)
+//   K1  patch gather (einops rearrange, vit_pytorch_face/vit_face.py:530); K1s its overlapping-window form (nn.Unfold, vits_face.py:446-450)
 //   K10 cls-pool + LayerNorm + CosFace / ArcFace margin head (vit_face.py:540-546, 171-208, 72-143) fwd / bwd
 //       ArcFace departs from the reference in one place: sine = sqrt(max(1 - cos^2, 0)) and its derivative divides by max(sine, 1e-6),
 //       where the reference's sqrt returns NaN at |cos| > 1 (rounding) and an infinite gradient at |cos| = 1.
@@ -44,6 +44,125 @@ extern "C" int gsl_patchify(const float* img, void* out, int B, int C, int H, in
   else if (dtype == GSL_F32) hipLaunchKernelGGL(patchify_kernel<float>, dim3(grid), dim3(256), 0, as_stream(s), img, (float*)out, B, C, H, W, p);
   else return fail(GSL_ERR_ARG, "gsl_patchify: bad dtype%s %ld", "", dtype);
   return check_launch("gsl_patchify");
+}
+
+// ------------------------------------------------------------------ K1s overlapping unfold (ViTs_face, vits_face.py:446-450, 489-491)
+// nn.Unfold(k, stride, pad) -> [B*T, ldo]: row b*T is the zero cls slot, row b*T + 1 + t window t (row-major over Lh x Lw), column
+// j = c*k*k + kh*k + kw; out-of-image taps and the K padding j >= C*k*k are 0. Every element is written.
+// The column decode is the same for every row: one LDS table per workgroup, {c*H*W + kh*W + kw, kh << 16 | kw}; padding columns carry an
+// out-of-range kh, so they fail the bounds test like a padding tap. A workgroup takes UNF_ROWS consecutive rows (neighbouring windows of
+// one image: the ~(k/stride)^2 re-reads of a pixel hit L2) and its lanes walk them as 8-column chunks, consecutive lanes on consecutive
+// chunks of a row: one 16-byte store per lane for 16-bit outputs, two for f32. The cls row gets an out-of-range h0 and comes out 0.
+constexpr int UNF_ROWS = 32;
+constexpr int UNF_MAX_LDO = 4096;      // LDS table: 8 bytes per column
+
+template <typename T>
+__device__ __forceinline__ void unf_store8(T* p, const float v[8]);
+template <>
+__device__ __forceinline__ void unf_store8<float>(float* p, const float v[8]) {
+  reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
+  reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
+}
+template <>
+__device__ __forceinline__ void unf_store8<bf16_t>(bf16_t* p, const float v[8]) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7]));
+}
+template <>
+__device__ __forceinline__ void unf_store8<f16_t>(f16_t* p, const float v[8]) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(pack2h(v[0], v[1]), pack2h(v[2], v[3]), pack2h(v[4], v[5]), pack2h(v[6], v[7]));
+}
+
+// 8 consecutive columns of one row (tab = the table at the first of them); ok = false: no load, zeros
+__device__ __forceinline__ void unf_gather8(const float* __restrict__ img, int H, int W, int h0, int w0, long base, const int2* tab, bool ok,
+                                            float v[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int2 te = tab[e];
+    const int h = h0 + (te.y >> 16), w = w0 + (te.y & 0xffff);
+    v[e] = (ok && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) ? img[base + te.x] : 0.f;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) unfold_patches_kernel(const float* __restrict__ img, T* __restrict__ out, int C, int H, int W, int k,
+                                                             int stride, int pad, int Lw, int Tn, int ldo, int rows) {
+  fp16_sat_on();
+  extern __shared__ int2 unf_tab[];      // [ldo]
+  __shared__ long r_base[UNF_ROWS];      // b*C*H*W + h0*W + w0 of the row's window
+  __shared__ int r_h0[UNF_ROWS], r_w0[UNF_ROWS];
+  const int kk = k * k, Kc = C * kk;
+  for (int j = threadIdx.x; j < ldo; j += blockDim.x) {
+    if (j < Kc) {
+      const int c = j / kk, r = j - c * kk, kh = r / k, kw = r - kh * k;
+      unf_tab[j] = make_int2(c * H * W + kh * W + kw, (kh << 16) | kw);
+    } else {
+      unf_tab[j] = make_int2(0, 0x7fff << 16);      // kh out of range: always 0
+    }
+  }
+  const int nch = ldo >> 3, per = UNF_ROWS * nch;
+  const int step_r = blockDim.x / nch, step_c = blockDim.x - step_r * nch;
+  for (int blk = blockIdx.x; blk * UNF_ROWS < rows; blk += gridDim.x) {
+    const int r0 = blk * UNF_ROWS;
+    __syncthreads();      // (the table above / the previous block's row info is published and consumed)
+    if (threadIdx.x < UNF_ROWS) {
+      const int row = r0 + threadIdx.x;
+      const int b = row / Tn, t = row - b * Tn;
+      int h0 = -(1 << 24), w0 = 0;      // cls slot (or past the end): every tap out of range
+      if (t > 0 && row < rows) {
+        const int wh = (t - 1) / Lw, ww = (t - 1) - wh * Lw;
+        h0 = wh * stride - pad;
+        w0 = ww * stride - pad;
+      }
+      r_h0[threadIdx.x] = h0;
+      r_w0[threadIdx.x] = w0;
+      r_base[threadIdx.x] = (long)b * C * H * W + (long)h0 * W + w0;
+    }
+    __syncthreads();
+    int rl = threadIdx.x / nch, ch = threadIdx.x - rl * nch;
+    // two chunks per pass (i and i + blockDim): the gathers of both are in flight before either store waits on them
+    for (int i = threadIdx.x; i < per; i += 2 * blockDim.x) {
+      if (r0 + rl >= rows) break;
+      int rl2 = rl + step_r, ch2 = ch + step_c;
+      if (ch2 >= nch) { ch2 -= nch; ++rl2; }
+      const bool in2 = i + (int)blockDim.x < per;      // (rl2 < UNF_ROWS)
+      const bool ok2 = in2 && r0 + rl2 < rows;
+      const int rb = in2 ? rl2 : rl;
+      float va[8], vb[8];
+      unf_gather8(img, H, W, r_h0[rl], r_w0[rl], r_base[rl], unf_tab + ch * 8, true, va);
+      unf_gather8(img, H, W, r_h0[rb], r_w0[rb], r_base[rb], unf_tab + ch2 * 8, ok2, vb);
+      unf_store8<T>(out + (size_t)(r0 + rl) * ldo + ch * 8, va);
+      if (ok2) unf_store8<T>(out + (size_t)(r0 + rl2) * ldo + ch2 * 8, vb);
+      rl = rl2 + step_r;
+      ch = ch2 + step_c;
+      if (ch >= nch) { ch -= nch; ++rl; }
+    }
+  }
+}
+
+extern "C" int gsl_unfold_patches(const float* img, void* out, int B, int C, int H, int W, int k, int stride, int pad, int ldo, int dtype,
+                                  gsl_stream_t s) {
+  GSL_CHECK_ARG(img && out && B > 0 && C > 0 && H > 0 && W > 0 && H < 32768 && W < 32768 && (long)C * H * W < (1L << 31), "shape");
+  GSL_CHECK_ARG(k > 0 && stride > 0 && pad >= 0 && pad < k, "k > 0, stride > 0, 0 <= pad < k");
+  GSL_CHECK_ARG(H + 2 * pad >= k && W + 2 * pad >= k, "Lh, Lw >= 1");
+  const int Lh = (H + 2 * pad - k) / stride + 1, Lw = (W + 2 * pad - k) / stride + 1;
+  GSL_CHECK_ARG((long)C * k * k <= ldo && ldo % 8 == 0 && ldo <= UNF_MAX_LDO, "C*k*k <= ldo <= 4096, ldo % 8 == 0");
+  GSL_CHECK_ARG(((uintptr_t)out & 15) == 0, "out 16-byte aligned");
+  const long Tn = 1 + (long)Lh * Lw, rows = (long)B * Tn;
+  GSL_CHECK_ARG(rows < (1L << 30), "B*T < 2^30");
+  const int nblk = (int)((rows + UNF_ROWS - 1) / UNF_ROWS);
+  const int grid = nblk;      // one block of rows per workgroup (a capped grid left half the workgroups a second block: a 2x tail)
+  const size_t lds = (size_t)ldo * sizeof(int2);
+  if (dtype == GSL_BF16)
+    hipLaunchKernelGGL(unfold_patches_kernel<bf16_t>, dim3(grid), dim3(256), lds, as_stream(s), img, (bf16_t*)out, C, H, W, k, stride, pad, Lw,
+                       (int)Tn, ldo, (int)rows);
+  else if (dtype == GSL_F16)
+    hipLaunchKernelGGL(unfold_patches_kernel<f16_t>, dim3(grid), dim3(256), lds, as_stream(s), img, (f16_t*)out, C, H, W, k, stride, pad, Lw,
+                       (int)Tn, ldo, (int)rows);
+  else if (dtype == GSL_F32)
+    hipLaunchKernelGGL(unfold_patches_kernel<float>, dim3(grid), dim3(256), lds, as_stream(s), img, (float*)out, C, H, W, k, stride, pad, Lw,
+                       (int)Tn, ldo, (int)rows);
+  else return fail(GSL_ERR_ARG, "gsl_unfold_patches: bad dtype%s %ld", "", dtype);
+  return check_launch("gsl_unfold_patches");
 }
 
 // ------------------------------------------------------------------ K10 head

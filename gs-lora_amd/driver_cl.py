@@ -37,7 +37,7 @@ import loralib as lora  # noqa: E402
 from gslora_hip.optim import create_optimizer, create_scheduler  # noqa: E402
 from util.cal_norm import get_norm_of_lora  # noqa: E402
 from util.utils import AverageMeter, calculate_prototypes, count_trainable_parameters, reinitialize_lora_parameters  # noqa: E402
-from vit_pytorch_face import ViT_face  # noqa: E402
+from vit_pytorch_face import ViT_face, ViTs_face  # noqa: E402
 
 METERS = ("losses_forget", "losses_remain", "losses_total", "losses_structure", "top1_forget", "top1_remain", "losses_prototype_forget",
           "losses_prototype_remain")
@@ -78,6 +78,8 @@ def get_args(argv=None):
     p.add_argument("--dropout", type=float, default=0.1)
     p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 (16-bit MFMA operands) | fp32 (parity mode)")
     p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
+    p.add_argument("-n", "--net", default="VIT", choices=["VIT", "VITs"],
+                   help="backbone (util/args.py -n): ViT_face, or ViTs_face with 12 x 12 windows at stride 8, pad 4 (train_own_forget_cl.py:222-236)")
     p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"],
                    help="classification head of ViT_face (config.py -head; SFaceLoss is not implemented)")
     p.add_argument("--outdir", default=None)
@@ -207,8 +209,12 @@ def main(argv=None):
     order = list(range(args.num_class))                       # reference :198-204
     random.seed(args.seed)
     random.shuffle(order)
-    model = ViT_face(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout,
-                     lora_rank=args.lora_rank, **geo)
+    if args.net == "VITs":                                    # :222-236: the same geometry with overlapping 12 x 12 windows
+        model = ViTs_face(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout,
+                          lora_rank=args.lora_rank, ac_patch_size=12, pad=4, **geo)
+    else:
+        model = ViT_face(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout,
+                         lora_rank=args.lora_rank, **geo)
     lora.mark_only_lora_as_trainable(model)                   # :314-317
     print("trainable parameters:", count_trainable_parameters(model))
     model = model.to(dev).set_compute_dtype(args.dtype)
@@ -228,7 +234,8 @@ def main(argv=None):
                     te_f=mk(subset(x_te, y_te, forget_cls), 5 * args.batch_size, False),
                     te_r=mk(subset(x_te, y_te, remain_cls), 5 * args.batch_size, False), protos=protos, info=dict(forget_cls=forget_cls))
 
-    report, ema_model = run_tasks(model, args, task_data, dev, out, geo["depth"])
+    cfg = {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net}
+    report, ema_model = run_tasks(model, args, task_data, dev, out, geo["depth"], cfg=cfg)
     return report, out, (model if ema_model is None else (model, ema_model))
 
 

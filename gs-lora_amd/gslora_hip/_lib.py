@@ -29,6 +29,7 @@ SIGNATURES = {
     "gsl_version": [],
     "gsl_last_error": [],
     "gsl_patchify": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "gsl_unfold_patches": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gsl_gemm_nt": [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _i,
                     _vp, _vp, _i, _f, _u64, _u32, _vp],
     "gsl_gemm_nt_lora": [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i,

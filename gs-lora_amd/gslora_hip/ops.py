@@ -49,6 +49,30 @@ def patchify(img, p, dtype):
     return out
 
 
+def unfold_geometry(H, W, k, stride, pad):
+    """(Lh, Lw) windows of nn.Unfold(k, stride=stride, padding=pad) over an H x W image."""
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def unfold_patches(img, k, stride, pad, dtype):
+    """nn.Unfold(k, stride, pad)(img).transpose(1, 2) with a zero cls row per image and the feature dimension zero-padded to a multiple
+    of 64 (the patch GEMM's K): [B*T, Kpad], T = 1 + Lh*Lw, Kpad = ceil(C*k*k / 64)*64. img: one [B, C, H, W] batch or a list of batches
+    of one image shape; the batches land in consecutive row ranges of the output."""
+    parts = list(img) if isinstance(img, (tuple, list)) else [img]
+    _need(*parts)
+    _, Cc, H, W = parts[0].shape
+    Lh, Lw = unfold_geometry(H, W, k, stride, pad)
+    T = 1 + Lh * Lw
+    kpad = -(-Cc * k * k // 64) * 64
+    out = torch.empty(sum(t.shape[0] for t in parts) * T, kpad, device=parts[0].device, dtype=dtype)
+    row = 0
+    for t in parts:
+        L.check(L.load().gsl_unfold_patches(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, k, stride, pad, kpad, code(dtype), _stream()),
+                "gsl_unfold_patches")
+        row += t.shape[0] * T
+    return out
+
+
 # optional per-kernel timing hook used by bench.py: {tag: [(start_event, end_event), ...]} recorded on the
 # stream the kernel is launched on (torch's current stream == the hipStream_t handed to the C ABI)
 PROFILE = None

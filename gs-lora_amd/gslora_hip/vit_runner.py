@@ -100,13 +100,20 @@ class ModelSpec:
                     easy_margin; reference :72-143) — cos_s / cos_m are the head's s and m — or "softmax" (nn.Linear with bias,
                     reference :14-52: logits only when a label is passed, the label itself is ignored).
       ModifiedViT   (vit_pytorch_face/modified_VIT.py:5-45 over torchvision vit_b_16): conv16 patch embedding, QKV bias,
-                    LN eps 1e-6, scale head_dim^-0.5, nn.Linear head with bias, the label argument is ignored."""
+                    LN eps 1e-6, scale head_dim^-0.5, nn.Linear head with bias, the label argument is ignored.
+      ViTs_face     (vit_pytorch_face/vits_face.py, reference vits_face.py:414-509): ViT_face with an overlapping patch stage —
+                    nn.Unfold(patch_kernel, patch_stride, patch_pad) windows (gsl_unfold_patches) into the same Linear embedding, whose
+                    weight is zero-padded along K to a multiple of 64; num_tokens = 1 + the number of windows."""
     __slots__ = ("patch_size", "num_tokens", "dim", "heads", "attn_scale", "ln_eps", "dropout_p", "emb_dropout_p", "lora_rank",
                  "patch_w", "patch_is_conv", "patch_b", "cls", "pos", "blocks", "final_ln", "head_kind", "head_w", "head_b",
-                 "cos_s", "cos_m", "easy_margin", "lora_site", "pool")
+                 "cos_s", "cos_m", "easy_margin", "lora_site", "pool", "patch_kernel", "patch_stride", "patch_pad", "image_size")
 
     def __init__(self, **kw):
         kw.setdefault("easy_margin", False)    # ArcFace only
+        kw.setdefault("patch_kernel", 0)       # > 0: overlapping unfold windows of this size (ViTs_face); 0: gsl_patchify's p x p tiles
+        kw.setdefault("patch_stride", 0)       # (the unfold's stride and zero padding)
+        kw.setdefault("patch_pad", 0)
+        kw.setdefault("image_size", None)      # (checked against the input on the unfold path)
         kw.setdefault("lora_site", "ffn")      # "ffn" (GS-LoRA) or "attention" (--lora_pos Attention ablation)
         kw.setdefault("pool", "cls")           # "cls" (token 0) or "mean" (mean over the tokens, vit_face.py:540)
         for k in self.__slots__:
@@ -272,6 +279,14 @@ class ViTRunner:
             w2 = p.permute(0, 2, 3, 1).reshape(p.shape[0], -1).contiguous()
             return w2 if dtype == torch.float32 else ops.cast(w2, dtype)
         return self._cached(self._wcache, (name, "conv", dtype), param, build)
+
+    def w_kpad(self, name, param, kpad, dtype):
+        """[D, K] weight zero-padded to [D, kpad] (the patch GEMM of the unfold path: K = C*k*k need not be a multiple of 64)."""
+        def build(p):
+            w2 = torch.zeros(p.shape[0], kpad, device=p.device, dtype=torch.float32)
+            w2[:, :p.shape[1]] = p
+            return w2 if dtype == torch.float32 else ops.cast(w2, dtype)
+        return self._cached(self._wcache, (name, "kpad", kpad, dtype), param, build)
 
     def wT(self, name, param, dtype):
         """[K,N] transposed operand (dX GEMMs)."""
@@ -440,13 +455,22 @@ class ViTRunner:
         s_lora = (1.0 / r) if r > 0 else 0.0
         eps = sp.ln_eps
 
-        patches = ops.patchify(parts, sp.patch_size, dt)
+        if sp.patch_kernel:      # ViTs_face: overlapping zero-padded windows, K padded to a multiple of 64 (weight and patches alike)
+            if sp.image_size is not None and tuple(img.shape[2:]) != (sp.image_size, sp.image_size):
+                raise ValueError(f"{type(m).__name__}: input images are {tuple(img.shape[2:])}, the model was built for "
+                                 f"{sp.image_size} x {sp.image_size}")
+            patches = ops.unfold_patches(parts, sp.patch_kernel, sp.patch_stride, sp.patch_pad, dt)
+            if patches.shape[0] != B * T:
+                raise ValueError(f"{type(m).__name__}: the unfold yields {patches.shape[0] // B} tokens per image, the model has {T}")
+            pw = self.w_kpad("pe", sp.patch_w, patches.shape[1], dt)
+        else:
+            patches = ops.patchify(parts, sp.patch_size, dt)
+            pw = self.w_conv("pe", sp.patch_w, dt) if sp.patch_is_conv else self.w("pe", sp.patch_w, dt)
         xbf = dt in OP16 and FWD_STREAM != "f32"        # the residual stream in 2 bytes per element
         xf16 = xbf and (FWD_STREAM == "f16" or dt == torch.float16)      # (fp16 operands: the 16-bit stream is fp16 too)
         xdt = (torch.float16 if xf16 else torch.bfloat16) if xbf else torch.float32            # dtype of the residual stream
         epi_res = (L.EPI_BIAS_RES_F16 if xf16 else L.EPI_BIAS_RES_BF16) if xbf else L.EPI_BIAS_RES_F32
         x = torch.empty(M, D, device=img.device, dtype=xdt)
-        pw = self.w_conv("pe", sp.patch_w, dt) if sp.patch_is_conv else self.w("pe", sp.patch_w, dt)
         ops.gemm_nt(patches, pw, x, epilogue=(L.EPI_PATCH_F16 if xf16 else L.EPI_PATCH_BF16) if xbf else L.EPI_PATCH, bias=sp.patch_b.detach(),
                     pos=sp.pos.detach()[0, :T].contiguous(), cls=sp.cls.detach().reshape(-1), T=T,
                     p_drop=p_emb, seed=seed, site=SITE_EMB | sflag)

@@ -330,4 +330,10 @@ def _not_in_scope(name, why):
 
 ViT_face_low = _not_in_scope("ViT_face_low", "LIRF baseline half-network, reference vit_face.py:551-781")
 ViT_face_up = _not_in_scope("ViT_face_up", "LIRF baseline half-network, reference vit_face.py:551-781")
-ViTs_face = _not_in_scope("ViTs_face", "overlapping-patch variant, not used by any GS-LoRA config")
+
+
+def __getattr__(name):      # vit_face.ViTs_face keeps resolving: the overlapping-patch model lives in vits_face.py (as in the reference)
+    if name == "ViTs_face":
+        from .vits_face import ViTs_face
+        return ViTs_face
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

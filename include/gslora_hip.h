@@ -84,6 +84,13 @@ GSL_API const char* gsl_last_error(void);
  * img f32 [B,C,H,W] -> out[dtype] [B*T, p*p*C], T = 1 + (H/p)*(W/p); row b*T (cls slot) is zero. */
 GSL_API int gsl_patchify(const float* img, void* out, int B, int C, int H, int W, int p, int dtype, gsl_stream_t s);
 
+/* ---- K1s overlapping patch gather of ViTs_face: nn.Unfold(k, stride, pad)(img).transpose(1, 2) (vits_face.py:446-450, 489-491).
+ * img f32 [B,C,H,W] -> out[dtype] [B*T, ldo], T = 1 + Lh*Lw, Lh = (H + 2*pad - k)/stride + 1 (Lw likewise). Row b*T (cls slot) is zero,
+ * row b*T + 1 + t holds window t (row-major over Lh x Lw) in Unfold's order j = c*k*k + kh*k + kw; taps outside the image and the K padding
+ * C*k*k <= j < ldo are zero. Every element of out is written. 0 <= pad < k, ldo % 8 == 0, C*k*k <= ldo <= 4096, out 16-byte aligned. */
+GSL_API int gsl_unfold_patches(const float* img, void* out, int B, int C, int H, int W, int k, int stride, int pad, int ldo, int dtype,
+                               gsl_stream_t s);
+
 /* ---- K3/K5/K6/K7/K8 dense NT GEMM with an optional second K segment (the LoRA rank-r term)
  * and a fused epilogue. Replaces F.linear + loralib.Linear.forward (vit_face.py:330-334,349-356)
  * and their autograd dX.
