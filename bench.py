@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — forgetting-step images/sec of the GS-LoRA step on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config 2|4|5] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config 2|4|5] [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU over RCCL. Either the driver launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or, when WORLD_SIZE is not set,
@@ -20,8 +20,12 @@ all-reduce when N > 1, AdamW). Prints ONE JSON line on rank 0.
      dropout 0 (torchvision default), the step replayed as HIP-graph segments (what the engines pick below 256 images)   [configs[3]]
   5  few-shot GS-LoRA++: ViT-P8S8 d6 r=8, per-GPU batch 4 + 4, BND_pro 50, pro_f_weight 0.017 (scripts/run_cl_forget.sh:223-235),
      HIP-graph replay (launch-bound regime)                                                                  [configs[4]]
-For graph-replayed configs the per-kernel HIP-event timings of `roofline` come from eager steps run AFTER the timed region (a replay
-makes no Python launch to bracket); the kernels are the same.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line (for eager configs its
+`roofline` comes from HIP events around launches inside the timed region, at no extra run). `--full` adds the legs that run after the
+timed region: the CPU baseline (config 2), the bf16 `secondary` leg (config 2, fp16), the `eval` leg, the LayerNorm / attention
+`memory_bound_kernels` steps (eager configs) and, for graph-replayed configs, the 3 eager steps whose per-kernel HIP-event timings give
+their `roofline` (a replay makes no Python launch to bracket; the kernels are the same). The --no-* options drop single legs of --full.
 """
 import argparse
 import json
@@ -328,13 +332,15 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--dtype", default="fp16", help="fp16 (default since round 5: IEEE fp16 MFMA operands, loss-scaled backward) | bf16 | fp32 (parity mode)")
     ap.add_argument("--dropout", type=float, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the CPU baseline, the secondary, eval and "
+                    "memory-bound-kernel legs and, for graph-replayed configs, the eager steps of the roofline (off: only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (N = 1, config 2 only)")
     ap.add_argument("--graph", action="store_true", default=None, help="replay the step as captured HIP graph segments (the engines' default for launch-bound batches; default: the config's)")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
-    ap.add_argument("--no-eval", action="store_true", help="skip the eval_data leg (N = 1 only: test-set evaluation throughput, batches of 5 x batch)")
+    ap.add_argument("--no-eval", action="store_true", help="with --full: skip the eval_data leg (N = 1 only: test-set evaluation throughput, batches of 5 x batch)")
     ap.add_argument("--eval-batches", type=int, default=3)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary leg (N = 1, config 2, --dtype fp16 only: the same step on bf16 operands = BASELINE configs[1] as written, 3 warm-up + 10 timed steps after the timed region)")
-    ap.add_argument("--no-mem-kernels", action="store_true", help="skip the two extra steps after the timed region that time the LayerNorm / attention launches (roofline.memory_bound_kernels); the profiling scripts pass it so that a trace holds warmup + steps only")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary leg (N = 1, config 2, --dtype fp16 only: the same step on bf16 operands = BASELINE configs[1] as written, 3 warm-up + 10 timed steps after the timed region)")
+    ap.add_argument("--no-mem-kernels", action="store_true", help="with --full: skip the two extra steps after the timed region that time the LayerNorm / attention launches (roofline.memory_bound_kernels)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (its 8 meters, "
                     "the updated LoRA parameters and their gradients) as DIR/<name>.npy in float32, on rank 0")
     args = ap.parse_args()
@@ -344,6 +350,8 @@ def main():
     args.batch = C["batch"] if args.batch is None else args.batch
     args.dropout = C["dropout"] if args.dropout is None else args.dropout
     args.graph = C["graph"] if args.graph is None else args.graph
+    if not args.full:
+        args.no_cpu_baseline = args.no_eval = args.no_secondary = args.no_mem_kernels = True
 
     stub = os.environ.get("GSL_BENCH_STUB") == "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -423,9 +431,10 @@ def main():
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
         if args.graph:      # a replay makes no Python launch to bracket: time the same kernels in eager steps OUTSIDE the timed region
             ops.PROFILE = {"ffn1": [], "ffn2dx": []}
-            for _ in range(3):
-                wl.step(eager=True)
-            fence()
+            if args.full:       # (a plain run carries no roofline for graph-replayed configs)
+                for _ in range(3):
+                    wl.step(eager=True)
+                fence()
             prof_source = "HIP events around every launch of 3 eager steps run after the timed region (the timed steps are HIP-graph replays)"
         prof, ops.PROFILE = ops.PROFILE, None
         # north_star: "achieved HBM GB/s on the norm/softmax kernels": LayerNorm and attention launches bracketed by HIP events in TWO extra
@@ -519,7 +528,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype,
             "dtype_note": {"fp16": "IEEE fp16 MFMA operands (v_mfma_f32_16x16x32_f16: the rate and bytes of bf16, 11-bit significand), f32 accumulate, "
-                                   "backward on loss-scaled gradients; --dtype bf16 runs the same kernels on bf16 operands (secondary leg). "
+                                   "backward on loss-scaled gradients; --dtype bf16 runs the same kernels on bf16 operands (the secondary leg of --full). "
                                    "Two sub-16-bit approximations sit on the path in both 16-bit modes: GELU'*dropout-mask is saved as an 8-bit "
                                    "fixed-point code (q = round(GELU' * keep * 200 + 26), abs. error <= 0.0025/(1-p)), and GELU / GELU' of the fused "
                                    "FFN1 epilogue come from a 4096-entry table (|dPhi| <= 4.5e-4); both are inside the accuracy statistics of DESIGN.md section 7",
@@ -569,8 +578,8 @@ def main():
             out["eval"] = eval_res
         if world == 1 and not args.no_cpu_baseline and not stub and args.config == 2:
             out["cpu_baseline"] = cpu_baseline()
-        elif not stub and args.config != 2:
-            out["cpu_baseline_note"] = "timed on the configuration the metric is quoted on only (python bench.py --config 2)"
+        elif args.full and not stub and args.config != 2:
+            out["cpu_baseline_note"] = "timed on the configuration the metric is quoted on only (python bench.py --config 2 --full)"
     # the JSON line must be the LAST line of the job's stdout: RCCL writes its version banner through C stdio, which a piped stdout
     # only flushes at exit (i.e. after Python's own print) — push every rank's C buffer out first, then let rank 0 print
     sys.stdout.flush()
