@@ -1,9 +1,10 @@
-// attention.hip — softmax(Q Kᵀ · scale) V for head_dim 64, no mask, T <= 224 tokens
+// attention.hip — softmax(Q Kᵀ · scale) V for head_dim 64, no mask, T <= 1025 tokens (GSL_ATTN_MAX_T)
 // (reference vit_pytorch_face/vit_face.py:358-376; T = 197 for both ViT-P8S8 and ViT-B/16).
 //
-// One workgroup per (image, head): the whole K/V (or Q/dO) panel of a head fits in LDS
+// T <= 224 (the cls forward: T <= 256): one workgroup per (image, head): the whole K/V (or Q/dO) panel of a head fits in LDS
 // (197 x 64 bf16 = 25 KB), so there is no online-softmax loop — each wave owns 16-query (or
 // 16-key) tiles and keeps a full score row-block in registers.
+// T > 224: the long-sequence kernels further down stream 64-row panels through LDS with an online softmax (see "long sequences").
 //
 // bf16 path (MFMA v_mfma_f32_16x16x32_bf16, f32 accumulate):
 //   * scores are computed TRANSPOSED (Sᵀ = K Qᵀ) so that a lane owns one query column: the row
@@ -25,6 +26,7 @@
 //   the cls-query kernels of the last block are templated on the element type.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "gsl_common.h"
@@ -1602,12 +1604,620 @@ __global__ __launch_bounds__(256) void attn_fwd_cls_kernel(const T* __restrict__
   if (tid == 0) lse_cls[(size_t)b * H + h] = m + logf(e);
 }
 
+// =====================================================================================
+// long sequences (single-panel limit < T <= GSL_ATTN_MAX_T): the K / V (or Q / dO) rows of an item stream through LDS in
+// panels of 64 rows instead of sitting there whole. Entered only above today's limits (T > 224; T > 256 for the cls forward), so every
+// shorter sequence keeps its launch sequence and its bits.
+//   forward: waves own one 16-query tile each, scores transposed (S^T = K Q^T, a lane owns a query column) as in the single-panel kernels;
+//     per panel the running max is updated BEFORE the panel is exponentiated (textbook online softmax: m' = max(m, panel max),
+//     l = l e^(m - m') + sum e^(s - m'), O = O e^(m - m') + P V), keys >= T are -inf before the max, rows >= T are never stored.
+//   backward: the two-kernel split form generalised to panels — dQ (waves own query tiles, walk the K / V panels; writes delta =
+//     rowsum(dO o)) and dK / dV (waves own key tiles, walk the Q / dO panels; reads delta). No atomics, every sum in a fixed order:
+//     deterministic. S and dP are computed in both kernels (seven MFMA products per tile pair instead of five).
+//   Panels are double-buffered: the global loads of panel p + 1 are in registers while panel p is computed, then stored into the other
+//   buffer, one workgroup barrier per panel.
+//   Work split: a workgroup owns a block of <= 16 tiles of one item; an item's blocks share an XCD (workgroup w runs on XCD w % 8), so
+//   its K / V (Q / dO) rows are re-read from that XCD's L2. With fewer blocks than CUs the tiles of an item are split further (>= 4
+//   tiles per workgroup).
+// f32 (parity mode): the same panel structure on plain f32 FMAs, one lane per query (forward, dQ) or two lanes per key (dK / dV).
+// =====================================================================================
+// the bound is GSL_ATTN_MAX_T of include/gslora_hip.h; its value is spelled into the argument-check message
+#define GSL_ATTN_STR2(x) #x
+#define GSL_ATTN_STR(x) GSL_ATTN_STR2(x)
+#define GSL_ATTN_MAX_T_MSG "T <= " GSL_ATTN_STR(GSL_ATTN_MAX_T) " tokens (GSL_ATTN_MAX_T)"
+constexpr int PK = 64;                // rows per streamed panel
+typedef unsigned int pu32x4_t __attribute__((ext_vector_type(4)));
+// one 64-row panel of two [T][64] 16-bit operands in flight: 512 16-byte chunks each, workgroups of >= 256 threads
+struct PanelRegs {
+  pu32x4_t a[2], b[2];
+  float la, lb;      // one float of two [T] vectors (threads < 64; the dK / dV kernel's lse and delta)
+};
+__device__ __forceinline__ void panel_load(PanelRegs& r, const bf16_t* s0, long ld0, const bf16_t* s1, long ld1, int row0, int T) {
+  const pu32x4_t z = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int idx = threadIdx.x + it * blockDim.x, t = idx >> 3, c = idx & 7;
+    r.a[it] = z; r.b[it] = z;
+    if (idx < PK * 8 && row0 + t < T) {
+      r.a[it] = *reinterpret_cast<const pu32x4_t*>(s0 + (size_t)(row0 + t) * ld0 + c * 8);
+      r.b[it] = *reinterpret_cast<const pu32x4_t*>(s1 + (size_t)(row0 + t) * ld1 + c * 8);
+    }
+  }
+}
+__device__ __forceinline__ void panel_store(bf16_t* d0, bf16_t* d1, const PanelRegs& r) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int idx = threadIdx.x + it * blockDim.x, t = idx >> 3, c = idx & 7;
+    if (idx < PK * 8) {
+      *reinterpret_cast<pu32x4_t*>(d0 + lds_off(t, c * 8)) = r.a[it];
+      *reinterpret_cast<pu32x4_t*>(d1 + lds_off(t, c * 8)) = r.b[it];
+    }
+  }
+}
+// workgroup -> (item, tile block): the nb blocks of an item run on one XCD. Returns false for the padding workgroups of the last group.
+__device__ __forceinline__ bool long_item(int nitems, int nb, int& item, int& blk) {
+  const int w = blockIdx.x, x = w & 7, j = w >> 3;
+  blk = j % nb;
+  item = (j / nb) * 8 + x;
+  return item < nitems;
+}
+
+__global__ __launch_bounds__(1024) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
+                                                             int T, int H, float scale, int hm, int nitems, int nb) {
+  GSL_OP16_KERNEL_ENTRY();
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[2][PK * KLD];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[2][PK * KLD];
+  int item, blk;
+  if (!long_item(nitems, nb, item, blk)) return;
+  const int b = item / H, h = item % H;
+  const long ldi = hm ? (long)HD : 3L * H * HD, ko = hm ? (long)T * HD : (long)H * HD;
+  const bf16_t* qb = qkv + (hm ? (size_t)(b * H + h) * 3 * T * HD : (size_t)b * T * ldi + h * HD);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fc = lane >> 4;
+  const int nqt = (T + 15) / 16, qt = blk * (int)(blockDim.x >> 6) + wave;
+  const bool active = qt < nqt;      // wave-uniform; idle waves still load panels and take every barrier
+  const int qr = qt * 16 + fr;
+  bf16x8_t qf0, qf1;
+  {
+    const bf16_t* qrow = qb + (size_t)min(qr, T - 1) * ldi;
+    qf0 = gl_frag(qrow, 0, fc); qf1 = gl_frag(qrow, 1, fc);
+  }
+  PanelRegs pr;
+  panel_load(pr, qb + ko, ldi, qb + 2 * ko, ldi, 0, T);
+  panel_store(Ks[0], Vs[0], pr);
+  wg_barrier_lds();
+  const int np = (T + PK - 1) / PK;
+  const float c2 = scale * 1.4426950408889634f;
+  f32x4_t oacc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m = -3.0e38f, l = 0.f;
+#pragma unroll 1
+  for (int p = 0; p < np; ++p) {
+    const int cur = p & 1;
+    if (p + 1 < np) panel_load(pr, qb + ko, ldi, qb + 2 * ko, ldi, (p + 1) * PK, T);
+    if (active) {
+      const bf16_t* K = Ks[cur];
+      const bf16_t* V = Vs[cur];
+      f32x4_t s[4];
+      float pm = -3.0e38f;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+        acc = mfma16(lds_frag_rm(K, kt * 16 + fr, 0, fc), qf0, acc);
+        acc = mfma16(lds_frag_rm(K, kt * 16 + fr, 1, fc), qf1, acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {      // acc[r] = S[key p*64 + kt*16 + fc*4 + r][query qr] (raw, unscaled)
+          if (p * PK + kt * 16 + fc * 4 + r >= T) acc[r] = -3.0e38f;
+          pm = fmaxf(pm, acc[r]);
+        }
+        s[kt] = acc;
+      }
+      pm = fmaxf(pm, __shfl_xor(pm, 16, 64));
+      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
+      const float mn = fmaxf(m, pm), mc = mn * c2;
+      const float alpha = __builtin_amdgcn_exp2f(fmaf(m, c2, -mc));      // 0 on the first panel (m = -3e38)
+      float ls = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], c2, -mc)); ls += s[kt][r]; }
+      ls += __shfl_xor(ls, 16, 64);
+      ls += __shfl_xor(ls, 32, 64);
+      l = fmaf(l, alpha, ls);
+      m = mn;
+      Frag pf[2];
+#pragma unroll
+      for (int q2 = 0; q2 < 2; ++q2)
+        pf[q2].u = make_uint4(pack2o(s[2 * q2][0], s[2 * q2][1]), pack2o(s[2 * q2][2], s[2 * q2][3]),
+                              pack2o(s[2 * q2 + 1][0], s[2 * q2 + 1][1]), pack2o(s[2 * q2 + 1][2], s[2 * q2 + 1][3]));
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) oacc[dt][r] *= alpha;
+#pragma unroll
+        for (int q2 = 0; q2 < 2; ++q2) oacc[dt] = mfma16(lds_frag_trr(V, dt, q2, lane), pf[q2].v, oacc[dt]);
+      }
+    }
+    if (p + 1 < np) {      // the other buffer was last read before the previous barrier
+      panel_store(Ks[cur ^ 1], Vs[cur ^ 1], pr);
+      wg_barrier_lds();
+    }
+  }
+  if (active) {
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)      // oacc[dt][r] = O[q = qr][d = dt*16 + fc*4 + r]
+      if (qr < T) store4bf(o + ((size_t)b * T + qr) * (H * HD) + h * HD + dt * 16 + fc * 4, oacc[dt], inv);
+    if (fc == 0 && qr < T) lse[((size_t)b * H + h) * T + qr] = m * scale + __logf(l);
+  }
+}
+
+// backward dQ (16-bit): waves own query tiles, K / V panels stream; delta = rowsum(dO o) -> delta_ws for the dK / dV kernel
+__global__ __launch_bounds__(1024) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+                                                                const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
+                                                                bf16_t* __restrict__ dqkv, float* __restrict__ delta, int T, int H, float scale,
+                                                                int hm, int nitems, int nb) {
+  GSL_OP16_KERNEL_ENTRY();
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[2][PK * KLD];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[2][PK * KLD];
+  int item, blk;
+  if (!long_item(nitems, nb, item, blk)) return;
+  const int b = item / H, h = item % H;
+  const long ld = 3L * H * HD, ldo = (long)H * HD;
+  const long ldi = hm ? (long)HD : ld, ko = hm ? (long)T * HD : (long)H * HD;
+  const bf16_t* qb = qkv + (hm ? (size_t)(b * H + h) * 3 * T * HD : (size_t)b * T * ld + h * HD);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fc = lane >> 4;
+  const int nqt = (T + 15) / 16, qt = blk * (int)(blockDim.x >> 6) + wave;
+  const bool active = qt < nqt;
+  const int qr = qt * 16 + fr, qrc = min(qr, T - 1);
+  bf16x8_t qf0, qf1;
+  Frag dof0, dof1;
+  float dl = 0.f;
+  {
+    const bf16_t* qrow = qb + (size_t)qrc * ldi;
+    const bf16_t* dorow = d_o + ((size_t)b * T + qrc) * ldo + h * HD;
+    const bf16_t* orow = o + ((size_t)b * T + qrc) * ldo + h * HD;
+    Frag of0, of1;
+    qf0 = gl_frag(qrow, 0, fc); qf1 = gl_frag(qrow, 1, fc);
+    dof0.v = gl_frag(dorow, 0, fc); dof1.v = gl_frag(dorow, 1, fc);
+    of0.v = gl_frag(orow, 0, fc); of1.v = gl_frag(orow, 1, fc);
+    const uint32_t a[8] = {dof0.u.x, dof0.u.y, dof0.u.z, dof0.u.w, dof1.u.x, dof1.u.y, dof1.u.z, dof1.u.w};
+    const uint32_t c[8] = {of0.u.x, of0.u.y, of0.u.z, of0.u.w, of1.u.x, of1.u.y, of1.u.z, of1.u.w};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float a0, a1, c0, c1;
+      unpack2o(a[i], a0, a1); unpack2o(c[i], c0, c1);
+      dl += a0 * c0;
+      dl += a1 * c1;
+    }
+    dl += __shfl_xor(dl, 16, 64);
+    dl += __shfl_xor(dl, 32, 64);
+  }
+  if (active && fc == 0 && qr < T) delta[((size_t)b * H + h) * T + qr] = dl;
+  const float c2 = scale * 1.4426950408889634f, lq2 = lse[((size_t)b * H + h) * T + qrc] * 1.4426950408889634f;
+  PanelRegs pr;
+  panel_load(pr, qb + ko, ldi, qb + 2 * ko, ldi, 0, T);
+  panel_store(Ks[0], Vs[0], pr);
+  wg_barrier_lds();
+  const int np = (T + PK - 1) / PK;
+  f32x4_t dqa[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dqa[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int p = 0; p < np; ++p) {
+    const int cur = p & 1;
+    if (p + 1 < np) panel_load(pr, qb + ko, ldi, qb + 2 * ko, ldi, (p + 1) * PK, T);
+    if (active) {
+      const bf16_t* K = Ks[cur];
+      const bf16_t* V = Vs[cur];
+      Frag dsf[2];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        f32x4_t sa = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+        sa = mfma16(lds_frag_rm(K, kt * 16 + fr, 0, fc), qf0, sa);
+        sa = mfma16(lds_frag_rm(K, kt * 16 + fr, 1, fc), qf1, sa);
+        dp = mfma16(lds_frag_rm(V, kt * 16 + fr, 0, fc), dof0.v, dp);
+        dp = mfma16(lds_frag_rm(V, kt * 16 + fr, 1, fc), dof1.v, dp);
+        float ds[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {      // dS without the softmax scale (applied once at the store)
+          float pv = __builtin_amdgcn_exp2f(fmaf(sa[r], c2, -lq2));
+          if (p * PK + kt * 16 + fc * 4 + r >= T) pv = 0.f;
+          ds[r] = pv * (dp[r] - dl);
+        }
+        if ((kt & 1) == 0) { dsf[kt / 2].u.x = pack2o(ds[0], ds[1]); dsf[kt / 2].u.y = pack2o(ds[2], ds[3]); }
+        else { dsf[kt / 2].u.z = pack2o(ds[0], ds[1]); dsf[kt / 2].u.w = pack2o(ds[2], ds[3]); }
+      }
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int q2 = 0; q2 < 2; ++q2) dqa[dt] = mfma16(lds_frag_trr(K, dt, q2, lane), dsf[q2].v, dqa[dt]);
+    }
+    if (p + 1 < np) {
+      panel_store(Ks[cur ^ 1], Vs[cur ^ 1], pr);
+      wg_barrier_lds();
+    }
+  }
+  if (active && qr < T) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) store4bf(dqkv + ((size_t)b * T + qr) * ld + h * HD + dt * 16 + fc * 4, dqa[dt], scale);
+  }
+}
+
+// backward dK / dV (16-bit): waves own key tiles (the key on the lane), Q / dO panels and their lse / delta stream
+__global__ __launch_bounds__(1024) void attn_bwd_dkv_long_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ d_o,
+                                                                 const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                 bf16_t* __restrict__ dqkv, int T, int H, float scale, int hm, int nitems, int nb) {
+  GSL_OP16_KERNEL_ENTRY();
+  __shared__ __attribute__((aligned(16))) bf16_t Qs[2][PK * KLD];
+  __shared__ __attribute__((aligned(16))) bf16_t Gs[2][PK * KLD];   // dO row-major
+  __shared__ __attribute__((aligned(16))) float lse_s[2][PK];       // log2 units; padded queries 1e30 -> p = 0
+  __shared__ __attribute__((aligned(16))) float del_s[2][PK];
+  int item, blk;
+  if (!long_item(nitems, nb, item, blk)) return;
+  const int b = item / H, h = item % H;
+  const long ld = 3L * H * HD, ldo = (long)H * HD;
+  const long ldi = hm ? (long)HD : ld, ko = hm ? (long)T * HD : (long)H * HD;
+  const bf16_t* qb = qkv + (hm ? (size_t)(b * H + h) * 3 * T * HD : (size_t)b * T * ld + h * HD);
+  const bf16_t* dob = d_o + (size_t)b * T * ldo + h * HD;
+  const float* lrow = lse + ((size_t)b * H + h) * T;
+  const float* drow = delta + ((size_t)b * H + h) * T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fc = lane >> 4;
+  const int nkt = (T + 15) / 16, kt = blk * (int)(blockDim.x >> 6) + wave;
+  const bool active = kt < nkt;
+  const int kr = kt * 16 + fr, krc = min(kr, T - 1);
+  bf16x8_t kf0, kf1, vf0, vf1;
+  {
+    const bf16_t* krow = qb + (size_t)krc * ldi + ko;
+    const bf16_t* vrow = qb + (size_t)krc * ldi + 2 * ko;
+    kf0 = gl_frag(krow, 0, fc); kf1 = gl_frag(krow, 1, fc);
+    vf0 = gl_frag(vrow, 0, fc); vf1 = gl_frag(vrow, 1, fc);
+  }
+  auto load = [&](PanelRegs& r, int row0) {
+    panel_load(r, qb, ldi, dob, ldo, row0, T);
+    if (threadIdx.x < PK) {
+      const int t = row0 + threadIdx.x;
+      r.la = (t < T) ? lrow[t] * 1.4426950408889634f : 1.0e30f;
+      r.lb = (t < T) ? drow[t] : 0.f;
+    }
+  };
+  auto store = [&](int buf, const PanelRegs& r) {
+    panel_store(Qs[buf], Gs[buf], r);
+    if (threadIdx.x < PK) { lse_s[buf][threadIdx.x] = r.la; del_s[buf][threadIdx.x] = r.lb; }
+  };
+  PanelRegs pr;
+  load(pr, 0);
+  store(0, pr);
+  wg_barrier_lds();
+  const int np = (T + PK - 1) / PK;
+  const float c2 = scale * 1.4426950408889634f;
+  f32x4_t adk[4], adv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { adk[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; adv[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll 1
+  for (int p = 0; p < np; ++p) {
+    const int cur = p & 1;
+    if (p + 1 < np) load(pr, (p + 1) * PK);
+    if (active) {
+      const bf16_t* Q = Qs[cur];
+      const bf16_t* G = Gs[cur];
+#pragma unroll
+      for (int qp = 0; qp < 2; ++qp) {
+        Frag pf, dsf;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const int qt = 2 * qp + half;
+          const bf16x8_t q0 = lds_frag_rm(Q, qt * 16 + fr, 0, fc), q1 = lds_frag_rm(Q, qt * 16 + fr, 1, fc);
+          const bf16x8_t g0 = lds_frag_rm(G, qt * 16 + fr, 0, fc), g1 = lds_frag_rm(G, qt * 16 + fr, 1, fc);
+          const float4 l4 = *reinterpret_cast<const float4*>(&lse_s[cur][qt * 16 + fc * 4]);
+          const float4 d4 = *reinterpret_cast<const float4*>(&del_s[cur][qt * 16 + fc * 4]);
+          const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
+          f32x4_t sa = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+          sa = mfma16(q0, kf0, sa);      // S[q = qt*16 + fc*4 + r][key = kr]
+          sa = mfma16(q1, kf1, sa);
+          dp = mfma16(g0, vf0, dp);      // dP[q][key]
+          dp = mfma16(g1, vf1, dp);
+          float pv[4], ds[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            pv[r] = __builtin_amdgcn_exp2f(fmaf(sa[r], c2, -lv[r]));
+            ds[r] = pv[r] * (dp[r] - dv[r]);      // softmax scale applied once to dK at the store
+          }
+          if (half == 0) {
+            pf.u.x = pack2o(pv[0], pv[1]); pf.u.y = pack2o(pv[2], pv[3]);
+            dsf.u.x = pack2o(ds[0], ds[1]); dsf.u.y = pack2o(ds[2], ds[3]);
+          } else {
+            pf.u.z = pack2o(pv[0], pv[1]); pf.u.w = pack2o(pv[2], pv[3]);
+            dsf.u.z = pack2o(ds[0], ds[1]); dsf.u.w = pack2o(ds[2], ds[3]);
+          }
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          adv[dt] = mfma16(lds_frag_trr(G, dt, qp, lane), pf.v, adv[dt]);      // dV^T[d][key]
+          adk[dt] = mfma16(lds_frag_trr(Q, dt, qp, lane), dsf.v, adk[dt]);     // dK^T[d][key]
+        }
+      }
+    }
+    if (p + 1 < np) {
+      store(cur ^ 1, pr);
+      wg_barrier_lds();
+    }
+  }
+  if (active && kr < T) {
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      bf16_t* base = dqkv + ((size_t)b * T + kr) * ld + h * HD + dt * 16 + fc * 4;
+      store4bf(base + H * HD, adk[dt], scale);
+      store4bf(base + 2 * H * HD, adv[dt], 1.0f);
+    }
+  }
+}
+
+// ---- f32 (parity mode), token-major qkv only. Scores are k-ordered fmaf chains over d ascending times scale, exactly as the single-panel
+// f32 kernels form them; the softmax is the online form above in expf / logf. One 64-lane workgroup per 64 queries (forward, dQ) or
+// 32 keys (dK / dV: two lanes per key, 32 head dims each). Panel rows sit in LDS unpadded: every lane reads the same row (broadcast).
+__device__ __forceinline__ void stage_f32_panel(float* d0, const float* s0, long ld0, float* d1, const float* s1, long ld1, int row0, int T) {
+  for (int idx = threadIdx.x; idx < PK * 16; idx += blockDim.x) {
+    const int t = idx >> 4, c = idx & 15;
+    f32x4_t a = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
+    if (row0 + t < T) {
+      a = *reinterpret_cast<const f32x4_t*>(s0 + (size_t)(row0 + t) * ld0 + c * 4);
+      v = *reinterpret_cast<const f32x4_t*>(s1 + (size_t)(row0 + t) * ld1 + c * 4);
+    }
+    *reinterpret_cast<f32x4_t*>(d0 + t * HD + c * 4) = a;
+    *reinterpret_cast<f32x4_t*>(d1 + t * HD + c * 4) = v;
+  }
+}
+__device__ __forceinline__ void ld_row64(float (&r)[HD], const float* p) {
+#pragma unroll
+  for (int c = 0; c < HD / 4; ++c) {
+    const f32x4_t v = *reinterpret_cast<const f32x4_t*>(p + 4 * c);
+    r[4 * c] = v[0]; r[4 * c + 1] = v[1]; r[4 * c + 2] = v[2]; r[4 * c + 3] = v[3];
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_fwd_long_f32_kernel(const float* __restrict__ qkv, float* __restrict__ o, float* __restrict__ lse,
+                                                               int T, int H, float scale) {
+  __shared__ __attribute__((aligned(16))) float Ks[PK * HD];
+  __shared__ __attribute__((aligned(16))) float Vs[PK * HD];
+  __shared__ float Ss[PK * 64];      // lane-private score slots [key][lane]
+  const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
+  const long ld = 3L * H * HD;
+  const float* qb = qkv + (size_t)b * T * ld + h * HD;
+  const int q = blockIdx.y * 64 + lane;
+  float qv[HD], acc[HD];
+  ld_row64(qv, qb + (size_t)min(q, T - 1) * ld);
+#pragma unroll
+  for (int d = 0; d < HD; ++d) acc[d] = 0.f;
+  float m = -3.0e38f, l = 0.f;
+#pragma unroll 1
+  for (int j0 = 0; j0 < T; j0 += PK) {
+    if (j0) wg_barrier_lds();      // everybody is done with the previous panel
+    stage_f32_panel(Ks, qb + H * HD, ld, Vs, qb + 2 * H * HD, ld, j0, T);
+    wg_barrier_lds();
+    const int nk = min(PK, T - j0);
+    float pm = -3.0e38f;
+#pragma unroll 1
+    for (int j = 0; j < nk; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) s = fmaf(qv[d], Ks[j * HD + d], s);
+      s *= scale;
+      Ss[j * 64 + lane] = s;
+      pm = fmaxf(pm, s);
+    }
+    const float mn = fmaxf(m, pm), alpha = expf(m - mn);      // 0 on the first panel
+    l *= alpha;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) acc[d] *= alpha;
+#pragma unroll 1
+    for (int j = 0; j < nk; ++j) {
+      const float pv = expf(Ss[j * 64 + lane] - mn);
+      l += pv;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) acc[d] = fmaf(pv, Vs[j * HD + d], acc[d]);
+    }
+    m = mn;
+  }
+  if (q < T) {
+    const float inv = 1.0f / l;
+    float* orow = o + ((size_t)b * T + q) * (H * HD) + h * HD;
+#pragma unroll
+    for (int c = 0; c < HD / 4; ++c)
+      *reinterpret_cast<f32x4_t*>(orow + 4 * c) = f32x4_t{acc[4 * c] * inv, acc[4 * c + 1] * inv, acc[4 * c + 2] * inv, acc[4 * c + 3] * inv};
+    lse[((size_t)b * H + h) * T + q] = m + logf(l);
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_bwd_dq_long_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
+                                                                  const float* __restrict__ d_o, const float* __restrict__ lse,
+                                                                  float* __restrict__ dqkv, float* __restrict__ delta, int T, int H, float scale) {
+  __shared__ __attribute__((aligned(16))) float Ks[PK * HD];
+  __shared__ __attribute__((aligned(16))) float Vs[PK * HD];
+  const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
+  const long ld = 3L * H * HD, ldo = (long)H * HD;
+  const float* qb = qkv + (size_t)b * T * ld + h * HD;
+  const int q = blockIdx.y * 64 + lane, qc = min(q, T - 1);
+  float qv[HD], gv[HD], dq[HD];
+  ld_row64(qv, qb + (size_t)qc * ld);
+  ld_row64(gv, d_o + ((size_t)b * T + qc) * ldo + h * HD);
+  float dl = 0.f;
+  {
+    const float* orow = o + ((size_t)b * T + qc) * ldo + h * HD;
+#pragma unroll
+    for (int d = 0; d < HD; ++d) { dl = fmaf(gv[d], orow[d], dl); dq[d] = 0.f; }
+  }
+  if (q < T) delta[((size_t)b * H + h) * T + q] = dl;
+  const float lq = lse[((size_t)b * H + h) * T + qc];
+#pragma unroll 1
+  for (int j0 = 0; j0 < T; j0 += PK) {
+    if (j0) wg_barrier_lds();
+    stage_f32_panel(Ks, qb + H * HD, ld, Vs, qb + 2 * H * HD, ld, j0, T);
+    wg_barrier_lds();
+    const int nk = min(PK, T - j0);
+#pragma unroll 1
+    for (int j = 0; j < nk; ++j) {
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) { s = fmaf(qv[d], Ks[j * HD + d], s); dp = fmaf(gv[d], Vs[j * HD + d], dp); }
+      const float pv = expf(s * scale - lq);
+      const float ds = pv * (dp - dl) * scale;
+#pragma unroll
+      for (int d = 0; d < HD; ++d) dq[d] = fmaf(ds, Ks[j * HD + d], dq[d]);
+    }
+  }
+  if (q < T) {
+    float* drow = dqkv + ((size_t)b * T + q) * ld + h * HD;
+#pragma unroll
+    for (int c = 0; c < HD / 4; ++c) *reinterpret_cast<f32x4_t*>(drow + 4 * c) = f32x4_t{dq[4 * c], dq[4 * c + 1], dq[4 * c + 2], dq[4 * c + 3]};
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_bwd_dkv_long_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
+                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                   float* __restrict__ dqkv, int T, int H, float scale) {
+  constexpr int HH = HD / 2;
+  __shared__ __attribute__((aligned(16))) float Qs[PK * HD];
+  __shared__ __attribute__((aligned(16))) float Gs[PK * HD];
+  __shared__ float ls_s[PK], dl_s[PK];
+  const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x, half = lane & 1;
+  const long ld = 3L * H * HD, ldo = (long)H * HD;
+  const float* qb = qkv + (size_t)b * T * ld + h * HD;
+  const int kr = blockIdx.y * 32 + (lane >> 1), krc = min(kr, T - 1);
+  float kv[HH], vv[HH], dk[HH], dv[HH];
+  {
+    const float* krow = qb + (size_t)krc * ld + H * HD + half * HH;
+    const float* vrow = qb + (size_t)krc * ld + 2 * H * HD + half * HH;
+#pragma unroll
+    for (int d = 0; d < HH; ++d) { kv[d] = krow[d]; vv[d] = vrow[d]; dk[d] = 0.f; dv[d] = 0.f; }
+  }
+  const float* lrow = lse + ((size_t)b * H + h) * T;
+  const float* drow = delta + ((size_t)b * H + h) * T;
+#pragma unroll 1
+  for (int i0 = 0; i0 < T; i0 += PK) {
+    if (i0) wg_barrier_lds();
+    stage_f32_panel(Qs, qb, ld, Gs, d_o + (size_t)b * T * ldo + h * HD, ldo, i0, T);
+    {
+      const int t = i0 + lane;
+      ls_s[lane] = (t < T) ? lrow[t] : 0.f;
+      dl_s[lane] = (t < T) ? drow[t] : 0.f;
+    }
+    wg_barrier_lds();
+    const int nq = min(PK, T - i0);
+#pragma unroll 1
+    for (int i = 0; i < nq; ++i) {
+      const float* qrow = Qs + i * HD + half * HH;
+      const float* grow = Gs + i * HD + half * HH;
+      float s = 0.f, dp = 0.f;
+#pragma unroll
+      for (int d = 0; d < HH; ++d) { s = fmaf(qrow[d], kv[d], s); dp = fmaf(grow[d], vv[d], dp); }
+      s += __shfl_xor(s, 1, 64);      // (a + b in one lane, b + a in the other: the same value)
+      dp += __shfl_xor(dp, 1, 64);
+      const float pv = expf(s * scale - ls_s[i]);
+      const float ds = pv * (dp - dl_s[i]) * scale;
+#pragma unroll
+      for (int d = 0; d < HH; ++d) { dv[d] = fmaf(pv, grow[d], dv[d]); dk[d] = fmaf(ds, qrow[d], dk[d]); }
+    }
+  }
+  if (kr < T) {
+    float* base = dqkv + ((size_t)b * T + kr) * ld + h * HD + half * HH;
+#pragma unroll
+    for (int c = 0; c < HH / 4; ++c) {
+      *reinterpret_cast<f32x4_t*>(base + H * HD + 4 * c) = f32x4_t{dk[4 * c], dk[4 * c + 1], dk[4 * c + 2], dk[4 * c + 3]};
+      *reinterpret_cast<f32x4_t*>(base + 2 * H * HD + 4 * c) = f32x4_t{dv[4 * c], dv[4 * c + 1], dv[4 * c + 2], dv[4 * c + 3]};
+    }
+  }
+}
+
+// cls forward above 256 keys: the score buffer holds one chunk of 256 keys; chunks are combined with the online max / sum (the chunk's
+// max decision before its exponentials, as above). Same 8-lanes-per-row access as attn_fwd_cls_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_fwd_cls_long_kernel(const T* __restrict__ qkv, const T* __restrict__ q_cls, T* __restrict__ o_cls,
+                                                                float* __restrict__ lse_cls, int Tn, int H, float scale, int hm) {
+  GSL_OP16_KERNEL_ENTRY();
+  constexpr int CH = 256;
+  __shared__ float q0[HD], sc[CH], red[32][HD];
+  __shared__ float sm[16];
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const long ldo = (long)H * HD;
+  ClsAddr ad;
+  const T* qb = cls_base(qkv, b, h, Tn, H, hm, ad);
+  const int tid = threadIdx.x;
+  if (tid < HD) q0[tid] = Elem<T>::ld(hm == 2 ? q_cls + (size_t)b * ldo + h * HD + tid : qb + tid);
+  __syncthreads();
+  const int grp = tid >> 3, sub = tid & 7;
+  float qs[8], acc[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { qs[i] = q0[sub * 8 + i]; acc[i] = 0.f; }
+  float m = -3.0e38f, e = 0.f;
+  for (int c0 = 0; c0 < Tn; c0 += CH) {
+    const int nc = min(CH, Tn - c0);
+    if (c0) __syncthreads();      // every group is done with the previous chunk's probabilities
+    for (int j0 = 0; j0 < nc; j0 += 32) {
+      const int j = j0 + grp, jc = c0 + (j < nc ? j : nc - 1);
+      const T* kr = qb + (size_t)jc * ad.ldi + ad.ko + sub * 8;
+      float kv[8];
+      Elem<T>::ld4(kr, kv); Elem<T>::ld4(kr + 4, kv + 4);
+      float sdot = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sdot = fmaf(qs[i], kv[i], sdot);
+#pragma unroll
+      for (int sh = 1; sh < 8; sh <<= 1) sdot += __shfl_xor(sdot, sh, 64);
+      if (j < nc && sub == 0) sc[j] = sdot * scale;
+    }
+    __syncthreads();
+    float cm = -3.0e38f;
+    for (int j = tid; j < nc; j += 256) cm = fmaxf(cm, sc[j]);
+    cm = block_max(cm, sm);
+    const float mn = fmaxf(m, cm), alpha = expf(m - mn);      // 0 for the first chunk
+    float ce = 0.f;
+    for (int j = tid; j < nc; j += 256) { const float p = expf(sc[j] - mn); sc[j] = p; ce += p; }
+    ce = block_sum(ce, sm);        // (its barriers also publish the p values)
+    e = fmaf(e, alpha, ce);
+    m = mn;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= alpha;
+    for (int j0 = 0; j0 < nc; j0 += 32) {
+      const int j = j0 + grp;
+      if (j < nc) {
+        const T* vr = qb + (size_t)(c0 + j) * ad.ldi + ad.vo + sub * 8;
+        float vv[8];
+        Elem<T>::ld4(vr, vv); Elem<T>::ld4(vr + 4, vv + 4);
+        const float p = sc[j];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(p, vv[i], acc[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) red[grp][sub * 8 + i] = acc[i];
+  __syncthreads();
+  if (tid < HD) {
+    float t = 0.f;
+#pragma unroll
+    for (int g = 0; g < 32; ++g) t += red[g][tid];       // fixed order
+    Elem<T>::st(o_cls + (size_t)b * ldo + h * HD + tid, t / e);
+  }
+  if (tid == 0) lse_cls[(size_t)b * H + h] = m + logf(e);
+}
+
 extern "C" int GSL_ENTRY(gsl_attention_fwd_cls)(const void* qkv, const void* q_cls, void* o_cls, float* lse_cls, int B, int T, int H, float scale,
                                      int dtype, int qkv_layout, gsl_stream_t s) {
   GSL_FORWARD_H16(dtype, h16_gsl_attention_fwd_cls(qkv, q_cls, o_cls, lse_cls, B, T, H, scale, dtype, qkv_layout, s));
-  GSL_CHECK_ARG(qkv && o_cls && lse_cls && B > 0 && T > 1 && T <= 256 && H > 0, "null/size (T <= 256)");
+  GSL_CHECK_ARG(qkv && o_cls && lse_cls && B > 0 && T > 1 && H > 0, "null/size");
+  GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
   GSL_CHECK_ARG(qkv_layout >= 0 && qkv_layout <= 2 && (qkv_layout != 2 || q_cls), "qkv_layout: 0 token-major, 1 head-major, 2 kv + q_cls");
   const dim3 grid(B * H), blk(256);
+  if (T > 256) {      // key chunks with the online max / sum
+    if (dtype == GSL_OP16)
+      hipLaunchKernelGGL(attn_fwd_cls_long_kernel<bf16_t>, grid, blk, 0, as_stream(s), (const bf16_t*)qkv, (const bf16_t*)q_cls, (bf16_t*)o_cls, lse_cls, T, H, scale, qkv_layout);
+#if GSL_HAS_F32
+    else if (dtype == GSL_F32)
+      hipLaunchKernelGGL(attn_fwd_cls_long_kernel<float>, grid, blk, 0, as_stream(s), (const float*)qkv, (const float*)q_cls, (float*)o_cls, lse_cls, T, H, scale, qkv_layout);
+#endif
+    else return fail(GSL_ERR_ARG, "gsl_attention_fwd_cls: bad dtype%s %ld", "", dtype);
+    return check_launch("gsl_attention_fwd_cls");
+  }
   if (dtype == GSL_OP16)
     hipLaunchKernelGGL(attn_fwd_cls_kernel<bf16_t>, grid, blk, 0, as_stream(s), (const bf16_t*)qkv, (const bf16_t*)q_cls, (bf16_t*)o_cls, lse_cls, T, H, scale, qkv_layout);
 #if GSL_HAS_F32
@@ -1659,6 +2269,18 @@ static inline int attn_num_cus() {
   return n;
 }
 static inline int attn_abl() { return attn_env("GSL_ATTN_ABL", 0); }
+// Launch shape of the long-sequence kernels (T > 224): tiles (query tiles of the forward / dQ, key tiles of dK / dV) per workgroup = waves.
+// Blocks of <= 16 tiles; while items * blocks < CUs (few images) an item is split further, down to 4 tiles per workgroup. Returns the
+// waves per workgroup and sets nb = blocks per item and the grid (items rounded up to a multiple of 8: long_item()).
+static inline int attn_long_shape(int T, int items, int& nb, dim3& grid) {
+  const int nt = (T + 15) / 16;
+  nb = (nt + 15) / 16;
+  if ((long)items * nb < attn_num_cus()) nb = std::max(nb, std::min((attn_num_cus() + items - 1) / items, (nt + 3) / 4));
+  const int w = std::max(4, (nt + nb - 1) / nb);      // >= 256 threads: panel_load() covers a panel in two rounds
+  nb = (nt + w - 1) / w;
+  grid = dim3((unsigned)(((items + 7) / 8) * 8 * nb));
+  return w;
+}
 
 // =====================================================================================
 // C ABI
@@ -1669,8 +2291,20 @@ extern "C" int GSL_ENTRY(gsl_attention_fwd)(const void* qkv, void* o, float* lse
   GSL_CHECK_ARG(qkv && o && lse && B > 0 && T > 1 && H > 0, "null/size");
   GSL_CHECK_ARG(qkv_layout == 0 || (qkv_layout == 1 && dtype == GSL_OP16), "qkv_layout: 0 token-major, 1 head-major (bf16 kernels only)");
   const int hm = qkv_layout;
-  GSL_CHECK_ARG(T <= 224, "T <= 224 tokens (single-panel attention)");
+  GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
   hipStream_t st = as_stream(s);
+  if (T > 224) {      // K / V panels streamed through LDS
+    int nb = 1; dim3 lg;
+    const int w = attn_long_shape(T, B * H, nb, lg);
+    if (dtype == GSL_OP16)
+      hipLaunchKernelGGL(attn_fwd_long_kernel, lg, dim3(64 * w), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, hm, B * H, nb);
+#if GSL_HAS_F32
+    else if (dtype == GSL_F32)
+      hipLaunchKernelGGL(attn_fwd_long_f32_kernel, dim3(B * H, (T + 63) / 64), dim3(64), 0, st, (const float*)qkv, (float*)o, lse, T, H, scale);
+#endif
+    else return fail(GSL_ERR_ARG, "gsl_attention_fwd: bad dtype%s %ld", "", dtype);
+    return check_launch("gsl_attention_fwd");
+  }
   const dim3 grid(B * H), blk(256);
   // (item_remap for the forward: measured +1 % — 212 -> 215 us at B = 1024 —, so the plain order stays; the backward gains 2.3 %: profiles/r04_notes.md)
   const int imap = (B % 8 == 0 && attn_num_cus() % 8 == 0) ? attn_env("GSL_ATTN_ITEM_REMAP_FWD", 0) : 0;
@@ -1700,8 +2334,28 @@ extern "C" int GSL_ENTRY(gsl_attention_bwd)(const void* qkv, const void* o, cons
   GSL_CHECK_ARG(qkv && o && d_o && lse && dqkv && delta_ws && B > 0 && T > 1 && H > 0, "null/size");
   GSL_CHECK_ARG(qkv_layout == 0 || (qkv_layout == 1 && dtype == GSL_OP16), "qkv_layout: 0 token-major, 1 head-major (bf16 kernels only)");
   const int hm = qkv_layout;
-  GSL_CHECK_ARG(T <= 224, "T <= 224 tokens (single-panel attention)");
+  GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
   hipStream_t st = as_stream(s);
+  if (T > 224) {      // dQ over K / V panels (writes delta_ws), then dK / dV over Q / dO panels (reads it)
+    if (dtype == GSL_OP16) {
+      const bf16_t* q = (const bf16_t*)qkv; const bf16_t* oo = (const bf16_t*)o; const bf16_t* g = (const bf16_t*)d_o;
+      bf16_t* dq = (bf16_t*)dqkv;
+      int nb = 1; dim3 lg;
+      const int w = attn_long_shape(T, B * H, nb, lg);
+      hipLaunchKernelGGL(attn_bwd_dq_long_kernel, lg, dim3(64 * w), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale, hm, B * H, nb);
+      hipLaunchKernelGGL(attn_bwd_dkv_long_kernel, lg, dim3(64 * w), 0, st, q, g, lse, delta_ws, dq, T, H, scale, hm, B * H, nb);
+    }
+#if GSL_HAS_F32
+    else if (dtype == GSL_F32) {
+      const float* q = (const float*)qkv; const float* oo = (const float*)o; const float* g = (const float*)d_o;
+      float* dq = (float*)dqkv;
+      hipLaunchKernelGGL(attn_bwd_dq_long_f32_kernel, dim3(B * H, (T + 63) / 64), dim3(64), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale);
+      hipLaunchKernelGGL(attn_bwd_dkv_long_f32_kernel, dim3(B * H, (T + 31) / 32), dim3(64), 0, st, q, g, lse, delta_ws, dq, T, H, scale);
+    }
+#endif
+    else return fail(GSL_ERR_ARG, "gsl_attention_bwd: bad dtype%s %ld", "", dtype);
+    return check_launch("gsl_attention_bwd");
+  }
   const dim3 grid(B * H), blk(256);
   if (dtype == GSL_OP16) {
     const bf16_t* q = (const bf16_t*)qkv; const bf16_t* oo = (const bf16_t*)o; const bf16_t* g = (const bf16_t*)d_o;

@@ -6,6 +6,17 @@ import torch
 
 from . import _lib as L
 
+# Longest sequence the attention entry points accept (include/gslora_hip.h, GSL_ATTN_MAX_T): a 32 x 32 patch grid plus the cls token.
+ATTN_MAX_T = 1025
+
+
+def check_num_tokens(model, T):
+    """Refuse, at construction, a geometry whose token count the attention kernels do not serve."""
+    if T > ATTN_MAX_T:
+        raise NotImplementedError(f"{model}: this geometry gives {T} tokens per image; the gs-lora_amd attention kernels take at most "
+                                  f"{ATTN_MAX_T} (GSL_ATTN_MAX_T: a 32 x 32 patch grid plus the cls token)")
+
+
 DT = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}      # (fp16: MFMA operand format of the "fp16" mode; also the forward residual stream of both 16-bit modes)
 
 
@@ -241,7 +252,9 @@ def layernorm_bwd(dy, x, row_stride, gamma, mean, rstd, dres, want_copy=True, p_
 
 @_profiled("attn_fwd", lambda qkv, B, T, H, *a, **k: (B * T, H * 64, T, H))
 def attention_fwd(qkv, B, T, H, scale, layout=0):
-    """layout: 0 = qkv token-major [B*T, 3*H*64], 1 = head-major [B][H][3][T][64] (bf16; see gemm_nt(epilogue=EPI_STORE_QKV_HM))."""
+    """layout: 0 = qkv token-major [B*T, 3*H*64], 1 = head-major [B][H][3][T][64] (bf16; see gemm_nt(epilogue=EPI_STORE_QKV_HM)).
+    2 <= T <= ATTN_MAX_T: up to 224 tokens one LDS panel holds an item's K / V; above, 64-key panels stream with an online softmax.
+    o [B*T, H*64] token-major, lse f32 [B, H, T] (natural-log logsumexp of the scaled scores) in both regimes."""
     _need(qkv)
     o = torch.empty(B * T, H * 64, device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
@@ -252,7 +265,8 @@ def attention_fwd(qkv, B, T, H, scale, layout=0):
 
 @_profiled("attn_bwd", lambda qkv, o, d_o, lse, B, T, H, *a, **k: (B * T, H * 64, T, H))
 def attention_bwd(qkv, o, d_o, lse, B, T, H, scale, layout=0):
-    """dqkv is token-major [B*T, 3*H*64] whatever the layout of the qkv input."""
+    """dqkv is token-major [B*T, 3*H*64] whatever the layout of the qkv input. 2 <= T <= ATTN_MAX_T; deterministic (no atomics) at
+    every T. `delta` [B, H, T] is the rowsum(dO o) hand-off between the dQ and the dK / dV kernels of the split forms (T <= 64, T > 224)."""
     _need(qkv, o, d_o, lse)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
@@ -263,7 +277,8 @@ def attention_bwd(qkv, o, d_o, lse, B, T, H, scale, layout=0):
 
 def attention_fwd_cls(qkv, B, T, H, scale, layout=0, q_cls=None):
     """Attention output of the cls query alone (the last block under pool='cls'): o_cls [B, H*64], lse_cls [B, H].
-    layout 2: `qkv` is kv [B*T, 2*H*64] (k | v, token-major) and q_cls [B, H*64] holds the queries."""
+    layout 2: `qkv` is kv [B*T, 2*H*64] (k | v, token-major) and q_cls [B, H*64] holds the queries. 2 <= T <= ATTN_MAX_T (above 256
+    keys the softmax runs over 256-key chunks with an online max / sum)."""
     _need(qkv, q_cls)
     o = torch.empty(B, H * 64, device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty(B, H, device=qkv.device, dtype=torch.float32)
@@ -274,7 +289,8 @@ def attention_fwd_cls(qkv, B, T, H, scale, layout=0, q_cls=None):
 
 def attention_bwd_cls(qkv, o, d_o_cls, lse, B, T, H, scale, layout=0, q_cls=None):
     """o / lse: either the full forward tensors ([B*T, H*64] / [B, H, T]) or the compact ones of attention_fwd_cls ([B, H*64] / [B, H]).
-    layout 0 / 1 -> dqkv [B*T, 3*H*64]; layout 2 (kv + q_cls) -> (dkv [B*T, 2*H*64], dq_cls [B, H*64])."""
+    layout 0 / 1 -> dqkv [B*T, 3*H*64]; layout 2 (kv + q_cls) -> (dkv [B*T, 2*H*64], dq_cls [B, H*64]). Any T >= 2 (it walks the keys
+    in steps of 32)."""
     _need(qkv, o, d_o_cls, lse, q_cls)
     nw = 2 if layout == 2 else 3
     dqkv = torch.empty(B * T, nw * H * 64, device=qkv.device, dtype=qkv.dtype)

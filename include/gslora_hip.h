@@ -168,7 +168,12 @@ GSL_API int gsl_layernorm_bwd(const void* dy, const void* x, long x_row_stride, 
 /* ---- K4 attention, head_dim 64, no mask, softmax(QK^T*scale)V (vit_face.py:358-376).
  * qkv_layout (the INPUT qkv): 0 = token-major qkv[dtype] [B*T, 3*H*64] (q|k|v, each 'b n (h d)', as the reference's to_qkv output),
  * 1 = head-major [B][H][3][T][64] (bf16 kernels only; written by gsl_gemm_nt's GSL_EPI_STORE_QKV_HM): every panel row is a full
- * 128-byte line next to its neighbours. Outputs are token-major in both cases: o[dtype] [B*T, H*64], lse f32 [B,H,T]. */
+ * 128-byte line next to its neighbours. Outputs are token-major in both cases: o[dtype] [B*T, H*64], lse f32 [B,H,T].
+ * Token limit: 2 <= T <= GSL_ATTN_MAX_T (1025 = a 32 x 32 patch grid plus the cls token) for gsl_attention_fwd, gsl_attention_bwd and
+ * gsl_attention_fwd_cls; a longer sequence fails with GSL_ERR_ARG. Up to 224 tokens (256 for the cls forward) an item's K / V sit in LDS
+ * whole; above, they stream through LDS in 64-row panels with an online softmax (same output formats, same lse). gsl_attention_bwd_cls
+ * takes any T. */
+#define GSL_ATTN_MAX_T 1025
 GSL_API int gsl_attention_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, float scale, int dtype, int qkv_layout, gsl_stream_t s);
 /* dqkv[dtype] [B*T,3*H*64] (token-major, always); delta_ws f32 [B,H,T] scratch. */
 GSL_API int gsl_attention_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv,
