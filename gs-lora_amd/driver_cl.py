@@ -82,6 +82,9 @@ def get_args(argv=None):
                    help="backbone (util/args.py -n): ViT_face, or ViTs_face with 12 x 12 windows at stride 8, pad 4 (train_own_forget_cl.py:222-236)")
     p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"],
                    help="classification head of ViT_face (config.py -head; SFaceLoss is not implemented)")
+    p.add_argument("--u8_input", default=False, action="store_true",
+                   help="feed uint8 images (the decoder's bytes): the model normalises them inside the patch gather (set_input_norm) "
+                        "instead of a ToTensor() dataset transform on the host")
     p.add_argument("--outdir", default=None)
     p.add_argument("--seed", type=int, default=1337)
     p.add_argument("--average_weight", default=False, action="store_true", help="EMA model of the reference (:502-507, :1058-1098)")
@@ -103,14 +106,16 @@ def task_hyper(args, task_i, epoch):
     return beta, pro_f, alpha
 
 
-def synthetic_dataset(num_class, per_class, image_size, seed):
-    """Class-conditional synthetic faces: a per-class low-frequency pattern plus noise, u8/255 like ToTensor()."""
+def synthetic_dataset(num_class, per_class, image_size, seed, u8=False):
+    """Class-conditional synthetic faces: a per-class low-frequency pattern plus noise, u8/255 like ToTensor() — or, with u8, the bytes
+    themselves (the same images before ToTensor())."""
     g = torch.Generator().manual_seed(seed)
     base = torch.rand(num_class, 3, 7, 7, generator=g)
     base = torch.nn.functional.interpolate(base, size=image_size, mode="bilinear", align_corners=False)
     x = base.repeat_interleave(per_class, 0) * 0.7 + 0.3 * torch.rand(num_class * per_class, 3, image_size, image_size, generator=g)
     y = torch.arange(num_class).repeat_interleave(per_class)
-    return (x * 255).round().clamp(0, 255) / 255.0, y
+    b = (x * 255).round().clamp(0, 255)
+    return (b.to(torch.uint8) if u8 else b / 255.0), y
 
 
 def subset(x, y, classes):
@@ -218,8 +223,10 @@ def main(argv=None):
     lora.mark_only_lora_as_trainable(model)                   # :314-317
     print("trainable parameters:", count_trainable_parameters(model))
     model = model.to(dev).set_compute_dtype(args.dtype)
-    x_all, y_all = synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed)
-    x_te, y_te = synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1)
+    if args.u8_input:                                         # the dataset transform (:131-147, ToTensor()) moves into the patch gather
+        model.set_input_norm("totensor")
+    x_all, y_all = synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed, u8=args.u8_input)
+    x_te, y_te = synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1, u8=args.u8_input)
     num_first = args.num_class - args.per_forget_cls           # classes not yet forgotten after task 0
 
     def task_data(task_i, model):

@@ -46,16 +46,80 @@ def code(dtype):
         raise RuntimeError(f"gslora_hip: unsupported compute dtype {dtype}")
 
 
-def patchify(img, p, dtype):
-    """img: one [B, C, H, W] batch or a list of batches of one image shape; the batches land in consecutive row ranges of the output."""
+# ---- uint8 image batches (gsl_patchify_u8 / gsl_unfold_patches_u8): ToTensor() + Normalize(mean, std) happen inside the gather
+# named (mean, std) pairs: the face drivers use ToTensor() alone, the ImageNet-100 driver the ImageNet constants
+INPUT_NORM_TOTENSOR = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+INPUT_NORM_IMAGENET = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))
+INPUT_NORMS = {"totensor": INPUT_NORM_TOTENSOR, "imagenet": INPUT_NORM_IMAGENET}
+
+
+def u8_reference(u, mean, std):
+    """The float32 image a uint8 batch stands for: ToTensor() then Normalize(mean, std), in torchvision's operation order. This expression
+    is the definition; u8_norm_table() evaluates it for every (channel, byte) and the gathers look the result up."""
+    mean = torch.as_tensor(mean, dtype=torch.float32, device=u.device)
+    std = torch.as_tensor(std, dtype=torch.float32, device=u.device)
+    return u.to(torch.float32).div(255).sub(mean[None, :, None, None]).div(std[None, :, None, None])
+
+
+def u8_norm_table(mean, std):
+    """[C, 256] float32 (host): row c holds u8_reference() of the bytes 0 .. 255 in channel c."""
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    if len(mean) != len(std) or not mean:
+        raise ValueError(f"input norm: mean and std need one entry per channel, got {len(mean)} and {len(std)}")
+    if any(v == 0.0 or v != v for v in std):
+        raise ValueError(f"input norm: std must be non-zero, got {std}")
+    u = torch.arange(256, dtype=torch.uint8).reshape(256, 1, 1, 1).expand(256, len(mean), 1, 1)
+    return u8_reference(u, mean, std).reshape(256, len(mean)).t().contiguous()
+
+
+def _u8_source(t):
+    """(layout code, tensor the kernel can read) of one [B, C, H, W] uint8 batch: NCHW-contiguous bytes, or NHWC bytes (a tensor that is
+    contiguous in torch.channels_last: what a decoder produces, permuted to the logical shape); anything else is copied to NCHW."""
+    if t.is_contiguous():
+        return L.U8_NCHW, t
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return L.U8_NHWC, t
+    return L.U8_NCHW, t.contiguous()
+
+
+def _image_parts(img, table, what):
     parts = list(img) if isinstance(img, (tuple, list)) else [img]
-    _need(*parts)
+    u8 = parts[0].dtype == torch.uint8
+    if any((t.dtype == torch.uint8) != u8 for t in parts):
+        raise ValueError(f"{what}: the batches of one call must be all uint8 or all float")
+    if not u8:
+        _need(*parts)
+        return parts, None
+    if table is None:
+        raise RuntimeError(f"{what}: a uint8 image needs the [C, 256] value table of its normalisation (ops.u8_norm_table)")
+    _need(table)
+    if not all(t.is_cuda for t in parts):
+        raise RuntimeError("gslora_hip: tensors must live on a ROCm GPU (the HIP path has no CPU fallback)")
+    if table.dtype != torch.float32 or tuple(table.shape) != (parts[0].shape[1], 256):
+        raise ValueError(f"{what}: the value table must be float32 [{parts[0].shape[1]}, 256], got {table.dtype} {tuple(table.shape)}")
+    src = []
+    for t in parts:
+        lay, t = _u8_source(t)
+        if t.data_ptr() % 8:      # (a view at an odd byte offset: the wide loads want 8-byte alignment)
+            t = t.clone(memory_format=torch.preserve_format)
+        src.append((lay, t))
+    return parts, src
+
+
+def patchify(img, p, dtype, table=None):
+    """img: one [B, C, H, W] batch or a list of batches of one image shape; the batches land in consecutive row ranges of the output.
+    float32 batches are gathered as they are; uint8 batches (NCHW-contiguous or channels_last) are normalised through `table` on the way."""
+    parts, src = _image_parts(img, table, "patchify")
     _, Cc, H, W = parts[0].shape
     T = 1 + (H // p) * (W // p)
     out = torch.empty(sum(t.shape[0] for t in parts) * T, p * p * Cc, device=parts[0].device, dtype=dtype)
     row = 0
-    for t in parts:
-        L.check(L.load().gsl_patchify(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, p, code(dtype), _stream()), "gsl_patchify")
+    for i, t in enumerate(parts):
+        if src is None:
+            L.check(L.load().gsl_patchify(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, p, code(dtype), _stream()), "gsl_patchify")
+        else:
+            L.check(L.load().gsl_patchify_u8(_p(src[i][1]), src[i][0], _p(table), _p(out[row:]), t.shape[0], Cc, H, W, p, code(dtype), _stream()),
+                    "gsl_patchify_u8")
         row += t.shape[0] * T
     return out
 
@@ -65,21 +129,24 @@ def unfold_geometry(H, W, k, stride, pad):
     return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
 
 
-def unfold_patches(img, k, stride, pad, dtype):
+def unfold_patches(img, k, stride, pad, dtype, table=None):
     """nn.Unfold(k, stride, pad)(img).transpose(1, 2) with a zero cls row per image and the feature dimension zero-padded to a multiple
     of 64 (the patch GEMM's K): [B*T, Kpad], T = 1 + Lh*Lw, Kpad = ceil(C*k*k / 64)*64. img: one [B, C, H, W] batch or a list of batches
-    of one image shape; the batches land in consecutive row ranges of the output."""
-    parts = list(img) if isinstance(img, (tuple, list)) else [img]
-    _need(*parts)
+    of one image shape; the batches land in consecutive row ranges of the output. uint8 batches: as patchify (padding taps stay 0)."""
+    parts, src = _image_parts(img, table, "unfold_patches")
     _, Cc, H, W = parts[0].shape
     Lh, Lw = unfold_geometry(H, W, k, stride, pad)
     T = 1 + Lh * Lw
     kpad = -(-Cc * k * k // 64) * 64
     out = torch.empty(sum(t.shape[0] for t in parts) * T, kpad, device=parts[0].device, dtype=dtype)
     row = 0
-    for t in parts:
-        L.check(L.load().gsl_unfold_patches(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, k, stride, pad, kpad, code(dtype), _stream()),
-                "gsl_unfold_patches")
+    for i, t in enumerate(parts):
+        if src is None:
+            L.check(L.load().gsl_unfold_patches(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, k, stride, pad, kpad, code(dtype), _stream()),
+                    "gsl_unfold_patches")
+        else:
+            L.check(L.load().gsl_unfold_patches_u8(_p(src[i][1]), src[i][0], _p(table), _p(out[row:]), t.shape[0], Cc, H, W, k, stride, pad,
+                                                   kpad, code(dtype), _stream()), "gsl_unfold_patches_u8")
         row += t.shape[0] * T
     return out
 

@@ -210,6 +210,12 @@ def _arm_overflow_guard(net, optimizer):
     optimizer.overflow_guard = g
 
 
+def _model_input(net, x):
+    """The reference's inputs.float() — except for a uint8 batch of a model that normalises bytes itself (set_input_norm): that one
+    stays uint8 up to the patch gather (a cast here would change its values and put four bytes per sub-pixel back on the bus)."""
+    return x if (x.dtype == torch.uint8 and getattr(net, "input_norm", None) is not None) else x.float()
+
+
 def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha, BND, use_structure=True,
                  group_type="block", use_prototype=False, proto_table=None, w_f=0.0, w_r=0.0, BND_pro=0.0,
                  backend=HipBackend, fuse_batches=True, _comm=_EagerComm):
@@ -222,6 +228,9 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
     world = _world()
     dev = x_r.device
     split = None
+    if getattr(net, "input_norm", None) is not None and (x_r.dtype == torch.uint8) != (x_f.dtype == torch.uint8):
+        raise ValueError("gs_lora_step: the remain batch and the forget batch of one step must be both uint8 or both float "
+                         f"(got {x_r.dtype} and {x_f.dtype}) for a model with set_input_norm() in effect")
     if fuse_batches:
         # every operation of the network is per-sample (no BatchNorm), so one forward over the concatenated batch is
         # arithmetically identical to the reference's two forwards and halves the number of kernel launches / tile tails
@@ -229,14 +238,15 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
         y_all = _cat_labels(y_r, y_f)
         # (the HIP model takes the two image batches as a tuple and patchifies each into its row range: no 2 x 77 MB concatenated
         #  copy at batch 512 + 512; any other module gets the concatenated tensor)
-        both = (x_r, x_f) if getattr(net, "accepts_batch_tuple", False) and x_r.shape[1:] == x_f.shape[1:] else torch.cat((x_r.float(), x_f.float()), 0)
+        both = ((x_r, x_f) if getattr(net, "accepts_batch_tuple", False) and x_r.shape[1:] == x_f.shape[1:]
+                else torch.cat((_model_input(net, x_r), _model_input(net, x_f)), 0))
         out, emb = model(both, y_all)
         out_r, out_f, emb_r, emb_f = out[:nr], out[nr:], emb[:nr], emb[nr:]
         if _plain_ce(criterion) and hasattr(backend, "ce_sum_top1_split"):
             split = (out, emb, y_all, nr)       # losses on the two row ranges of the un-sliced tensors (one gradient buffer each)
     else:
-        out_r, emb_r = model(x_r.float(), y_r)
-        out_f, emb_f = model(x_f.float(), y_f)
+        out_r, emb_r = model(_model_input(net, x_r), y_r)
+        out_f, emb_f = model(_model_input(net, x_f), y_f)
     n_r, n_f = float(x_r.size(0)), float(x_f.size(0))
     if (split is not None and LOSS_TAIL and not _dp_active() and hasattr(backend, "loss_tail") and out.dtype == torch.float32
             and out.is_contiguous() and out.dim() == 2 and 0 < nr < out.shape[0] <= min(LOSS_TAIL_ROWS, backend.loss_tail_max_rows()) and out.shape[1] <= 1024
@@ -397,7 +407,8 @@ class GraphedStep:
         drop = (getattr(self.net, "dropout_p", None), getattr(self.net, "emb_dropout_p", None))
         return (tuple(x_r.shape), tuple(x_f.shape), x_r.dtype, y_r.dtype, self.net.training, self.net.compute_dtype,
                 sum(p._version for p in self._frozen), None if pt is None else (pt.data_ptr(), tuple(pt.shape)),
-                tuple(sorted((k, v) for k, v in kw.items() if k != "proto_table")), hyper, drop)
+                tuple(sorted((k, v) for k, v in kw.items() if k != "proto_table")), hyper, drop, getattr(self.net, "input_norm", None),
+                tuple(x.stride() for x in (x_r, x_f)))      # (the normalisation and the byte layout are baked into the captured gathers)
 
     def _usable(self):
         return (hasattr(self.optimizer, "graph_capturable") and _plain_ce(self.criterion) and not isinstance(self.model, nn.DataParallel))

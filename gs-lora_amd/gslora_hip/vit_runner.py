@@ -193,6 +193,7 @@ class ViTRunner:
         self._wcache = {}
         self._lcache = {}
         self._packs, self._pack_tables, self._retired = {}, {}, []
+        self._u8tab = None        # ((mean, std), device) -> the [C, 256] value table of uint8 inputs (input_table)
         self._rank = 0
         self.seed_dev = None      # int64 [1] device tensor: dropout seed of a step that is being captured / replayed as a HIP graph
         # dropout stream: torch.manual_seed() selects it (like the reference's nn.Dropout), and every data-parallel rank draws its own
@@ -248,6 +249,20 @@ class ViTRunner:
         or drop the graphs (GraphedStep.graphs.clear())."""
         self._wcache = {k: v for k, v in self._wcache.items() if k and k[0] == "zeros"}
         self._lcache.clear()
+
+    def input_table(self, norm, channels, device):
+        """Device copy of the [C, 256] value table of the model's input normalisation (ops.u8_norm_table), cached on (mean, std) and the
+        device alone. A replaced table is retired, not freed: a captured HIP graph may still read it."""
+        ent = self._u8tab
+        if ent is None or ent[0] != (norm, device):
+            if len(norm[0]) != channels:
+                raise ValueError(f"{type(self.model).__name__}: set_input_norm() was given {len(norm[0])} channels, the images have {channels}")
+            if ent is not None:
+                self._retired.append(ent[1])
+            ent = self._u8tab = ((norm, device), ops.u8_norm_table(*norm).to(device))
+        if ent[1].shape[0] != channels:
+            raise ValueError(f"{type(self.model).__name__}: set_input_norm() was given {ent[1].shape[0]} channels, the images have {channels}")
+        return ent[1]
 
     def w(self, name, param, dtype):
         """[N,K] operand in compute dtype."""
@@ -420,7 +435,14 @@ class ViTRunner:
         """img: [B, C, H, W], or a tuple of such batches that are processed as ONE batch (gs_lora_step hands over the remain and the
         forget batch this way: each is patchified into its row range of the token matrix, no concatenated image copy is made)."""
         m = self.model
-        parts = [t.float().contiguous() for t in img] if isinstance(img, (tuple, list)) else [img.float().contiguous()]
+        raw = list(img) if isinstance(img, (tuple, list)) else [img]
+        # uint8 batches of a model that was told how to normalise them (set_input_norm) stay bytes up to the patch gather, which looks
+        # ToTensor() + Normalize() up in a [C, 256] table; any other input is a value cast, as the reference's inputs.float()
+        norm = getattr(m, "input_norm", None)
+        u8 = norm is not None and all(t.dtype == torch.uint8 for t in raw)
+        if norm is not None and not u8 and any(t.dtype == torch.uint8 for t in raw):
+            raise ValueError(f"{type(m).__name__}: the batches of one forward must be all uint8 or all float once set_input_norm() is in effect")
+        parts = raw if u8 else [t.float().contiguous() for t in raw]
         img = parts[0]
         if not all(t.is_cuda for t in parts):
             raise RuntimeError(f"{type(m).__name__} (gs-lora_amd): the model runs only on a ROCm GPU through libgslora_hip.so; "
@@ -430,6 +452,7 @@ class ViTRunner:
         L.load()
         sp = m.hip_spec()
         dt = m.compute_dtype
+        u8tab = self.input_table(norm, img.shape[1], img.device) if u8 else None
         linear_head = sp.head_kind in LINEAR_HEADS
         if sp.head_kind == "linear":
             label = None                       # modified_VIT.py:23-24: "label is not used in this model"
@@ -459,12 +482,12 @@ class ViTRunner:
             if sp.image_size is not None and tuple(img.shape[2:]) != (sp.image_size, sp.image_size):
                 raise ValueError(f"{type(m).__name__}: input images are {tuple(img.shape[2:])}, the model was built for "
                                  f"{sp.image_size} x {sp.image_size}")
-            patches = ops.unfold_patches(parts, sp.patch_kernel, sp.patch_stride, sp.patch_pad, dt)
+            patches = ops.unfold_patches(parts, sp.patch_kernel, sp.patch_stride, sp.patch_pad, dt, table=u8tab)
             if patches.shape[0] != B * T:
                 raise ValueError(f"{type(m).__name__}: the unfold yields {patches.shape[0] // B} tokens per image, the model has {T}")
             pw = self.w_kpad("pe", sp.patch_w, patches.shape[1], dt)
         else:
-            patches = ops.patchify(parts, sp.patch_size, dt)
+            patches = ops.patchify(parts, sp.patch_size, dt, table=u8tab)
             pw = self.w_conv("pe", sp.patch_w, dt) if sp.patch_is_conv else self.w("pe", sp.patch_w, dt)
         xbf = dt in OP16 and FWD_STREAM != "f32"        # the residual stream in 2 bytes per element
         xf16 = xbf and (FWD_STREAM == "f16" or dt == torch.float16)      # (fp16 operands: the 16-bit stream is fp16 too)

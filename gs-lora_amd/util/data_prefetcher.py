@@ -4,7 +4,9 @@ util/data_prefetcher.py:10-58: `.next()` yields `(samples, targets)` and `(None,
 MI355X-first implementation: a small ring of batches is kept in flight on a dedicated copy stream (a `hipStream_t` on ROCm). Host
 batches are staged through reusable PINNED buffers so that the H2D copy is a true asynchronous DMA over PCIe; every ring slot carries
 an event that (a) the consumer's stream waits on before using the batch and (b) guards the slot's pinned buffers against being
-overwritten while their copy is still running. Batches that already live on the device pass through untouched."""
+overwritten while their copy is still running. Batches that already live on the device pass through untouched. Any dtype travels as it
+is: a uint8 image batch (NCHW or channels_last) costs a quarter of a float one in pinned memory and on the bus, and a model that was told
+its normalisation (set_input_norm) consumes the bytes directly."""
 import collections
 
 import torch
@@ -31,8 +33,10 @@ class data_prefetcher:
         if t.is_cuda:
             return t.to(self._device, non_blocking=True)
         buf = slot["pinned"].get(key)
-        if buf is None or buf.shape != t.shape or buf.dtype != t.dtype:
-            buf = slot["pinned"][key] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        # (an NHWC image batch — uint8 bytes as a decoder leaves them, channels_last — keeps its layout: no host-side permute)
+        fmt = torch.channels_last if (t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)) else torch.contiguous_format
+        if buf is None or buf.shape != t.shape or buf.dtype != t.dtype or not buf.is_contiguous(memory_format=fmt):
+            buf = slot["pinned"][key] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True, memory_format=fmt)
         buf.copy_(t)
         return buf.to(self._device, non_blocking=True)
 

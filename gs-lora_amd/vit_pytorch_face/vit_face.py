@@ -195,12 +195,32 @@ class HipModelMixin:
     """Shared by the model families that run on ViTRunner (ViT_face, ModifiedViT): compute-dtype switch, the lazily built
     runner / flat LoRA bucket, and the one-autograd-node call."""
     _runner = None
+    input_norm = None               # (mean, std) once set_input_norm() was called: uint8 batches are raw bytes normalised in the patch gather
     accepts_batch_tuple = True      # forward(img) also takes a tuple of image batches, processed as one batch (gslora_hip.step)
 
     def set_compute_dtype(self, name):
         """'fp16' / 'bf16' (speed: 16-bit MFMA operands of that format, f32 accumulate; fp16 runs its backward on loss-scaled gradients)
         or 'fp32' (parity: exact-f32 kernels)."""
         self.compute_dtype = compute_dtype_of(name)
+        return self
+
+    def set_input_norm(self, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
+        """Declare that uint8 batches are raw image bytes, to be normalised as the dataset transform ToTensor() + Normalize(mean, std)
+        would: x = ((u / 255) - mean[c]) / std[c], evaluated inside the patch gather (gsl_patchify_u8 / gsl_unfold_patches_u8), so the
+        batch crosses the host boundary in one byte per sub-pixel. mean / std: one value per channel, or a name — "totensor" (mean 0,
+        std 1: the face drivers) or "imagenet" (the ImageNet constants: the ImageNet-100 driver). set_input_norm(None) withdraws it.
+        float batches are untouched either way; without this call a uint8 batch is a value cast, as the reference's inputs.float()."""
+        from gslora_hip import ops
+        if mean is None:
+            self.input_norm = None
+            return self
+        if isinstance(mean, str):
+            if mean.lower() not in ops.INPUT_NORMS:
+                raise ValueError(f"set_input_norm: unknown name {mean!r}; use one of {sorted(ops.INPUT_NORMS)} or per-channel values")
+            mean, std = ops.INPUT_NORMS[mean.lower()]
+        norm = (tuple(float(v) for v in mean), tuple(float(v) for v in std))
+        ops.u8_norm_table(*norm)      # validates (one entry per channel, non-zero std)
+        self.input_norm = norm
         return self
 
     def runner(self):

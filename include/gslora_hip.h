@@ -91,6 +91,19 @@ GSL_API int gsl_patchify(const float* img, void* out, int B, int C, int H, int W
 GSL_API int gsl_unfold_patches(const float* img, void* out, int B, int C, int H, int W, int k, int stride, int pad, int ldo, int dtype,
                                gsl_stream_t s);
 
+/* ---- K1 / K1s from uint8 images: the dataset transform ToTensor() + Normalize(mean, std) of the drivers (train/train_own_forget_cl.py:131-147)
+ * fused into the two gathers above, so that a batch crosses the host boundary as the decoder's bytes. img u8 in layout GSL_U8_NCHW
+ * ([B,C,H,W]) or GSL_U8_NHWC ([B,H,W,C]); table f32 [C][256] on the device: table[c*256 + u] is the value of byte u in channel c (the
+ * caller builds it with the expression it wants to match, ((u / 255) - mean[c]) / std[c] in f32). out is exactly what the float gather
+ * writes for the image of those values: cls rows, out-of-image taps and the K padding are 0 (not table[c][0]). img 8-byte aligned
+ * (gsl_unfold_patches_u8; gsl_patchify_u8 takes any address and loads 8 bytes at a time when p % 8 == 0, C is 1 or 3 and img is 8-byte
+ * aligned), out 16-byte aligned, k < 256; otherwise the float forms' conditions. */
+enum gsl_u8_layout { GSL_U8_NCHW = 0, GSL_U8_NHWC = 1 };
+GSL_API int gsl_patchify_u8(const uint8_t* img, int layout, const float* table, void* out, int B, int C, int H, int W, int p, int dtype,
+                            gsl_stream_t s);
+GSL_API int gsl_unfold_patches_u8(const uint8_t* img, int layout, const float* table, void* out, int B, int C, int H, int W, int k, int stride,
+                                  int pad, int ldo, int dtype, gsl_stream_t s);
+
 /* ---- K3/K5/K6/K7/K8 dense NT GEMM with an optional second K segment (the LoRA rank-r term)
  * and a fused epilogue. Replaces F.linear + loralib.Linear.forward (vit_face.py:330-334,349-356)
  * and their autograd dX.
