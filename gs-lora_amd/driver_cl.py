@@ -36,7 +36,7 @@ import engine_cl  # noqa: E402
 import loralib as lora  # noqa: E402
 from gslora_hip.optim import create_optimizer, create_scheduler  # noqa: E402
 from util.cal_norm import get_norm_of_lora  # noqa: E402
-from util.utils import AverageMeter, calculate_prototypes, count_trainable_parameters, reinitialize_lora_parameters  # noqa: E402
+from util.utils import AverageMeter, calculate_prototypes, count_trainable_parameters, perform_val, reinitialize_lora_parameters  # noqa: E402
 from vit_pytorch_face import ViT_face, ViTs_face  # noqa: E402
 
 METERS = ("losses_forget", "losses_remain", "losses_total", "losses_structure", "top1_forget", "top1_remain", "losses_prototype_forget",
@@ -85,6 +85,8 @@ def get_args(argv=None):
     p.add_argument("--u8_input", default=False, action="store_true",
                    help="feed uint8 images (the decoder's bytes): the model normalises them inside the patch gather (set_input_norm) "
                         "instead of a ToTensor() dataset transform on the host")
+    p.add_argument("--verify_pairs", type=int, default=0,
+                   help="after each task, face verification (util.utils.perform_val) on this many synthetic same / different pairs; 0: off")
     p.add_argument("--outdir", default=None)
     p.add_argument("--seed", type=int, default=1337)
     p.add_argument("--average_weight", default=False, action="store_true", help="EMA model of the reference (:502-507, :1058-1098)")
@@ -116,6 +118,29 @@ def synthetic_dataset(num_class, per_class, image_size, seed, u8=False):
     y = torch.arange(num_class).repeat_interleave(per_class)
     b = (x * 255).round().clamp(0, 255)
     return (b.to(torch.uint8) if u8 else b / 255.0), y
+
+
+def synthetic_pairs(n_pairs, num_class, image_size, seed, u8=False):
+    """A verification set in load_bin's layout (util/utils.py:38-57): ([images, flipped images] each [2 * n_pairs, 3, S, S], issame).
+    Even pairs are an image of synthetic_dataset and a noisy twin of it, odd pairs images of two different classes."""
+    x, y = synthetic_dataset(num_class, 2, image_size, seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    imgs, issame = [], []
+    for p in range(n_pairs):
+        a = int(torch.randint(0, x.shape[0], (1,), generator=g))
+        if p % 2 == 0:
+            twin = (x[a] + 0.05 * torch.randn(x[a].shape, generator=g)).clamp(0, 1)
+            imgs += [x[a], (twin * 255).round() / 255.0]
+        else:
+            b = int(torch.randint(0, x.shape[0], (1,), generator=g))
+            while int(y[b]) == int(y[a]):
+                b = (b + 2) % x.shape[0]      # two images per class: the next class
+            imgs += [x[a], x[b]]
+        issame.append(p % 2 == 0)
+    imgs = torch.stack(imgs)
+    if u8:
+        imgs = (imgs * 255).round().clamp(0, 255).to(torch.uint8)
+    return [imgs, imgs.flip(3)], issame
 
 
 def subset(x, y, classes):
@@ -241,8 +266,18 @@ def main(argv=None):
                     te_f=mk(subset(x_te, y_te, forget_cls), 5 * args.batch_size, False),
                     te_r=mk(subset(x_te, y_te, remain_cls), 5 * args.batch_size, False), protos=protos, info=dict(forget_cls=forget_cls))
 
+    after_task = None
+    if args.verify_pairs > 0:      # "is the backbone still a good face model?" after every forgetting task
+        pair_set, issame = synthetic_pairs(args.verify_pairs, args.num_class, geo["image_size"], args.seed + 2, u8=args.u8_input)
+
+        def after_task(task_i, model, ema_model, rec):
+            acc, std, xnorm, thr, _ = perform_val(False, dev, geo["dim"], 5 * args.batch_size, model, pair_set, issame)
+            rec["verification"] = dict(pairs=args.verify_pairs, accuracy=float(acc), std=float(std), xnorm=float(xnorm), best_threshold=float(thr))
+            print(f"[task {task_i}] verification on {args.verify_pairs} pairs: accuracy {acc:.4f} +- {std:.4f}, xnorm {xnorm:.3f}, "
+                  f"best threshold {thr:.3f}")
+
     cfg = {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net}
-    report, ema_model = run_tasks(model, args, task_data, dev, out, geo["depth"], cfg=cfg)
+    report, ema_model = run_tasks(model, args, task_data, dev, out, geo["depth"], cfg=cfg, after_task=after_task)
     return report, out, (model if ema_model is None else (model, ema_model))
 
 

@@ -19,6 +19,7 @@ DEV_LIB_PATH = os.path.join(_HERE, "libgslora_hip_dev.so")
 F32, BF16, F16 = 0, 1, 2      # F16: IEEE fp16 MFMA operands (round 5) — and, as an x_dtype, the forward residual stream format of both 16-bit modes
 EPI_STORE, EPI_BIAS_RES_F32, EPI_BIAS_GELU, EPI_MUL, EPI_PATCH, EPI_STORE_F32, EPI_STORE_QKV_HM, EPI_BIAS_RES_BF16, EPI_PATCH_BF16 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 EPI_MUL_G8, EPI_BIAS_GELU_G8, EPI_BIAS_RES_F16, EPI_PATCH_F16, EPI_STORE_LN, EPI_STORE_QKV_HM_LN = 9, 10, 11, 12, 13, 14
+VERIF_FLIP_SUM, VERIF_PLAIN = 0, 1      # modes of gsl_verif_pair_dist
 U8_NCHW, U8_NHWC = 0, 1        # source layout of the uint8 gathers (gsl_patchify_u8 / gsl_unfold_patches_u8)
 NORM_SPLIT = 8
 SEED_ON_DEVICE = 0x80000000   # flag bit of a `site` argument: `seed` is a device pointer to a uint64 (HIP-graph replays)
@@ -74,6 +75,9 @@ SIGNATURES = {
     "gsl_pack_pad": [_vp, _l, _l, _i, _i, _f, _vp, _i, _i, _i, _vp],
     "gsl_pack_pad_batch": [_vp, _i, _l, _i, _vp],
     "gsl_dropout_mask": [_vp, _l, _f, _u64, _u32, _vp],
+    "gsl_verif_pair_dist": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "gsl_verif_fold_counts": [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp],
+    "gsl_verif_select": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"gsl_last_error": C.c_char_p, "gsl_lora_grad_ws_elems": C.c_long, "gsl_gemm_mulgrad_ws_elems": C.c_long,
              "gsl_lora_grad_batch_ws_elems": C.c_long}

@@ -679,3 +679,64 @@ def dropout_mask(n, p_drop, seed, site, device):
     keep = torch.empty(n, device=device, dtype=torch.uint8)
     L.check(L.load().gsl_dropout_mask(_p(keep), n, float(p_drop), int(seed), int(site), _stream()), "gsl_dropout_mask")
     return keep
+
+
+# ---- face verification on pairs (csrc/verif.hip; util/verification.py, util.utils.perform_val)
+def _rows_f32(t, what):
+    """A 2-D f32 device tensor with unit inner stride (row slices such as emb[0::2] are taken with their stride, not copied)."""
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"gslora_hip: {what} must be a torch tensor on a ROCm GPU (the HIP path has no CPU fallback)")
+    _need(t, rows_ok=True)
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise RuntimeError(f"gslora_hip: {what} must be a 2-D float32 tensor")
+    return t
+
+
+def verif_pair_dist(e0, e1, want_normed=False):
+    """perform_val's middle (utils.py:205-216 + verification.py:67-68): e0, e1 [2P, D] = the embeddings of the original and of the flipped
+    images. Returns (dist [P], xnorm [1], the normalised embeddings [2P, D] or None)."""
+    e0, e1 = _rows_f32(e0, "e0"), _rows_f32(e1, "e1")
+    if e0.shape != e1.shape or e0.shape[0] % 2 or e0.stride(0) != e1.stride(0):
+        raise ValueError(f"verif_pair_dist: e0 and e1 must be [2P, D] of one shape and row stride, not {tuple(e0.shape)} / {tuple(e1.shape)}")
+    P, D = e0.shape[0] // 2, e0.shape[1]
+    dist = torch.empty(P, device=e0.device, dtype=torch.float32)
+    xnorm = torch.empty(1, device=e0.device, dtype=torch.float32)
+    ws = torch.empty(P, device=e0.device, dtype=torch.float32)
+    nemb = torch.empty(2 * P, D, device=e0.device, dtype=torch.float32) if want_normed else None
+    L.check(L.load().gsl_verif_pair_dist(_p(e0), _p(e1), e0.stride(0), P, D, L.VERIF_FLIP_SUM, _p(dist), _p(xnorm), _p(ws), _p(nemb), _stream()),
+            "gsl_verif_pair_dist")
+    return dist, xnorm, nemb
+
+
+def verif_sq_dist(a, b):
+    """dist[p] = sum (a[p] - b[p])^2 of two [P, D] embedding arrays (verification.py:67-68, 159-160)."""
+    a, b = _rows_f32(a, "embeddings1"), _rows_f32(b, "embeddings2")
+    if a.shape != b.shape or a.stride(0) != b.stride(0):
+        raise ValueError(f"verif_sq_dist: the two embedding arrays must share shape and row stride, not {tuple(a.shape)} / {tuple(b.shape)}")
+    dist = torch.empty(a.shape[0], device=a.device, dtype=torch.float32)
+    L.check(L.load().gsl_verif_pair_dist(_p(a), _p(b), a.stride(0), a.shape[0], a.shape[1], L.VERIF_PLAIN, _p(dist), None, None, None, _stream()),
+            "gsl_verif_pair_dist")
+    return dist
+
+
+def verif_fold_counts(dist, issame, thresholds, nrof_folds):
+    """dist [P] f32, issame [P] uint8, thresholds [Tn] f64 (device) -> (counts int32 [F, Tn, 2] = true / false accepts of each KFold test
+    fold, fold_tot int32 [F, 2] = same / different pairs of each fold)."""
+    _need(dist, issame, thresholds)
+    if dist.dtype != torch.float32 or issame.dtype != torch.uint8 or thresholds.dtype != torch.float64 or issame.numel() != dist.numel():
+        raise RuntimeError("verif_fold_counts: dist f32 [P], issame uint8 [P], thresholds f64 [Tn]")
+    F, Tn = int(nrof_folds), thresholds.numel()
+    counts = torch.empty(F, Tn, 2, device=dist.device, dtype=torch.int32)
+    tot = torch.empty(F, 2, device=dist.device, dtype=torch.int32)
+    L.check(L.load().gsl_verif_fold_counts(_p(dist), _p(issame), dist.numel(), _p(thresholds), Tn, F, _p(counts), _p(tot), _stream()),
+            "gsl_verif_fold_counts")
+    return counts, tot
+
+
+def verif_select(counts, fold_tot, thresholds, xnorm=None):
+    """-> f64 [2F + 2Tn + 1]: accuracy [F], best_thresholds [F], tpr [Tn], fpr [Tn], xnorm (0 if not given)."""
+    _need(counts, fold_tot, thresholds, xnorm)
+    F, Tn = counts.shape[0], counts.shape[1]
+    out = torch.zeros(2 * F + 2 * Tn + 1, device=counts.device, dtype=torch.float64)
+    L.check(L.load().gsl_verif_select(_p(counts), _p(fold_tot), _p(thresholds), Tn, F, _p(xnorm), _p(out), _stream()), "gsl_verif_select")
+    return out

@@ -1,8 +1,9 @@
 """Step helpers of the reference's util/utils.py that sit on the GS-LoRA path
 (AverageMeter :316-332, train_accuracy :354-368, count_trainable_parameters :423-425,
 reinitialize_lora_parameters :428-441, calculate_prototypes :502-549, replace_ffn_with_lora :552-577,
-modify_head :580-621, resume_head :623-636, create_few_shot_dataset :457-499, get_unique_classes :444-454), backed by the HIP model.
-Data plumbing and face verification of that file are out of scope."""
+modify_head :580-621, resume_head :623-636, create_few_shot_dataset :457-499, get_unique_classes :444-454) and its face verification
+(perform_val :167-230, buffer_val :298-314), backed by the HIP model and the HIP metric kernels (util/verification.py).
+Data plumbing (load_bin / get_val_pair: mxnet, bcolz) and perform_val_deit are out of scope."""
 import copy
 import datetime
 import math
@@ -98,6 +99,92 @@ def calculate_prototypes(backbone, dataset, batch_size=32, device="cuda", aug_nu
             counts.index_add_(0, labels, torch.ones_like(labels, dtype=torch.float32))
     sums, counts = sums.cpu(), counts.cpu()
     return {int(c): (sums[c] / counts[c]) for c in torch.nonzero(counts).flatten().tolist()}
+
+
+def _eval_dtype_of(net):
+    """The compute dtype evaluation switches to (None: stay in the model's own), chosen as engine_cl.eval_data chooses it."""
+    import engine_cl
+    if engine_cl.EVAL_DTYPE in engine_cl._EVAL_SAME or not hasattr(net, "set_compute_dtype"):
+        return None
+    return engine_cl.EVAL_DTYPE
+
+
+def pair_embeddings(device, embedding_size, batch_size, backbone, data_set):
+    """The embedding pass of perform_val (reference :187-203): data_set = [images, flipped images], each [2P, C, H, W] (float, or uint8
+    bytes for a model that was given set_input_norm). Batches of batch_size with the ragged tail; the original and the flipped batch of
+    the same indices go through ONE forward as two parts. Returns (e0, e1), f32 [2P, embedding_size] on the device. The model must be
+    in eval mode already; no mode or dtype is changed here."""
+    if len(data_set) != 2 or len(data_set[0]) != len(data_set[1]):
+        raise ValueError("perform_val: data_set is [images, flipped images] of one length")
+    n = len(data_set[0])
+    e = [torch.empty(n, embedding_size, device=device, dtype=torch.float32) for _ in range(2)]
+    as_parts = getattr(backbone, "accepts_batch_tuple", False)
+    with torch.no_grad():
+        idx = 0
+        while idx < n:      # full batches, then the ragged tail (:193-202)
+            stop = min(idx + batch_size, n)
+            parts = [torch.as_tensor(c[idx:stop]).to(device) for c in data_set]
+            outs = backbone(tuple(parts)) if as_parts else [backbone(t) for t in parts]
+            if as_parts:
+                outs = outs[-1] if isinstance(outs, (tuple, list)) else outs      # ModifiedViT returns (logits, cls embeddings)
+                outs = [outs[:stop - idx], outs[stop - idx:]]
+            else:
+                outs = [o[-1] if isinstance(o, (tuple, list)) else o for o in outs]
+            for dst, o in zip(e, outs):
+                if o.shape != (stop - idx, embedding_size):
+                    raise ValueError(f"perform_val: the backbone returned {tuple(o.shape)} for {stop - idx} images, embedding_size is {embedding_size}")
+                dst[idx:stop] = o
+            idx = stop
+    return e[0], e[1]
+
+
+def perform_val(multi_gpu, device, embedding_size, batch_size, backbone, data_set, issame, nrof_folds=10):
+    """Face verification on a pair set (LFW etc.; reference :167-230): embeddings of the images and of their flipped copies, summed and
+    normalised, squared distance per pair, nrof_folds-fold threshold selection. Embeddings stay on the device; the metric runs in the HIP
+    kernels of util/verification.py with one host read at the end.
+
+    :return: (accuracy.mean(), accuracy.std(), xnorm, best_thresholds.mean(), roc) as the reference, except the fifth element: the ROC
+        itself, a float32 CPU tensor [2, 400] = (fpr, tpr) over the thresholds np.arange(0, 4, 0.01), not a matplotlib JPEG of it.
+
+    The evaluation dtype is engine_cl.eval_data's (GSLORA_EVAL_DTYPE, f32 by default). Unlike the reference, which leaves the model in
+    eval(), the model's train / eval mode (and with it the LoRA merge state) and its compute dtype are restored before returning."""
+    import numpy as np
+    from gslora_hip import ops
+    from util import verification
+    if multi_gpu:
+        backbone = backbone.module      # unpackage model from DataParallel
+    backbone = backbone.to(device)
+    verification.fold_bounds(len(issame), nrof_folds)      # argument errors before any GPU work
+    was_training = backbone.training
+    eval_dt, own_dt = _eval_dtype_of(backbone), getattr(backbone, "compute_dtype", None)
+    backbone.eval()
+    if eval_dt:
+        backbone.set_compute_dtype(eval_dt)
+    try:
+        e0, e1 = pair_embeddings(device, embedding_size, batch_size, backbone, data_set)
+    finally:
+        if eval_dt:
+            backbone.set_compute_dtype(own_dt)
+        backbone.train(was_training)
+    dist, xnorm, _ = ops.verif_pair_dist(e0, e1)
+    print("embeddings shape", tuple(e0.shape))
+    tpr, fpr, accuracy, best_thresholds, xn = verification.roc_from_dist(verification.THRESHOLDS, dist[:len(issame)], issame, nrof_folds, xnorm)
+    roc = torch.from_numpy(np.stack([fpr, tpr]).astype(np.float32))
+    return accuracy.mean(), accuracy.std(), xn, best_thresholds.mean(), roc
+
+
+def buffer_val(db_name, acc, std, xnorm, best_threshold, roc_curve_tensor, batch):
+    """Log one perform_val result (reference :298-314 sends the four scalars to wandb; here they go to wandb when it is importable and a
+    run is active, and are returned either way)."""
+    rec = {"{}_Accuracy".format(db_name): acc, "{}_Std".format(db_name): std, "{}_XNorm".format(db_name): xnorm,
+           "{}_Best_Threshold".format(db_name): best_threshold}
+    try:
+        import wandb
+        if getattr(wandb, "run", None) is not None:
+            wandb.log(rec, step=batch)
+    except ImportError:
+        pass
+    return rec
 
 
 def get_unique_classes(subset, original_dataset):

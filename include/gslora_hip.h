@@ -354,6 +354,26 @@ typedef struct gsl_pack_desc {
 } gsl_pack_desc;
 GSL_API int gsl_pack_pad_batch(const gsl_pack_desc* descs_dev, int n, long max_elems, int dtype, gsl_stream_t s);
 
+/* ---- face verification on pairs (util/utils.py:167-230 perform_val, util/verification.py evaluate / calculate_val); csrc/verif.hip.
+ * V1, mode GSL_VERIF_FLIP_SUM: e0, e1 f32 [2P, D] (row stride ld elements) = the embeddings of the original and of the flipped images (rows
+ * 2p, 2p + 1 = pair p), D <= 1024. Per row s = e0 + e1, n = s / ||s|| (a zero row stays zero, as sklearn.preprocessing.normalize);
+ * dist[p] = sum (n[2p] - n[2p+1])^2; xnorm[0] = mean of the 4P row norms of e0 and e1. pair_norm_ws f32 [P] scratch; nemb (nullable) f32
+ * [2P, D] receives n. Mode GSL_VERIF_PLAIN: e0, e1 [P, D], dist[p] = sum (e0[p] - e1[p])^2 (xnorm, pair_norm_ws, nemb unused) — on the nemb
+ * of the other mode the same distances bit for bit. One wave64 per pair, fixed-order sums. */
+enum { GSL_VERIF_FLIP_SUM = 0, GSL_VERIF_PLAIN = 1 };
+GSL_API int gsl_verif_pair_dist(const float* e0, const float* e1, long ld, int P, int D, int mode, float* dist, float* xnorm,
+                        float* pair_norm_ws, float* nemb, gsl_stream_t s);
+/* V2: decision counts of the un-shuffled KFold(nrof_folds) TEST folds (contiguous, the first P % F one longer): counts int32 [F][Tn][2] =
+ * { #(dist < thr & same), #(dist < thr & different) } with the compare (double)dist < thresholds[t], strict (np.less); fold_tot int32 [F][2] =
+ * { same, different } pairs of the fold. The thresholds (f64, any order) are taken as given. The train counts of a fold are the totals minus it. */
+GSL_API int gsl_verif_fold_counts(const float* dist, const uint8_t* issame, int P, const double* thresholds, int Tn, int nrof_folds,
+                          int* counts, int* fold_tot, gsl_stream_t s);
+/* V3: out f64 [2F + 2Tn + 1] = accuracy[F] (test accuracy at the fold's best threshold), best_threshold[F] (first arg-max of the train
+ * accuracy, np.argmax's tie rule), tpr[Tn], fpr[Tn] (means over the folds in fold order, 0 where a fold has no same / different pair), and
+ * (double)xnorm[0] if xnorm is given. Integer arithmetic up to the final IEEE f64 divisions. */
+GSL_API int gsl_verif_select(const int* counts, const int* fold_tot, const double* thresholds, int Tn, int nrof_folds, const float* xnorm,
+                     double* out, gsl_stream_t s);
+
 /* dropout keep-mask as the kernels compute it (for tests): keep[i] = 1/0 for element index i. */
 GSL_API int gsl_dropout_mask(uint8_t* keep, long n, float p_drop, uint64_t seed, uint32_t site, gsl_stream_t s);
 
