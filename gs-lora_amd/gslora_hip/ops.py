@@ -106,6 +106,20 @@ def _image_parts(img, table, what):
     return parts, src
 
 
+def _gather_parts(entry, parts, src, table, out, T, *geom):
+    """The per-batch launches of patchify / unfold_patches: batch i lands in its row range of `out` (T rows per image) through `entry`
+    (float images) or `entry`_u8 (bytes, their layout code and the value table in front of the same arguments)."""
+    row = 0
+    for i, t in enumerate(parts):
+        if src is None:
+            L.check(getattr(L.load(), entry)(_p(t), _p(out[row:]), t.shape[0], *geom, _stream()), entry)
+        else:
+            L.check(getattr(L.load(), entry + "_u8")(_p(src[i][1]), src[i][0], _p(table), _p(out[row:]), t.shape[0], *geom, _stream()),
+                    entry + "_u8")
+        row += t.shape[0] * T
+    return out
+
+
 def patchify(img, p, dtype, table=None):
     """img: one [B, C, H, W] batch or a list of batches of one image shape; the batches land in consecutive row ranges of the output.
     float32 batches are gathered as they are; uint8 batches (NCHW-contiguous or channels_last) are normalised through `table` on the way."""
@@ -113,15 +127,7 @@ def patchify(img, p, dtype, table=None):
     _, Cc, H, W = parts[0].shape
     T = 1 + (H // p) * (W // p)
     out = torch.empty(sum(t.shape[0] for t in parts) * T, p * p * Cc, device=parts[0].device, dtype=dtype)
-    row = 0
-    for i, t in enumerate(parts):
-        if src is None:
-            L.check(L.load().gsl_patchify(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, p, code(dtype), _stream()), "gsl_patchify")
-        else:
-            L.check(L.load().gsl_patchify_u8(_p(src[i][1]), src[i][0], _p(table), _p(out[row:]), t.shape[0], Cc, H, W, p, code(dtype), _stream()),
-                    "gsl_patchify_u8")
-        row += t.shape[0] * T
-    return out
+    return _gather_parts("gsl_patchify", parts, src, table, out, T, Cc, H, W, p, code(dtype))
 
 
 def unfold_geometry(H, W, k, stride, pad):
@@ -139,16 +145,22 @@ def unfold_patches(img, k, stride, pad, dtype, table=None):
     T = 1 + Lh * Lw
     kpad = -(-Cc * k * k // 64) * 64
     out = torch.empty(sum(t.shape[0] for t in parts) * T, kpad, device=parts[0].device, dtype=dtype)
-    row = 0
-    for i, t in enumerate(parts):
-        if src is None:
-            L.check(L.load().gsl_unfold_patches(_p(t), _p(out[row:]), t.shape[0], Cc, H, W, k, stride, pad, kpad, code(dtype), _stream()),
-                    "gsl_unfold_patches")
-        else:
-            L.check(L.load().gsl_unfold_patches_u8(_p(src[i][1]), src[i][0], _p(table), _p(out[row:]), t.shape[0], Cc, H, W, k, stride, pad,
-                                                   kpad, code(dtype), _stream()), "gsl_unfold_patches_u8")
-        row += t.shape[0] * T
-    return out
+    return _gather_parts("gsl_unfold_patches", parts, src, table, out, T, Cc, H, W, k, stride, pad, kpad, code(dtype))
+
+
+_ws_cache = {}
+_ws_retired = []
+
+
+def _workspace(key, need, device, floor=0):
+    """The f32 scratch buffer of `key`, grown to `need` elements (at least `floor` when it is created or grown). A buffer that is
+    outgrown is retired, never freed: a captured HIP graph may still launch with it."""
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        if ws is not None:
+            _ws_retired.append(ws)
+        ws = _ws_cache[key] = torch.empty(max(need, floor), device=device, dtype=torch.float32)
+    return ws
 
 
 # optional per-kernel timing hook used by bench.py: {tag: [(start_event, end_event), ...]} recorded on the
@@ -158,22 +170,31 @@ PROFILE = None
 
 def _profiled(tag, shape_of):
     """bench.py: when PROFILE holds `tag`, bracket the launch with HIP events on the launch stream and record (ev0, ev1, *shape_of(args)).
-    (The GEMM wrappers do this per call-site tag; these are the memory-bound kernels of the step: LayerNorm and attention.)"""
+    tag None: the tag is the call's own `tag=` keyword (the GEMM wrappers are tagged per call site; the fixed tags are the memory-bound
+    kernels of the step: LayerNorm and attention)."""
     def deco(fn):
         def wrapped(*a, **kw):
-            if PROFILE is None or tag not in PROFILE:
+            if PROFILE is None:
+                return fn(*a, **kw)
+            t = tag or kw.get("tag")
+            if t not in PROFILE:
                 return fn(*a, **kw)
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
             out = fn(*a, **kw)
             ev[1].record()
-            PROFILE[tag].append((ev[0], ev[1]) + tuple(shape_of(*a, **kw)))
+            PROFILE[t].append((ev[0], ev[1]) + tuple(shape_of(*a, **kw)))
             return out
         wrapped.__name__, wrapped.__doc__ = fn.__name__, fn.__doc__
         return wrapped
     return deco
 
 
+def _gemm_shape(A, W, *a, A2=None, **kw):
+    return A.shape[0], W.shape[0], A.shape[1], 0 if A2 is None else A2.shape[1]      # M, N, K1, K2
+
+
+@_profiled(None, _gemm_shape)
 def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, bias=None, res=None, aux=None, out2=None,
             pos=None, cls=None, T=0, p_drop=0.0, seed=0, site=0, tag=None):
     _need(A2, W2, bias, aux, out2, pos, cls)
@@ -183,14 +204,6 @@ def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, b
     M, K1 = A1.shape
     N = W1.shape[0]
     K2 = 0 if A2 is None else A2.shape[1]
-    if PROFILE is not None and tag in PROFILE:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        gemm_nt(A1, W1, out, epilogue=epilogue, A2=A2, W2=W2, alpha=alpha, bias=bias, res=res, aux=aux, out2=out2, pos=pos,
-                cls=cls, T=T, p_drop=p_drop, seed=seed, site=site, tag=None)
-        ev[1].record()
-        PROFILE[tag].append((ev[0], ev[1], M, N, K1, K2))
-        return out
     L.check(L.load().gsl_gemm_nt(_p(A1), A1.stride(0), _p(W1), W1.stride(0), K1, _p(A2), 0 if A2 is None else A2.stride(0),
                                  _p(W2), 0 if W2 is None else W2.stride(0), K2, M, N, code(A1.dtype), epilogue, float(alpha),
                                  _p(bias), _p(res), _p(aux), _p(out), _p(out2), out.stride(0), _p(pos), _p(cls), int(T),
@@ -198,20 +211,13 @@ def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, b
     return out
 
 
+@_profiled(None, _gemm_shape)
 def gemm_nt_lora(A, W, P, Q, lora_scale, tout, out, *, epilogue=L.EPI_STORE, bias=None, res=None, aux=None, out2=None, p_drop=0.0,
                  seed=0, site=0, tag=None):
     """out = epilogue(A W^T + t Q^T), t = lora_scale * A P^T computed inside the kernel and stored to tout [M,64] (bf16)."""
     _need(A, W, P, Q, tout, out, bias, res, aux, out2)
     M, K = A.shape
     N = W.shape[0]
-    if PROFILE is not None and tag in PROFILE:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        gemm_nt_lora(A, W, P, Q, lora_scale, tout, out, epilogue=epilogue, bias=bias, res=res, aux=aux, out2=out2, p_drop=p_drop,
-                     seed=seed, site=site)
-        ev[1].record()
-        PROFILE[tag].append((ev[0], ev[1], M, N, K, 0))
-        return out
     L.check(L.load().gsl_gemm_nt_lora(_p(A), A.stride(0), _p(W), W.stride(0), K, _p(P), P.stride(0), _p(Q), Q.stride(0),
                                       float(lora_scale), _p(tout), 0 if tout is None else tout.stride(0), M, N, code(A.dtype), epilogue,
                                       _p(bias), _p(res), _p(aux), _p(out), _p(out2), out.stride(0), float(p_drop), int(seed), int(site),
@@ -219,6 +225,7 @@ def gemm_nt_lora(A, W, P, Q, lora_scale, tout, out, *, epilogue=L.EPI_STORE, bia
     return out
 
 
+@_profiled(None, _gemm_shape)
 def gemm_nt_lora_mulgrad(A, W, P, Q, lora_scale, tout, out, aux, U1, G1, g1s, Y2, G2, g2s, r, accumulate=True, tag=None, p_drop=0.0, gscale=None):
     """out = (A W^T + t Q^T) * aux with t = lora_scale * A P^T (as gemm_nt_lora, epilogue MUL) and, from the same tiles,
     G1[n*g1s[0] + j*g1s[1]] (+)= sum_m out[m,n] U1[m,j] and G2[n*g2s[0] + j*g2s[1]] (+)= sum_m Y2[m,n] t[m,j].
@@ -227,24 +234,11 @@ def gemm_nt_lora_mulgrad(A, W, P, Q, lora_scale, tout, out, aux, U1, G1, g1s, Y2
     _need(A, W, P, Q, tout, out, aux, U1, Y2, gscale)
     M, K = A.shape
     N = W.shape[0]
-    if PROFILE is not None and tag in PROFILE:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-        gemm_nt_lora_mulgrad(A, W, P, Q, lora_scale, tout, out, aux, U1, G1, g1s, Y2, G2, g2s, r, accumulate, p_drop=p_drop, gscale=gscale)
-        ev[1].record()
-        PROFILE[tag].append((ev[0], ev[1], M, N, K, 0))
-        return out
     if not (out.stride(0) == aux.stride(0) == Y2.stride(0) and U1.stride(1) == 1):
         raise RuntimeError("gemm_nt_lora_mulgrad: out / aux / Y2 must share one row stride")
     lib = L.load()
     need = lib.gsl_gemm_mulgrad_ws_elems(M, N, r)
-    key = (A.device.index, "mulgrad")
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _ws_retired.append(ws)
-        ws = torch.empty(need, device=A.device, dtype=torch.float32)
-        _ws_cache[key] = ws
+    ws = _workspace((A.device.index, "mulgrad"), need, A.device)
     L.check(lib.gsl_gemm_nt_lora_mulgrad(_p(A), A.stride(0), _p(W), W.stride(0), K, _p(P), P.stride(0), _p(Q), Q.stride(0),
                                          float(lora_scale), _p(tout), 0 if tout is None else tout.stride(0), M, N, _p(aux), _p(out),
                                          out.stride(0), _p(U1), U1.stride(0), G1.data_ptr(), g1s[0], g1s[1], _p(Y2), G2.data_ptr(),
@@ -368,8 +362,6 @@ def attention_bwd_cls(qkv, o, d_o_cls, lse, B, T, H, scale, layout=0, q_cls=None
     return (dqkv, dq) if layout == 2 else dqkv
 
 
-_ws_cache = {}
-_ws_retired = []
 
 
 def lora_grad(Y, U, G, gsn, gsj, r, accumulate=True, gscale=None):
@@ -380,13 +372,7 @@ def lora_grad(Y, U, G, gsn, gsj, r, accumulate=True, gscale=None):
     M, N = Y.shape
     lib = L.load()
     need = lib.gsl_lora_grad_ws_elems(M, N, r)
-    key = (Y.device.index,)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _ws_retired.append(ws)      # a captured HIP graph may still launch with the old workspace: never free it
-        ws = torch.empty(max(need, 1 << 22), device=Y.device, dtype=torch.float32)
-        _ws_cache[key] = ws
+    ws = _workspace((Y.device.index,), need, Y.device, floor=1 << 22)
     L.check(lib.gsl_lora_grad(_p(Y), Y.stride(0), _p(U), U.stride(0), G.data_ptr(), gsn, gsj, M, N, r, code(Y.dtype),
                               1 if accumulate else 0, _p(ws), _p(gscale), _stream()), "gsl_lora_grad")
 
@@ -419,13 +405,7 @@ def lora_grad_batch(entries, gscale=None):
     if need < 0:
         L.check(int(need), "gsl_lora_grad_batch_ws_elems")
     dev = entries[0][0].device
-    key = (dev.index,)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _ws_retired.append(ws)      # a captured HIP graph may still launch with the old workspace: never free it
-        ws = torch.empty(max(need, 1 << 22), device=dev, dtype=torch.float32)
-        _ws_cache[key] = ws
+    ws = _workspace((dev.index,), need, dev, floor=1 << 22)
     L.check(lib.gsl_lora_grad_batch(arr, len(entries), _p(ws), code(entries[0][0].dtype), _p(gscale), _stream()), "gsl_lora_grad_batch")
 
 
@@ -475,7 +455,11 @@ def cosface_prep(W):
     return Wn
 
 
-def head_fwd(x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_bias=None, linear=False, pool_mean=False):
+HEAD_KINDS = {"cosface": 0, "arcface": 1}      # head_kind of gsl_head_fwd_margin / gsl_head_bwd_margin
+
+
+def _head_fwd(entry, margin, x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_bias, linear, pool_mean):
+    """gsl_head_fwd, or (margin = (kind, m, easy_margin)) gsl_head_fwd_margin, which takes those three and cos_y behind the same arguments."""
     _need(x, gamma, beta, Wn, label, head_bias)
     dev = x.device
     emb = torch.empty(B, D, device=dev, dtype=torch.float32)
@@ -483,10 +467,44 @@ def head_fwd(x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_bias=No
     rstd = torch.empty(B, device=dev, dtype=torch.float32)
     C = Wn.shape[0] if Wn is not None else 0
     logits = torch.empty(B, C, device=dev, dtype=torch.float32) if (label is not None or linear) else None
-    L.check(L.load().gsl_head_fwd(_p(x), code(x.dtype), T, _p(gamma), _p(beta), float(eps), _p(Wn), _p(label), _p(emb), _p(mean), _p(rstd),
-                                  _p(logits), B, D, C, float(cos_s), float(cos_m), _p(head_bias), 1 if linear else 0,
-                                  1 if pool_mean else 0, _stream()), "gsl_head_fwd")
-    return logits, emb, mean, rstd
+    cos_y = torch.empty(B, device=dev, dtype=torch.float32) if (margin and margin[0] and logits is not None) else None
+    tail = (margin[0], float(margin[1]), 1 if margin[2] else 0, _p(cos_y)) if margin else ()
+    L.check(getattr(L.load(), entry)(_p(x), code(x.dtype), T, _p(gamma), _p(beta), float(eps), _p(Wn), _p(label), _p(emb), _p(mean),
+                                     _p(rstd), _p(logits), B, D, C, float(cos_s), float(cos_m), _p(head_bias), 1 if linear else 0,
+                                     1 if pool_mean else 0, *tail, _stream()), entry)
+    return logits, emb, mean, rstd, cos_y
+
+
+def head_fwd(x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_bias=None, linear=False, pool_mean=False):
+    return _head_fwd("gsl_head_fwd", None, x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_bias, linear, pool_mean)[:4]
+
+
+def head_fwd_margin(x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_kind, m=0.5, easy_margin=False, head_bias=None,
+                    linear=False, pool_mean=False):
+    """head_fwd with the margin head chosen by head_kind ("cosface" | "arcface"; gsl_head_fwd_margin). m / easy_margin: the ArcFace
+    margin (cos_m is CosFace's). Returns (logits, emb, mean, rstd, cos_y): cos_y [B] is the label column's cosine before the margin
+    (ArcFace with labels; None otherwise), which head_bwd_margin needs."""
+    return _head_fwd("gsl_head_fwd_margin", (HEAD_KINDS[head_kind], m, easy_margin), x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m,
+                     head_bias, linear, pool_mean)
+
+
+def _head_bwd(entry, margin, dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype, p_drop, seed, site, linear, pool_mean,
+              stream_dtype, compact, gscale, target_exp):
+    """gsl_head_bwd, or (margin = (kind, m, easy_margin, cos_y, label)) gsl_head_bwd_margin, which takes those five behind the same arguments."""
+    _need(dlogits, demb, x, gamma, mean, rstd, emb, Wn, gscale, *(margin[3:] if margin else ()))
+    if gscale is not None and (gscale.numel() < 4 or gscale.dtype != torch.float32):
+        raise RuntimeError(f"{entry[4:]}: gscale must be a float32 tensor of 4 elements {{S, 1/S, seen maximum, exponent}}")
+    amax_ws = torch.empty(B, device=x.device, dtype=torch.float32) if gscale is not None else None
+    rows = B if compact else B * T
+    dx = torch.empty(rows, D, device=x.device, dtype=stream_dtype)
+    dxb = torch.empty(rows, D, device=x.device, dtype=dtype)
+    C = Wn.shape[0] if Wn is not None else 0
+    tail = (margin[0], float(margin[1]), 1 if margin[2] else 0, _p(margin[3]), _p(margin[4])) if margin else ()
+    L.check(getattr(L.load(), entry)(_p(dlogits), _p(demb), _p(x), code(x.dtype), T, _p(gamma), _p(mean), _p(rstd), _p(emb), _p(Wn), _p(dx),
+                                     _p(dxb), B, D, C, float(cos_s), code(dtype), code(stream_dtype), float(p_drop), int(seed), int(site),
+                                     1 if linear else 0, 1 if pool_mean else 0, 1 if compact else 0, _p(gscale), _p(amax_ws),
+                                     int(target_exp), *tail, _stream()), entry)
+    return dx, dxb
 
 
 def head_bwd(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype, p_drop=0.0, seed=0, site=0, linear=False,
@@ -496,43 +514,8 @@ def head_bwd(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype
     multiplied by the power of two S the kernel picks from their largest magnitude; gscale receives {S, 1/S} for the LoRA-gradient
     reductions, [2] is cleared for the overflow guard of this backward (layernorm_bwd(gmax=gscale[2:])) and [3] carries the exponent in use
     (gsl_head_bwd). target_exp: 0 = the default 11."""
-    _need(dlogits, demb, x, gamma, mean, rstd, emb, Wn, gscale)
-    if gscale is not None and (gscale.numel() < 4 or gscale.dtype != torch.float32):
-        raise RuntimeError("head_bwd: gscale must be a float32 tensor of 4 elements {S, 1/S, seen maximum, exponent}")
-    amax_ws = torch.empty(B, device=x.device, dtype=torch.float32) if gscale is not None else None
-    rows = B if compact else B * T
-    dx = torch.empty(rows, D, device=x.device, dtype=stream_dtype)
-    dxb = torch.empty(rows, D, device=x.device, dtype=dtype)
-    C = Wn.shape[0] if Wn is not None else 0
-    L.check(L.load().gsl_head_bwd(_p(dlogits), _p(demb), _p(x), code(x.dtype), T, _p(gamma), _p(mean), _p(rstd), _p(emb), _p(Wn), _p(dx),
-                                  _p(dxb), B, D, C, float(cos_s), code(dtype), code(stream_dtype), float(p_drop), int(seed), int(site),
-                                  1 if linear else 0, 1 if pool_mean else 0, 1 if compact else 0, _p(gscale), _p(amax_ws), int(target_exp), _stream()),
-            "gsl_head_bwd")
-    return dx, dxb
-
-
-HEAD_KINDS = {"cosface": 0, "arcface": 1}      # head_kind of gsl_head_fwd_margin / gsl_head_bwd_margin
-
-
-def head_fwd_margin(x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_kind, m=0.5, easy_margin=False, head_bias=None,
-                    linear=False, pool_mean=False):
-    """head_fwd with the margin head chosen by head_kind ("cosface" | "arcface"; gsl_head_fwd_margin). m / easy_margin: the ArcFace
-    margin (cos_m is CosFace's). Returns (logits, emb, mean, rstd, cos_y): cos_y [B] is the label column's cosine before the margin
-    (ArcFace with labels; None otherwise), which head_bwd_margin needs."""
-    _need(x, gamma, beta, Wn, label, head_bias)
-    kind = HEAD_KINDS[head_kind]
-    dev = x.device
-    emb = torch.empty(B, D, device=dev, dtype=torch.float32)
-    mean = torch.empty(B, device=dev, dtype=torch.float32)
-    rstd = torch.empty(B, device=dev, dtype=torch.float32)
-    C = Wn.shape[0] if Wn is not None else 0
-    logits = torch.empty(B, C, device=dev, dtype=torch.float32) if (label is not None or linear) else None
-    cos_y = torch.empty(B, device=dev, dtype=torch.float32) if (kind and logits is not None) else None
-    L.check(L.load().gsl_head_fwd_margin(_p(x), code(x.dtype), T, _p(gamma), _p(beta), float(eps), _p(Wn), _p(label), _p(emb), _p(mean),
-                                         _p(rstd), _p(logits), B, D, C, float(cos_s), float(cos_m), _p(head_bias), 1 if linear else 0,
-                                         1 if pool_mean else 0, kind, float(m), 1 if easy_margin else 0, _p(cos_y), _stream()),
-            "gsl_head_fwd_margin")
-    return logits, emb, mean, rstd, cos_y
+    return _head_bwd("gsl_head_bwd", None, dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype, p_drop, seed, site, linear,
+                     pool_mean, stream_dtype, compact, gscale, target_exp)
 
 
 def head_bwd_margin(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s, dtype, head_kind, m=0.5, easy_margin=False, cos_y=None,
@@ -540,21 +523,9 @@ def head_bwd_margin(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s
                     gscale=None, target_exp=0):
     """head_bwd with the margin head chosen by head_kind (gsl_head_bwd_margin). ArcFace with dlogits needs the forward's cos_y and the
     labels; everything else as head_bwd."""
-    _need(dlogits, demb, x, gamma, mean, rstd, emb, Wn, gscale, cos_y, label)
-    if gscale is not None and (gscale.numel() < 4 or gscale.dtype != torch.float32):
-        raise RuntimeError("head_bwd_margin: gscale must be a float32 tensor of 4 elements {S, 1/S, seen maximum, exponent}")
-    amax_ws = torch.empty(B, device=x.device, dtype=torch.float32) if gscale is not None else None
-    rows = B if compact else B * T
-    dx = torch.empty(rows, D, device=x.device, dtype=stream_dtype)
-    dxb = torch.empty(rows, D, device=x.device, dtype=dtype)
-    C = Wn.shape[0] if Wn is not None else 0
-    L.check(L.load().gsl_head_bwd_margin(_p(dlogits), _p(demb), _p(x), code(x.dtype), T, _p(gamma), _p(mean), _p(rstd), _p(emb), _p(Wn),
-                                         _p(dx), _p(dxb), B, D, C, float(cos_s), code(dtype), code(stream_dtype), float(p_drop), int(seed),
-                                         int(site), 1 if linear else 0, 1 if pool_mean else 0, 1 if compact else 0, _p(gscale), _p(amax_ws),
-                                         int(target_exp), HEAD_KINDS[head_kind], float(m), 1 if easy_margin else 0, _p(cos_y), _p(label),
-                                         _stream()),
-            "gsl_head_bwd_margin")
-    return dx, dxb
+    return _head_bwd("gsl_head_bwd_margin", (HEAD_KINDS[head_kind], m, easy_margin, cos_y, label), dlogits, demb, x, B, T, D, gamma, mean,
+                     rstd, emb, Wn, cos_s, dtype, p_drop, seed, site, linear, pool_mean, stream_dtype, compact, gscale, target_exp)
+
 
 def ce_fwd(logits, labels):
     _need(logits, labels)
@@ -643,9 +614,11 @@ def transpose_cast(W, dtype):
     return out
 
 
-def pack_pad(src, si, sj, rows, cols, rows_out, ld_out, dtype, scale=1.0):
-    _need(src)
-    out = torch.empty(rows_out, ld_out, device=src.device, dtype=dtype)
+def pack_pad(src, si, sj, rows, cols, rows_out, ld_out, dtype, scale=1.0, out=None):
+    """out given: that [rows_out, ld_out] buffer is rewritten in place (the persistent LoRA packs of the runner)."""
+    _need(src, out)
+    if out is None:
+        out = torch.empty(rows_out, ld_out, device=src.device, dtype=dtype)
     L.check(L.load().gsl_pack_pad(_p(src), si, sj, rows, cols, float(scale), _p(out), rows_out, ld_out, code(dtype), _stream()),
             "gsl_pack_pad")
     return out

@@ -186,6 +186,42 @@ class LoraBucket:
         return fresh
 
 
+def _res_epilogue(dtype):
+    """The GEMM epilogue out = res + drop(acc + bias), by the dtype of the stream that res and out share."""
+    return {torch.bfloat16: L.EPI_BIAS_RES_BF16, torch.float16: L.EPI_BIAS_RES_F16}.get(dtype, L.EPI_BIAS_RES_F32)
+
+
+class _Pass:
+    """What every step of one pass reads, computed once by the forward; the backward of the same pass goes on with it (`saved["ctx"]`)
+    and adds its own state: the loss scale and its overflow guard, the gradient views, the deferred LoRA-gradient reductions."""
+    __slots__ = ("sp", "dt", "xdt", "epi_res", "epi_patch", "B", "T", "D", "H", "M", "dev", "seed", "sflag", "p_drop", "p_emb", "r",
+                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending")
+
+    def __init__(self, sp, dt, B, dev, training, seed, sflag, save):
+        self.sp, self.dt, self.dev, self.seed, self.sflag, self.save = sp, dt, dev, seed, sflag, save
+        self.B, self.T, self.D, self.H, self.M = B, sp.num_tokens, sp.dim, sp.heads, B * sp.num_tokens
+        self.p_drop = sp.dropout_p if training else 0.0
+        self.p_emb = sp.emb_dropout_p if training else 0.0
+        self.r, self.eps = sp.lora_rank, sp.ln_eps
+        self.attn_site = self.r > 0 and sp.lora_site == "attention"
+        self.s_lora = (1.0 / self.r) if self.r > 0 else 0.0
+        xbf = dt in OP16 and FWD_STREAM != "f32"        # the residual stream in 2 bytes per element
+        xf16 = xbf and (FWD_STREAM == "f16" or dt == torch.float16)      # (fp16 operands: the 16-bit stream is fp16 too)
+        self.xdt = (torch.float16 if xf16 else torch.bfloat16) if xbf else torch.float32            # dtype of the residual stream
+        self.epi_res = _res_epilogue(self.xdt)
+        self.epi_patch = (L.EPI_PATCH_F16 if xf16 else L.EPI_PATCH_BF16) if xbf else L.EPI_PATCH
+
+
+def _cls_rows(c, t, w):
+    """Rows b*T of a [B*T, w] tensor."""
+    return t.view(c.B, c.T, w)[:, 0].contiguous()
+
+
+def _gp_rows(c, t, w):
+    """The cls rows of g'. (The 8-bit GELU' code tensor is slab-major [w/64][rows][64]: its cls rows, again slab-major for B rows.)"""
+    return t.view(w // 64, c.B, c.T, 64)[:, :, 0].contiguous().view(c.B, w) if t.dtype == torch.uint8 else _cls_rows(c, t, w)
+
+
 class ViTRunner:
     def __init__(self, model):
         self.model = model
@@ -234,13 +270,14 @@ class ViTRunner:
         return int(z & 0x7FFFFFFFFFF)      # 43 bits: (seed << 20) + call counter stays below 2^63
 
     # ------------------------------------------------------------------ caches
-    def _cached(self, cache, key, param, fn):
+    def _cached(self, cache, key, params, fn):
+        """fn(*params, detached), rebuilt when the (data_ptr, _version, device) of one of them changes. params: a tensor or a tuple of them."""
+        ps = params if isinstance(params, tuple) else (params,)
         ent = cache.get(key)
-        tag = (param.data_ptr(), param._version, param.device)
+        tag = tuple((p.data_ptr(), p._version, p.device) for p in ps)
         if ent is None or ent[0] != tag:
             with torch.no_grad():
-                ent = (tag, fn(param.detach()))
-            cache[key] = ent
+                ent = cache[key] = (tag, fn(*(p.detach() for p in ps)))
         return ent[1]
 
     def invalidate_operand_caches(self):
@@ -274,19 +311,13 @@ class ViTRunner:
         """Operands of a GEMM with a consumer-side LayerNorm in front (EPI_STORE_LN): W' = W * gamma along K in the operand format,
         c = rowsum(W') of the ROUNDED W' (so that the mean term cancels against what the matrix cores actually multiply), d = W beta (+ bias).
         Cached on the four parameters' versions (all frozen in GS-LoRA: built once)."""
-        key = (name, "ln", dtype)
-        ps = [weight, gamma, beta] + ([bias] if bias is not None else [])
-        tag = tuple((p.data_ptr(), p._version, p.device) for p in ps)
-        ent = self._wcache.get(key)
-        if ent is None or ent[0] != tag:
-            with torch.no_grad():
-                w32 = weight.detach().float()
-                wf = ops.cast((w32 * gamma.detach().float()[None, :]).contiguous(), dtype)
-                c = wf.float().sum(1).contiguous()
-                d = (w32 @ beta.detach().float()) + (bias.detach().float() if bias is not None else 0.0)
-                ent = (tag, (wf, c, d.contiguous()))
-            self._wcache[key] = ent
-        return ent[1]
+        def build(weight, gamma, beta, bias=None):
+            w32 = weight.float()
+            wf = ops.cast((w32 * gamma.float()[None, :]).contiguous(), dtype)
+            c = wf.float().sum(1).contiguous()
+            d = (w32 @ beta.float()) + (bias.float() if bias is not None else 0.0)
+            return wf, c, d.contiguous()
+        return self._cached(self._wcache, (name, "ln", dtype), (weight, gamma, beta) + (() if bias is None else (bias,)), build)
 
     def w_conv(self, name, param, dtype):
         """conv_proj weight [D, C, p, p] as the [D, p*p*C] operand matching gsl_patchify's (p1 p2 c) feature order."""
@@ -332,10 +363,8 @@ class ViTRunner:
             self._packs[key] = ent
             self._pack_tables.pop(dtype, None)
         if ent["version"] != param._version:
-            si, sj, pr, pc = ent["geom"]
             with torch.no_grad():
-                L.check(L.load().gsl_pack_pad(param.data_ptr(), si, sj, pr, pc, 1.0, ent["out"].data_ptr(), ent["out"].shape[0],
-                                              ent["out"].shape[1], ops.code(dtype), ops._stream()), "gsl_pack_pad")
+                ops.pack_pad(param, *ent["geom"], *ent["out"].shape, dtype, out=ent["out"])
             ent["version"] = param._version
         return ent["out"]
 
@@ -349,8 +378,7 @@ class ViTRunner:
         if ng * r > PADK:
             raise NotImplementedError("gs-lora_amd: 3 * lora_rank must not exceed 64 for --lora_pos Attention")
 
-        def build(_):
-            A, B = ml.lora_A.detach(), ml.lora_B.detach()
+        def build(A, B):
             inner = B.shape[0] // ng
             a_rows = torch.zeros(PADK, A.shape[1], device=A.device, dtype=torch.float32)
             a_rows[:ng * r] = A
@@ -359,14 +387,7 @@ class ViTRunner:
                 bblk[g * inner:(g + 1) * inner, g * r:(g + 1) * r] = B[g * inner:(g + 1) * inner]
             cast = (lambda t: t.contiguous()) if dtype == torch.float32 else (lambda t: ops.cast(t.contiguous(), dtype))
             return dict(A_rows=cast(a_rows), Bblk=cast(bblk), BblkT=cast(bblk.t()), AT=cast(a_rows.t()))
-        key = (f"qkvlora{i}", dtype)
-        ent = self._lcache.get(key)
-        tag = (ml.lora_A.data_ptr(), ml.lora_A._version, ml.lora_B._version, ml.lora_A.device)
-        if ent is None or ent[0] != tag:
-            with torch.no_grad():
-                ent = (tag, build(None))
-            self._lcache[key] = ent
-        return ent[1]
+        return self._cached(self._lcache, (f"qkvlora{i}", dtype), (ml.lora_A, ml.lora_B), build)
 
     def refresh_lora_packs(self, dtype):
         """One launch for every registered pack whose source changed (the optimizer touches all LoRA tensors each step)."""
@@ -434,6 +455,28 @@ class ViTRunner:
     def forward(self, img, label, save):
         """img: [B, C, H, W], or a tuple of such batches that are processed as ONE batch (gs_lora_step hands over the remain and the
         forget batch this way: each is patchified into its row range of the token matrix, no concatenated image copy is made)."""
+        c, parts, u8tab, label = self._fwd_prepare(img, label, save)
+        sp = c.sp
+        x = self._fwd_patch(c, parts, u8tab)
+        stash = []
+        for i, blk in enumerate(sp.blocks):
+            tail = TAIL_CLS and i == len(sp.blocks) - 1 and sp.pool == "cls"
+            xn, mean1, rstd1 = self._fwd_ln1(c, blk, x)
+            qkv, q_cls, uq, hm = self._fwd_qkv(c, i, blk, x, xn, mean1, rstd1, tail)
+            xn_keep = xn if (c.attn_site and save) else None
+            del xn
+            o, lse, x1 = self._fwd_attention(c, i, blk, x, qkv, q_cls, hm, tail)
+            x2, st = self._fwd_ffn(c, i, blk, x1)
+            if save:
+                st.update(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, qkv_hm=hm, o=o, lse=lse, x1=x1, xn=xn_keep, uq=uq, tail=tail, q_cls=q_cls)
+                stash.append(st)
+            x = x2
+        logits, emb, head = self._fwd_head(c, x, label)
+        return logits, emb, (dict(ctx=c, layers=stash, x_last=x, emb=emb, label=label, **head) if save else None)
+
+    def _fwd_prepare(self, img, label, save):
+        """Input validation, the uint8 / float decision with its value table, the dropout seed and the LoRA state of this pass.
+        -> (pass context, image batches, value table or None, label as the head wants it)"""
         m = self.model
         raw = list(img) if isinstance(img, (tuple, list)) else [img]
         # uint8 batches of a model that was told how to normalise them (set_input_norm) stay bytes up to the patch gather, which looks
@@ -451,176 +494,169 @@ class ViTRunner:
             raise ValueError("the batches of one forward must share the image shape")
         L.load()
         sp = m.hip_spec()
-        dt = m.compute_dtype
         u8tab = self.input_table(norm, img.shape[1], img.device) if u8 else None
-        linear_head = sp.head_kind in LINEAR_HEADS
         if sp.head_kind == "linear":
             label = None                       # modified_VIT.py:23-24: "label is not used in this model"
         elif label is not None:
             label = label.to(device=img.device, dtype=torch.int64).contiguous()
-        B = sum(t.shape[0] for t in parts)
-        T, D, H = sp.num_tokens, sp.dim, sp.heads
-        M = B * T
-        training = m.training
-        p_drop = sp.dropout_p if training else 0.0
-        p_emb = sp.emb_dropout_p if training else 0.0
         self.drop_calls += 1
         if self.seed_dev is not None:      # HIP-graph mode: the kernels read the seed from device memory; one captured increment per forward
             self.seed_dev.add_(1)
             seed, sflag = self.seed_dev.data_ptr(), L.SEED_ON_DEVICE
         else:
             seed, sflag = (self.drop_seed << 20) + self.drop_calls, 0
+        c = _Pass(sp, m.compute_dtype, sum(t.shape[0] for t in parts), img.device, m.training, seed, sflag, save)
         self.ensure_bucket(sp)
-        r = sp.lora_rank
-        attn_site = r > 0 and sp.lora_site == "attention"
-        if r > 0 and not attn_site:
-            self.refresh_lora_packs(dt)
-        s_lora = (1.0 / r) if r > 0 else 0.0
-        eps = sp.ln_eps
+        if c.r > 0 and not c.attn_site:
+            self.refresh_lora_packs(c.dt)
+        return c, parts, u8tab, label
 
+    def _fwd_patch(self, c, parts, u8tab):
+        """Patch stage: the patch gather (tiles, or ViTs_face's overlapping windows) and the embedding GEMM whose epilogue adds bias and
+        position, writes the cls rows and applies the embedding dropout. -> the residual stream x [M, D]"""
+        sp, dt, img = c.sp, c.dt, parts[0]
         if sp.patch_kernel:      # ViTs_face: overlapping zero-padded windows, K padded to a multiple of 64 (weight and patches alike)
             if sp.image_size is not None and tuple(img.shape[2:]) != (sp.image_size, sp.image_size):
-                raise ValueError(f"{type(m).__name__}: input images are {tuple(img.shape[2:])}, the model was built for "
+                raise ValueError(f"{type(self.model).__name__}: input images are {tuple(img.shape[2:])}, the model was built for "
                                  f"{sp.image_size} x {sp.image_size}")
             patches = ops.unfold_patches(parts, sp.patch_kernel, sp.patch_stride, sp.patch_pad, dt, table=u8tab)
-            if patches.shape[0] != B * T:
-                raise ValueError(f"{type(m).__name__}: the unfold yields {patches.shape[0] // B} tokens per image, the model has {T}")
+            if patches.shape[0] != c.M:
+                raise ValueError(f"{type(self.model).__name__}: the unfold yields {patches.shape[0] // c.B} tokens per image, the model has {c.T}")
             pw = self.w_kpad("pe", sp.patch_w, patches.shape[1], dt)
         else:
             patches = ops.patchify(parts, sp.patch_size, dt, table=u8tab)
             pw = self.w_conv("pe", sp.patch_w, dt) if sp.patch_is_conv else self.w("pe", sp.patch_w, dt)
-        xbf = dt in OP16 and FWD_STREAM != "f32"        # the residual stream in 2 bytes per element
-        xf16 = xbf and (FWD_STREAM == "f16" or dt == torch.float16)      # (fp16 operands: the 16-bit stream is fp16 too)
-        xdt = (torch.float16 if xf16 else torch.bfloat16) if xbf else torch.float32            # dtype of the residual stream
-        epi_res = (L.EPI_BIAS_RES_F16 if xf16 else L.EPI_BIAS_RES_BF16) if xbf else L.EPI_BIAS_RES_F32
-        x = torch.empty(M, D, device=img.device, dtype=xdt)
-        ops.gemm_nt(patches, pw, x, epilogue=(L.EPI_PATCH_F16 if xf16 else L.EPI_PATCH_BF16) if xbf else L.EPI_PATCH, bias=sp.patch_b.detach(),
-                    pos=sp.pos.detach()[0, :T].contiguous(), cls=sp.cls.detach().reshape(-1), T=T,
-                    p_drop=p_emb, seed=seed, site=SITE_EMB | sflag)
-        del patches
-        stash = []
-        for i, blk in enumerate(sp.blocks):
-            n1, n2 = blk.ln1, blk.ln2
-            attn_lora_live = attn_site and not blk.qkv_lora.merged      # the q / k / v adapters read LN1's output: no fold
-            fold = LN1_FOLD and dt in OP16 and x.dtype == dt and not attn_lora_live
-            if fold:
-                mean1, rstd1 = ops.layernorm_stats(x, D, M, D, n1.weight.detach(), n1.bias.detach(), eps, dt)
-                xn = None
-            else:
-                xn, mean1, rstd1 = ops.layernorm_fwd(x, D, M, D, n1.weight.detach(), n1.bias.detach(), eps, dt)
-            tail = TAIL_CLS and i == len(sp.blocks) - 1 and sp.pool == "cls"
-            qsplit = tail and QSPLIT and not attn_site
-            inner = H * 64
+        x = torch.empty(c.M, c.D, device=c.dev, dtype=c.xdt)
+        ops.gemm_nt(patches, pw, x, epilogue=c.epi_patch, bias=sp.patch_b.detach(), pos=sp.pos.detach()[0, :c.T].contiguous(),
+                    cls=sp.cls.detach().reshape(-1), T=c.T, p_drop=c.p_emb, seed=c.seed, site=SITE_EMB | c.sflag)
+        return x
+
+    def _fwd_ln1(self, c, blk, x):
+        """LayerNorm 1 -> (xn, mean, rstd); xn is None when the normalisation is folded into the QKV projection (LN1_FOLD)."""
+        n1 = blk.ln1
+        attn_lora_live = c.attn_site and not blk.qkv_lora.merged      # the q / k / v adapters read LN1's output: no fold
+        if LN1_FOLD and c.dt in OP16 and x.dtype == c.dt and not attn_lora_live:
+            return (None,) + ops.layernorm_stats(x, c.D, c.M, c.D, n1.weight.detach(), n1.bias.detach(), c.eps, c.dt)
+        return ops.layernorm_fwd(x, c.D, c.M, c.D, n1.weight.detach(), n1.bias.detach(), c.eps, c.dt)
+
+    def _fwd_qkv(self, c, i, blk, x, xn, mean1, rstd1, tail):
+        """QKV projection -> (qkv, q_cls, uq, layout). layout 0 / 1: qkv [M, 3*inner] token-major / head-major; layout 2 (cls-query last
+        block, QSPLIT): qkv is K | V [M, 2*inner] and q_cls [B, inner] the cls rows' Q. uq: the adapters' down-projection (attention site)."""
+        dt, B, T, D, M, inner = c.dt, c.B, c.T, c.D, c.M, c.H * 64
+        fold = xn is None
+        qsplit = tail and QSPLIT and not c.attn_site
+        qkv = torch.empty(M, (2 if qsplit else 3) * inner, device=c.dev, dtype=dt)
+        uq, lora = None, {}
+        if c.attn_site and not blk.qkv_lora.merged:      # q / k / v adapters: one block-diagonal LoRA K segment
+            qo = self.qkv_lora_ops(i, blk.qkv_lora, dt)
+            uq = torch.empty(M, PADK, device=c.dev, dtype=dt)
+            ops.gemm_nt(xn, qo["A_rows"], uq, alpha=c.s_lora)
+            lora = dict(A2=uq, W2=qo["Bblk"])
+        # operand, weight, bias and epilogue: the stream itself with W' = W * gamma, d = W beta (+ bias) and the row statistics finishing
+        # the normalisation in the epilogue (aux = rowsum(W')), or LayerNorm 1's output with the weight as it is
+        if fold:
+            a, (w, cw, b), ln = x, self.w_ln(f"qkv{i}", blk.qkv_w, blk.ln1.weight, blk.ln1.bias, blk.qkv_b, dt), dict(pos=mean1, cls=rstd1)
+        else:
+            a, w, cw, b, ln = xn, self.w(f"qkv{i}", blk.qkv_w, dt), None, (None if blk.qkv_b is None else blk.qkv_b.detach()), {}
+        if not qsplit:
             hm = 1 if (QKV_HEAD_MAJOR and dt in OP16) else 0
-            epi_qkv = L.EPI_STORE_QKV_HM if hm else L.EPI_STORE
-            uq = q_cls = None
-            if qsplit and fold:      # the same two GEMMs on the stream itself (W', c, d sliced like the weight; the cls rows' statistics gathered)
-                wf, cq, dq_ = self.w_ln(f"qkv{i}", blk.qkv_w, n1.weight, n1.bias, blk.qkv_b, dt)
-                qkv = torch.empty(M, 2 * inner, device=img.device, dtype=dt)
-                ops.gemm_nt(x, wf[inner:], qkv, epilogue=L.EPI_STORE_LN, pos=mean1, cls=rstd1, aux=cq[inner:], bias=dq_[inner:])
-                q_cls = torch.empty(B, inner, device=img.device, dtype=dt)
-                ops.gemm_nt(x.view(B, T * D)[:, :D], wf[:inner], q_cls, epilogue=L.EPI_STORE_LN, T=T, pos=mean1, cls=rstd1,      # (T: the cls rows' statistics, T apart)
-                            aux=cq[:inner], bias=dq_[:inner])
-                hm = 2
-            elif qsplit:      # K and V for every token, Q for the cls rows only (rows inner .. 3*inner of the fused weight are K | V)
-                wq = self.w(f"qkv{i}", blk.qkv_w, dt)
-                qb_ = None if blk.qkv_b is None else blk.qkv_b.detach()
-                qkv = torch.empty(M, 2 * inner, device=img.device, dtype=dt)
-                ops.gemm_nt(xn, wq[inner:], qkv, bias=None if qb_ is None else qb_[inner:])
-                q_cls = torch.empty(B, inner, device=img.device, dtype=dt)
-                ops.gemm_nt(xn.view(B, T * D)[:, :D], wq[:inner], q_cls, bias=None if qb_ is None else qb_[:inner].contiguous())      # A = the cls rows, T*D apart
-                hm = 2
-            elif attn_site and not blk.qkv_lora.merged:      # q / k / v adapters: one block-diagonal LoRA K segment
-                qkv = torch.empty(M, 3 * inner, device=img.device, dtype=dt)
-                qo = self.qkv_lora_ops(i, blk.qkv_lora, dt)
-                uq = torch.empty(M, PADK, device=img.device, dtype=dt)
-                ops.gemm_nt(xn, qo["A_rows"], uq, alpha=s_lora)
-                ops.gemm_nt(xn, self.w(f"qkv{i}", blk.qkv_w, dt), qkv, A2=uq, W2=qo["Bblk"], epilogue=epi_qkv, T=T,
-                            bias=None if blk.qkv_b is None else blk.qkv_b.detach())
-            elif fold:
-                wf, cq, dq_ = self.w_ln(f"qkv{i}", blk.qkv_w, n1.weight, n1.bias, blk.qkv_b, dt)
-                qkv = torch.empty(M, 3 * inner, device=img.device, dtype=dt)
-                ops.gemm_nt(x, wf, qkv, epilogue=L.EPI_STORE_QKV_HM_LN if hm else L.EPI_STORE_LN, T=T, pos=mean1, cls=rstd1, aux=cq, bias=dq_)
+            epi = (L.EPI_STORE_QKV_HM_LN if hm else L.EPI_STORE_LN) if fold else (L.EPI_STORE_QKV_HM if hm else L.EPI_STORE)
+            ops.gemm_nt(a, w, qkv, epilogue=epi, T=T, aux=cw, bias=b, **lora, **ln)
+            return qkv, None, uq, hm
+        # K and V for every token, Q for the cls rows only: rows inner .. 3*inner of the fused weight (and of W', c, d) are K | V
+        rows = lambda t, s: None if t is None else t[s]
+        kv, q = slice(inner, None), slice(None, inner)
+        epi = L.EPI_STORE_LN if fold else L.EPI_STORE
+        ops.gemm_nt(a, w[kv], qkv, epilogue=epi, aux=rows(cw, kv), bias=rows(b, kv), **ln)
+        q_cls = torch.empty(B, inner, device=c.dev, dtype=dt)
+        ops.gemm_nt(a.view(B, T * D)[:, :D], w[q], q_cls, epilogue=epi, T=T if fold else 0,      # A = the cls rows, T*D apart (T: their statistics, T apart)
+                    aux=rows(cw, q), bias=rows(b, q), **ln)
+        return qkv, q_cls, None, 2
+
+    def _fwd_attention(self, c, i, blk, x, qkv, q_cls, hm, tail):
+        """Attention and the out-projection with its residual: x1 = x + drop(Wo attn + bo). -> (o, lse, x1)"""
+        sp, B, T, D = c.sp, c.B, c.T, c.D
+        if tail:      # only the cls query of the last block is ever consumed: B rows from here on
+            o, lse = ops.attention_fwd_cls(qkv, B, T, c.H, sp.attn_scale, layout=hm, q_cls=q_cls)
+            xres = x.view(B, T, D)[:, 0].contiguous()
+        else:
+            o, lse = ops.attention_fwd(qkv, B, T, c.H, sp.attn_scale, layout=hm)
+            xres = x
+        x1 = torch.empty(xres.shape[0], D, device=c.dev, dtype=c.xdt)
+        ops.gemm_nt(o, self.w(f"wo{i}", blk.out.weight, c.dt), x1, epilogue=c.epi_res,
+                    bias=blk.out.bias.detach(), res=xres, p_drop=c.p_drop, seed=c.seed, site=(4 * i) | c.sflag)
+        return o, lse, x1
+
+    def _fwd_ffn(self, c, i, blk, x1):
+        """FFN sub-layer: x2 = x1 + drop(W2' drop(gelu(W1' LN2 x1))), W' = W + s B A while the FFN adapters are live.
+        -> (x2, this sub-layer's part of the block's stash or None)"""
+        dt, D, r, s_lora, dev, save = c.dt, c.D, c.r, c.s_lora, c.dev, c.save
+        p_drop, seed, sflag = c.p_drop, c.seed, c.sflag
+        n2, l1, l2 = blk.ln2, blk.l1, blk.l2
+        Mr, mlp = x1.shape[0], l1.weight.shape[0]
+        lora_on = r > 0 and not c.attn_site and not l1.merged
+        # bf16 stream: LayerNorm 2 also emits u1 = s * xn2 A1^T (the LoRA K segment of FFN1) instead of a skinny GEMM that re-reads xn2
+        ln_u1 = LN_LORA and lora_on and r <= 16 and D in (512, 768) and x1.dtype == torch.bfloat16 and dt == torch.bfloat16      # (bf16 operands + bf16 stream only)
+        if ln_u1:
+            xn2, mean2, rstd2, u1_ln = ops.layernorm_fwd_lora(x1, D, Mr, D, n2.weight.detach(), n2.bias.detach(), c.eps,
+                                                               self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), s_lora)
+        else:
+            xn2, mean2, rstd2 = ops.layernorm_fwd(x1, D, Mr, D, n2.weight.detach(), n2.bias.detach(), c.eps, dt)
+        if lora_on and (abs(l1.scaling * r - 1.0) > 1e-9 or abs(l2.scaling * r - 1.0) > 1e-9):
+            raise NotImplementedError("gs-lora_amd: the fused LoRA path uses scaling = 1 / r (lora_alpha = 1, the only value GS-LoRA "
+                                      f"passes); got scaling {l1.scaling} / {l2.scaling} for r = {r}")
+        u1 = u2 = u1c = None
+        h = torch.empty(Mr, mlp, device=dev, dtype=dt)
+        gp8 = GP8 and dt in OP16 and save and mlp % 64 == 0
+        epi_gelu = L.EPI_BIAS_GELU_G8 if gp8 else L.EPI_BIAS_GELU
+        gp = torch.empty(Mr, mlp, device=dev, dtype=torch.uint8 if gp8 else dt) if save else None
+        if lora_on:
+            if Mr < INK_MIN_ROWS and not ln_u1 and self.lora_in_kernel(dt, Mr, mlp):
+                # few rows: u1 = s * xn2 A1^T inside the FFN1 GEMM (64x64 ring kernel) instead of a skinny launch in front of it.
+                # (At full size the K-segment form below is as fast: the 8 N-tiles of a row panel would each recompute u1.)
+                u1 = torch.empty(Mr, PADK, device=dev, dtype=dt)
+                ops.gemm_nt_lora(xn2, self.w(f"w1_{i}", l1.weight, dt), self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows16", dt),
+                                 self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols32", dt), s_lora, u1, h, epilogue=epi_gelu,
+                                 bias=l1.bias.detach(), out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
             else:
-                qkv = torch.empty(M, 3 * inner, device=img.device, dtype=dt)
-                ops.gemm_nt(xn, self.w(f"qkv{i}", blk.qkv_w, dt), qkv, epilogue=epi_qkv, T=T,
-                            bias=None if blk.qkv_b is None else blk.qkv_b.detach())
-            xn_keep = xn if (attn_site and save) else None
-            del xn
-            if tail:      # only the cls query of the last block is ever consumed: B rows from here on
-                o, lse = ops.attention_fwd_cls(qkv, B, T, H, sp.attn_scale, layout=hm, q_cls=q_cls)
-                xres, Mr = x.view(B, T, D)[:, 0].contiguous(), B
-            else:
-                o, lse = ops.attention_fwd(qkv, B, T, H, sp.attn_scale, layout=hm)
-                xres, Mr = x, M
-            x1 = torch.empty(Mr, D, device=img.device, dtype=xdt)
-            ops.gemm_nt(o, self.w(f"wo{i}", blk.out.weight, dt), x1, epilogue=epi_res,
-                        bias=blk.out.bias.detach(), res=xres, p_drop=p_drop, seed=seed, site=(4 * i) | sflag)
-            del xres
-            l1, l2 = blk.l1, blk.l2
-            mlp = l1.weight.shape[0]
-            lora_on = r > 0 and not attn_site and not l1.merged
-            # bf16 stream: LayerNorm 2 also emits u1 = s * xn2 A1^T (the LoRA K segment of FFN1) instead of a skinny GEMM that re-reads xn2
-            ln_u1 = LN_LORA and lora_on and r <= 16 and D in (512, 768) and x1.dtype == torch.bfloat16 and dt == torch.bfloat16      # (bf16 operands + bf16 stream only)
-            if ln_u1:
-                xn2, mean2, rstd2, u1_ln = ops.layernorm_fwd_lora(x1, D, Mr, D, n2.weight.detach(), n2.bias.detach(), eps,
-                                                                   self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), s_lora)
-            else:
-                xn2, mean2, rstd2 = ops.layernorm_fwd(x1, D, Mr, D, n2.weight.detach(), n2.bias.detach(), eps, dt)
-            if lora_on and (abs(l1.scaling * r - 1.0) > 1e-9 or abs(l2.scaling * r - 1.0) > 1e-9):
-                raise NotImplementedError("gs-lora_amd: the fused LoRA path uses scaling = 1 / r (lora_alpha = 1, the only value GS-LoRA "
-                                          f"passes); got scaling {l1.scaling} / {l2.scaling} for r = {r}")
-            u1 = u2 = u1c = None
-            h = torch.empty(Mr, mlp, device=img.device, dtype=dt)
-            gp8 = GP8 and dt in OP16 and save and mlp % 64 == 0
-            epi_gelu = L.EPI_BIAS_GELU_G8 if gp8 else L.EPI_BIAS_GELU
-            gp = torch.empty(Mr, mlp, device=img.device, dtype=torch.uint8 if gp8 else dt) if save else None
-            if lora_on:
-                if Mr < INK_MIN_ROWS and not ln_u1 and self.lora_in_kernel(dt, Mr, mlp):
-                    # few rows: u1 = s * xn2 A1^T inside the FFN1 GEMM (64x64 ring kernel) instead of a skinny launch in front of it.
-                    # (At full size the K-segment form below is as fast: the 8 N-tiles of a row panel would each recompute u1.)
-                    u1 = torch.empty(Mr, PADK, device=img.device, dtype=dt)
-                    ops.gemm_nt_lora(xn2, self.w(f"w1_{i}", l1.weight, dt), self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows16", dt),
-                                     self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols32", dt), s_lora, u1, h, epilogue=epi_gelu,
-                                     bias=l1.bias.detach(), out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
+                if ln_u1:
+                    u1 = u1_ln
                 else:
-                    if ln_u1:
-                        u1 = u1_ln
-                    else:
-                        u1 = torch.empty(Mr, PADK, device=img.device, dtype=dt)
-                        # (16-bit modes: the GEMM also writes u1's first 16 columns as a compact [M, 16] tensor — the operand form the
-                        #  gradient-fused FFN2-dX epilogue reads 32 rows of with one contiguous 1 KB load; rank <= 16)
-                        u1c = torch.empty(Mr, 16, device=img.device, dtype=dt) if (save and dt in OP16 and r <= 16 and Mr >= INK_MIN_ROWS) else None
-                        ops.gemm_nt(xn2, self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), u1, alpha=s_lora, out2=u1c)
-                    ops.gemm_nt(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, A2=u1,
-                                W2=self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols", dt), bias=l1.bias.detach(), out2=gp,
-                                p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
-                u2 = torch.empty(Mr, PADK, device=img.device, dtype=dt)
-                if not self.lora_in_kernel(dt, Mr, D):
-                    ops.gemm_nt(h, self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows", dt), u2, alpha=s_lora)
-            else:
-                ops.gemm_nt(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, bias=l1.bias.detach(),
-                            out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag)
-            x2 = torch.empty(Mr, D, device=img.device, dtype=xdt)
-            if lora_on and self.lora_in_kernel(dt, Mr, D):
-                ops.gemm_nt_lora(h, self.w(f"w2_{i}", l2.weight, dt), self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows16", dt),
-                                 self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols32", dt), s_lora, u2, x2, epilogue=epi_res,
-                                 bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
-            else:
-                ops.gemm_nt(h, self.w(f"w2_{i}", l2.weight, dt), x2, epilogue=epi_res, A2=u2,
-                            W2=self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols", dt) if lora_on else None,
-                            bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
-            if save:
-                stash.append(dict(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, qkv_hm=hm, o=o, lse=lse, x1=x1, mean2=mean2, rstd2=rstd2,
-                                  xn2=xn2, u1=u1, u1c=u1c, h=h, gp=gp, u2=u2, lora_on=lora_on, xn=xn_keep, uq=uq, tail=tail, q_cls=q_cls))
-            x = x2
-        hn = sp.final_ln
+                    u1 = torch.empty(Mr, PADK, device=dev, dtype=dt)
+                    # (16-bit modes: the GEMM also writes u1's first 16 columns as a compact [M, 16] tensor — the operand form the
+                    #  gradient-fused FFN2-dX epilogue reads 32 rows of with one contiguous 1 KB load; rank <= 16)
+                    u1c = torch.empty(Mr, 16, device=dev, dtype=dt) if (save and dt in OP16 and r <= 16 and Mr >= INK_MIN_ROWS) else None
+                    ops.gemm_nt(xn2, self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), u1, alpha=s_lora, out2=u1c)
+                ops.gemm_nt(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, A2=u1,
+                            W2=self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols", dt), bias=l1.bias.detach(), out2=gp,
+                            p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
+            u2 = torch.empty(Mr, PADK, device=dev, dtype=dt)
+            if not self.lora_in_kernel(dt, Mr, D):
+                ops.gemm_nt(h, self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows", dt), u2, alpha=s_lora)
+        else:
+            ops.gemm_nt(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, bias=l1.bias.detach(),
+                        out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag)
+        x2 = torch.empty(Mr, D, device=dev, dtype=c.xdt)
+        if lora_on and self.lora_in_kernel(dt, Mr, D):
+            ops.gemm_nt_lora(h, self.w(f"w2_{i}", l2.weight, dt), self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows16", dt),
+                             self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols32", dt), s_lora, u2, x2, epilogue=c.epi_res,
+                             bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
+        else:
+            ops.gemm_nt(h, self.w(f"w2_{i}", l2.weight, dt), x2, epilogue=c.epi_res, A2=u2,
+                        W2=self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols", dt) if lora_on else None,
+                        bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
+        return x2, (dict(mean2=mean2, rstd2=rstd2, xn2=xn2, u1=u1, u1c=u1c, h=h, gp=gp, u2=u2, lora_on=lora_on) if save else None)
+
+    def _fwd_head(self, c, x, label):
+        """Final LayerNorm, pooling and the head of the model's kind. -> (logits, emb, what the head backward needs)"""
+        sp, B, D, hn = c.sp, c.B, c.D, c.sp.final_ln
         Th = x.shape[0] // B      # rows per image of the stream that reaches the head: T, or 1 after a cls-row-only last block
         cos_y = None
-        if linear_head:      # plain classifier, no normalisation, no margin: logits for every call (ModifiedViT) / with a label (Softmax)
+        ln = (x, B, Th, D, hn.weight.detach(), hn.bias.detach(), c.eps)
+        if sp.head_kind in LINEAR_HEADS:      # plain classifier, no normalisation, no margin: logits for every call (ModifiedViT) / with a label (Softmax)
             Wn = sp.head_w.detach().contiguous() if (sp.head_kind == "linear" or label is not None) else None
-            logits, emb, meanh, rstdh = ops.head_fwd(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, None, 1.0, 0.0,
-                                                     head_bias=sp.head_b.detach(), linear=Wn is not None, pool_mean=(sp.pool == "mean"))
+            logits, emb, meanh, rstdh = ops.head_fwd(*ln, Wn, None, 1.0, 0.0, head_bias=sp.head_b.detach(), linear=Wn is not None,
+                                                     pool_mean=(sp.pool == "mean"))
         else:
             if label is None:
                 Wn = None
@@ -629,195 +665,65 @@ class ViTRunner:
             else:      # frozen head (GS-LoRA trains the adapters only): the row-normalised weight is computed once per weight version
                 Wn = self._cached(self._wcache, ("cosface_wn",), sp.head_w, lambda p: ops.cosface_prep(p.contiguous()))
             if sp.head_kind == "arcface":      # cos_y: the label column's cosine before the margin, for the backward's branch
-                logits, emb, meanh, rstdh, cos_y = ops.head_fwd_margin(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, label,
-                                                                       sp.cos_s, 0.0, "arcface", m=sp.cos_m, easy_margin=sp.easy_margin,
-                                                                       pool_mean=(sp.pool == "mean"))
+                logits, emb, meanh, rstdh, cos_y = ops.head_fwd_margin(*ln, Wn, label, sp.cos_s, 0.0, "arcface", m=sp.cos_m,
+                                                                       easy_margin=sp.easy_margin, pool_mean=(sp.pool == "mean"))
             else:
-                logits, emb, meanh, rstdh = ops.head_fwd(x, B, Th, D, hn.weight.detach(), hn.bias.detach(), eps, Wn, label,
-                                                         sp.cos_s, sp.cos_m, pool_mean=(sp.pool == "mean"))
-        saved = None
-        if save:
-            saved = dict(layers=stash, x_last=x, Th=Th, meanh=meanh, rstdh=rstdh, emb=emb, Wn=Wn, B=B, seed=seed, sflag=sflag, p_drop=p_drop,
-                         dt=dt, spec=sp, cos_y=cos_y, label=label)
-        return logits, emb, saved
+                logits, emb, meanh, rstdh = ops.head_fwd(*ln, Wn, label, sp.cos_s, sp.cos_m, pool_mean=(sp.pool == "mean"))
+        return logits, emb, dict(Th=Th, meanh=meanh, rstdh=rstdh, Wn=Wn, cos_y=cos_y)
 
     # ------------------------------------------------------------------ backward
-    @staticmethod
-    def _head_bwd(saved, *args, **kw):
-        """ops.head_bwd, or its margin form for the ArcFace head (with the label column's cosine and the labels the forward saved)."""
-        sp = saved["spec"]
-        if sp.head_kind == "arcface":
-            return ops.head_bwd_margin(*args, head_kind="arcface", m=sp.cos_m, easy_margin=sp.easy_margin, cos_y=saved["cos_y"],
-                                       label=saved["label"], **kw)
-        return ops.head_bwd(*args, **kw)
-
     def backward(self, saved, dlogits, demb):
-        """Accumulates d(loss)/d(LoRA) into the flat gradient bucket (views are the params' .grad)."""
-        sp = saved["spec"]
-        bucket = self.bucket
+        """Accumulates d(loss)/d(LoRA) into the flat gradient bucket (views are the params' .grad). One chain for both LoRA sites: with
+        the adapters on the FFN it stops after the LoRA gradients of block 0's FFN; with the adapters on the QKV projection
+        (--lora_pos Attention; reference vit_face.py:349-355 with loralib.MergedLinear) the FFN is a plain frozen sub-layer (dX only),
+        every block's attention needs its dqkv, and the chain stops after the LoRA gradients of block 0's projection."""
+        c = saved["ctx"]
+        sp, bucket = c.sp, self.bucket
         if bucket is None:
             return
         bucket.attach_grads()
-        if sp.lora_site == "attention":
-            return self._backward_attention_site(saved, dlogits, demb)
-        dt = saved["dt"]
-        B, seed, p_drop, sflag = saved["B"], saved["seed"], saved["p_drop"], saved["sflag"]
-        T, D, H = sp.num_tokens, sp.dim, sp.heads
-        r = sp.lora_rank
-        s_lora = 1.0 / r
+        dx, dxb = self._bwd_head(c, saved, dlogits, demb)
+        c.gv = {id(p): g for p, g in zip(bucket.params, bucket.grad_views)}
+        c.pending = []      # deferred LoRA-gradient reductions (launch-bound regime): (Y, U, G, gsn, gsj, r, accumulate), operands kept alive
         nl = len(saved["layers"])
-        hn = sp.final_ln
-        linear_head = sp.head_kind in LINEAR_HEADS
-        if dlogits is not None:
-            dlogits = dlogits.contiguous().float()
-        if demb is not None:
-            demb = demb.contiguous().float()
-        if dlogits is not None and saved["Wn"] is None:
-            raise RuntimeError("backward through logits requires a forward with labels")
-        # fp16 operands: the backward runs on loss-scaled gradients — gsl_head_bwd picks the power of two S on the device and writes
-        # {S, 1/S} here; every LoRA-gradient reduction below multiplies by 1/S on the way out (bf16 / f32: no scaling)
-        gscale = self._loss_scale_state(saved["x_last"].device) if dt == torch.float16 else None
-        self._guard_on = gscale is not None
-        gmax = gscale[2:] if gscale is not None else None      # the overflow guard: raised by every LayerNorm backward below
-        dx, dxb = self._head_bwd(saved, dlogits, demb, saved["x_last"], B, saved["Th"], D, hn.weight.detach(), saved["meanh"], saved["rstdh"],
-                               saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=p_drop, seed=seed,
-                               site=(4 * (nl - 1) + 2) | sflag, linear=linear_head, pool_mean=(sp.pool == "mean"),
-                               stream_dtype=dt if (dt in OP16 and GRAD_STREAM_BF16) else torch.float32,
-                               compact=(sp.pool == "cls"), gscale=gscale, target_exp=GRAD_TARGET_EXP)      # pool='cls': [B, D] cls-row gradients, nothing zero-filled
-        blocks = sp.blocks
-        gv = {id(p): g for p, g in zip(bucket.params, bucket.grad_views)}
-        dev = dx.device
-        cls_rows = lambda t, w: t.view(B, T, w)[:, 0].contiguous()     # rows b*T of a [B*T, w] tensor
-        # (the 8-bit GELU' code tensor is slab-major [w/64][rows][64]: its cls rows, again slab-major for B rows)
-        gp_rows = lambda t, w: (t.view(w // 64, B, T, 64)[:, :, 0].contiguous().view(B, w) if t.dtype == torch.uint8 else cls_rows(t, w))
-        pending = []      # deferred LoRA-gradient reductions (launch-bound regime): (Y, U, G, gsn, gsj, r, accumulate), operands kept alive
-
-        def lgrad(Y, U, G, gsn, gsj, rr):
-            if Y.shape[0] < LGRAD_BATCH_MAX_ROWS and B * T < LGRAD_BATCH_MAX_ROWS and ops.lora_grad_batchable(Y, U, rr):
-                pending.append((Y, U, G, gsn, gsj, rr, True))
-            else:
-                ops.lora_grad(Y, U, G, gsn, gsj, rr, gscale=gscale)
-
-        def flush():
-            ops.lora_grad_batch(pending, gscale=gscale)
-            pending.clear()
-
         for i in reversed(range(nl)):
-            st = saved["layers"][i]
-            blk = blocks[i]
-            l1, l2 = blk.l1, blk.l2
-            mlp = l1.weight.shape[0]
-            if not st["lora_on"]:
-                raise RuntimeError("backward with merged LoRA weights is undefined (model.train() un-merges)")
+            st, blk = saved["layers"][i], sp.blocks[i]
             # The network pools x[:, 0] (vit_face.py:540): the stream gradient entering the LAST block is exactly zero
             # outside the B cls rows, so its FFN backward, LoRA-gradient reductions, LN2 backward, out-proj dX and the
             # attention backward (a rank-1 cls-query form) run on B rows instead of B*T. Exact, not an approximation.
             sparse = (i == nl - 1) and sp.pool == "cls"      # (with pool='mean' every token carries gradient: dense last block)
-            tail = st["tail"]      # the forward of this block already ran on the cls rows: every saved tensor behind the attention is [B, .]
-            if sparse and not tail:      # dx / dxb arrive compact ([B, D]) from the head backward
-                dyb, xn2, h, gp, u1, u2 = (dxb, cls_rows(st["xn2"], D), cls_rows(st["h"], mlp), gp_rows(st["gp"], mlp),
-                                           cls_rows(st["u1"], PADK), cls_rows(st["u2"], PADK))
-            else:
-                dyb, xn2, h, gp, u1, u2 = dxb, st["xn2"], st["h"], st["gp"], st["u1"], st["u2"]
-            u1c = None if (sparse and not tail) else st.get("u1c")      # the compact [M, 16] form of u1 (16-bit modes, full-size blocks)
-            Mrows = dyb.shape[0]
-            # ---- FFN sub-layer: y = x1 + drop(W2' h + b2), h = drop(gelu(W1' xn2 + b1)) -------------
-            ink = self.lora_in_kernel(dt, Mrows, mlp)       # FFN2-dX (N = mlp)
-            ink1 = self.lora_in_kernel(dt, Mrows, D)        # FFN1-dX (N = dim)
-            epi_mul = L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL      # g' as the 8-bit code of the forward (decode scale from p_drop)
-            v2 = torch.empty(Mrows, PADK, device=dev, dtype=dt)
-            da = torch.empty(Mrows, mlp, device=dev, dtype=dt)
-            fused_grads = ink and FUSE_LORA_GRAD and Mrows >= INK_MIN_ROWS      # the gradient-fused epilogue lives on the 8-phase kernel
-            if fused_grads:
-                # v2 = s*dy*B2 is produced inside the dX GEMM, and the two gradient reductions that contract over the rows of its
-                # [M, mlp] tiles (dB1 from the da it produces, dA2 from h and the v2 it holds) ride in its epilogue
-                ops.gemm_nt_lora_mulgrad(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
-                                         self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, gp,
-                                         (u1c if u1c is not None else u1), gv[id(l1.lora_B)], (r, 1), h, gv[id(l2.lora_A)], (1, mlp), r, tag="ffn2dx", p_drop=p_drop,
-                                         gscale=gscale)
-            elif ink:    # v2 = s*dy*B2 is produced inside the dX GEMM
-                ops.gemm_nt_lora(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
-                                 self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, epilogue=epi_mul, aux=gp, p_drop=p_drop)
-            else:
-                ops.gemm_nt(dyb, self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows", dt), v2, alpha=s_lora)
-                ops.gemm_nt(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=epi_mul, A2=v2,
-                            W2=self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols", dt), aux=gp, p_drop=p_drop)
-            lgrad(dyb, u2, gv[id(l2.lora_B)], r, 1, r)                        # dB2[c, j]
-            if not fused_grads:
-                lgrad(h, v2, gv[id(l2.lora_A)], 1, mlp, r)                    # dA2[j, hid]
-            v1 = torch.empty(Mrows, PADK, device=dev, dtype=dt)
-            dxn2 = None
-            if ink1 and i > 0:   # v1 = s*da*B1 is produced inside the FFN1-dX GEMM
-                dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
-                ops.gemm_nt_lora(da, self.wT(f"w1_{i}", l1.weight, dt), self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows16", dt),
-                                 self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols32", dt), s_lora, v1, dxn2)
-            else:
-                ops.gemm_nt(da, self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows", dt), v1, alpha=s_lora)
-            if not fused_grads:
-                lgrad(da, u1, gv[id(l1.lora_B)], r, 1, r)                     # dB1[hid, j]
-            lgrad(xn2, v1, gv[id(l1.lora_A)], 1, D, r)                        # dA1[j, c]
-            if self.grad_hook is not None:
-                flush()      # the hook hands finished gradient slices to the all-reduce
-                self.grad_hook(i)
-            if i == 0:
-                flush()
-                break   # nothing below the layer-0 FFN input is trainable
+            # tail: the forward of this block already ran on the cls rows, every saved tensor behind the attention is [B, .]; otherwise
+            # dx / dxb arrive compact ([B, D]) from the head backward and the cls rows of the dense saved tensors are gathered
+            gather = sparse and not st["tail"]
+            dxn2 = (self._bwd_ffn_frozen if c.attn_site else self._bwd_ffn_lora)(c, i, blk, st, dxb, gather)
             if dxn2 is None:
-                dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
-                ops.gemm_nt(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2, A2=v1,
-                            W2=self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols", dt))
-            del da, v1, v2
-            n2 = blk.ln2
-            if sparse and not tail:   # compact in, compact out: the cls rows of x1 are T*D apart, the dropout counters are those of the dense tensor
-                dx1, dx1b = ops.layernorm_bwd(dxn2, st["x1"], T * D, n2.weight.detach(), cls_rows(st["mean2"].view(-1, 1), 1).view(-1),
-                                              cls_rows(st["rstd2"].view(-1, 1), 1).view(-1), dx,
-                                              p_drop=p_drop, seed=seed, site=(4 * i) | sflag, drop_row_stride=T * D, gmax=gmax)
-            else:
-                dx1, dx1b = ops.layernorm_bwd(dxn2, st["x1"], D, n2.weight.detach(), st["mean2"], st["rstd2"], dx,
-                                              p_drop=p_drop, seed=seed, site=(4 * i) | sflag, gmax=gmax)
+                break   # FFN site: nothing below the layer-0 FFN input is trainable
+            dx1, dx1b = self._bwd_ln2(c, i, blk, st, dxn2, dx, gather)
             del dxn2
             # ---- attention sub-layer: x1 = x + drop(Wo o + bo) -------------------------------------
-            d_o = torch.empty(Mrows, H * 64, device=dev, dtype=dt)
-            ops.gemm_nt(dx1b, self.wT(f"wo{i}", blk.out.weight, dt), d_o)
-            dxn1 = torch.empty(B * T, D, device=dev, dtype=dt)
-            if sparse and st["q_cls"] is not None:      # Q was projected for the cls rows only: dX contracts over K | V, the cls rows get dQ W_q on top
-                inner = H * 64
-                dkv, dq_cls = ops.attention_bwd_cls(st["qkv"], st["o"], d_o, st["lse"], B, T, H, sp.attn_scale, layout=2, q_cls=st["q_cls"])
-                wt = self.wT(f"qkv{i}", blk.qkv_w, dt)                     # [dim, 3*inner]
-                ops.gemm_nt(dkv, wt[:, inner:], dxn1)
-                rows = dxn1.view(B, T * D)[:, :D]                          # the cls rows of dxn1, T*D apart: updated in place
-                ops.gemm_nt(dq_cls, wt[:, :inner], rows, epilogue={torch.bfloat16: L.EPI_BIAS_RES_BF16, torch.float16: L.EPI_BIAS_RES_F16}.get(dt, L.EPI_BIAS_RES_F32),
-                            bias=self._zeros(D, dev), res=rows)
-                del dkv, dq_cls
-            else:
-                if sparse:
-                    dqkv = ops.attention_bwd_cls(st["qkv"], st["o"], d_o, st["lse"], B, T, H, sp.attn_scale, layout=st["qkv_hm"])
-                else:
-                    dqkv = ops.attention_bwd(st["qkv"], st["o"], d_o, st["lse"], B, T, H, sp.attn_scale, layout=st["qkv_hm"])
-                ops.gemm_nt(dqkv, self.wT(f"qkv{i}", blk.qkv_w, dt), dxn1)
+            d_o = torch.empty(dx1b.shape[0], c.H * 64, device=c.dev, dtype=c.dt)
+            ops.gemm_nt(dx1b, self.wT(f"wo{i}", blk.out.weight, c.dt), d_o)
+            if c.attn_site:
+                dqkv = self._bwd_attention(c, st, d_o, sparse)
+                del d_o, dx1b
+                dxn1 = self._bwd_qkv_lora(c, i, blk, st, dqkv)
                 del dqkv
-            del d_o, dx1b
-            n1 = blk.ln1
-            dx, dxb = ops.layernorm_bwd(dxn1, st["x"], D, n1.weight.detach(), st["mean1"], st["rstd1"], dx1,
-                                        p_drop=p_drop, seed=seed, site=(4 * (i - 1) + 2) | sflag,
-                                        dres_cls_T=T if sparse else 0, gmax=gmax)      # after the cls-row-only block dx1 is compact [B, D]
+                if dxn1 is None:
+                    break      # attention site: nothing below the block-0 QKV projection is trainable
+            else:
+                dxn1 = self._bwd_qkv_frozen(c, i, blk, st, d_o, sparse)
+                del d_o, dx1b
+            dx, dxb = ops.layernorm_bwd(dxn1, st["x"], c.D, blk.ln1.weight.detach(), st["mean1"], st["rstd1"], dx1,
+                                        p_drop=c.p_drop, seed=c.seed, site=(4 * (i - 1) + 2) | c.sflag,
+                                        dres_cls_T=c.T if sparse else 0, gmax=c.gmax)      # after the cls-row-only block dx1 is compact [B, D]
             saved["layers"][i] = None   # free this layer's activations
-        if not torch.cuda.is_current_stream_capturing():
-            self.build_pack_tables(dt)    # every pack of the step is registered now: the next forward refreshes them in one launch
+        if not c.attn_site and not torch.cuda.is_current_stream_capturing():
+            self.build_pack_tables(c.dt)    # every pack of the step is registered now: the next forward refreshes them in one launch
 
-    def _backward_attention_site(self, saved, dlogits, demb):
-        """Backward when the adapters sit on the QKV projection (--lora_pos Attention; reference vit_face.py:349-355 with
-        loralib.MergedLinear): the FFN is a plain frozen sub-layer (dX only), every block's attention needs its dqkv, and the chain
-        stops after the LoRA gradients of block 0. Same kernels as the FFN-site path."""
-        sp, bucket = saved["spec"], self.bucket
-        dt = saved["dt"]
-        B, seed, p_drop, sflag = saved["B"], saved["seed"], saved["p_drop"], saved["sflag"]
-        T, D, H = sp.num_tokens, sp.dim, sp.heads
-        r = sp.lora_rank
-        s_lora = 1.0 / r
-        nl = len(saved["layers"])
-        hn = sp.final_ln
-        linear_head = sp.head_kind in LINEAR_HEADS
+    def _bwd_head(self, c, saved, dlogits, demb):
+        """Head backward with the loss-scale / overflow-guard state of the pass. -> (dx, dxb): the stream gradient entering the last block,
+        compact [B, D] cls rows under pool='cls' (nothing zero-filled)."""
+        sp, dt = c.sp, c.dt
         if dlogits is not None:
             dlogits = dlogits.contiguous().float()
         if demb is not None:
@@ -826,73 +732,156 @@ class ViTRunner:
             raise RuntimeError("backward through logits requires a forward with labels")
         # fp16 operands: the backward runs on loss-scaled gradients — gsl_head_bwd picks the power of two S on the device and writes
         # {S, 1/S} here; every LoRA-gradient reduction below multiplies by 1/S on the way out (bf16 / f32: no scaling)
-        gscale = self._loss_scale_state(saved["x_last"].device) if dt == torch.float16 else None
-        self._guard_on = gscale is not None
-        gmax = gscale[2:] if gscale is not None else None      # the overflow guard: raised by every LayerNorm backward below
-        dx, dxb = self._head_bwd(saved, dlogits, demb, saved["x_last"], B, saved["Th"], D, hn.weight.detach(), saved["meanh"], saved["rstdh"],
-                               saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=p_drop, seed=seed,
-                               site=(4 * (nl - 1) + 2) | sflag, linear=linear_head, pool_mean=(sp.pool == "mean"),
-                               stream_dtype=dt if (dt in OP16 and GRAD_STREAM_BF16) else torch.float32,
-                               compact=(sp.pool == "cls"), gscale=gscale, target_exp=GRAD_TARGET_EXP)      # pool='cls': [B, D] cls-row gradients, nothing zero-filled
-        gv = {id(p): g for p, g in zip(bucket.params, bucket.grad_views)}
-        dev = dx.device
-        cls_rows = lambda t, w: t.view(B, T, w)[:, 0].contiguous()
-        gp_rows = lambda t, w: (t.view(w // 64, B, T, 64)[:, :, 0].contiguous().view(B, w) if t.dtype == torch.uint8 else cls_rows(t, w))
-        for i in reversed(range(nl)):
-            st = saved["layers"][i]
-            blk = sp.blocks[i]
-            l1, l2, ml = blk.l1, blk.l2, blk.qkv_lora
-            if st["uq"] is None:
-                raise RuntimeError("backward with merged LoRA weights is undefined (model.train() un-merges)")
-            mlp = l1.weight.shape[0]
-            sparse = (i == nl - 1) and sp.pool == "cls"      # only the cls rows of the last block carry gradient (see the FFN-site path)
-            tail = st["tail"]
-            if sparse and not tail:
-                dyb, gp = dxb, gp_rows(st["gp"], mlp)
-            else:
-                dyb, gp = dxb, st["gp"]
-            Mrows = dyb.shape[0]
-            # ---- frozen FFN sub-layer: dX only
-            da = torch.empty(Mrows, mlp, device=dev, dtype=dt)
-            ops.gemm_nt(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
-                        p_drop=p_drop)
+        c.gscale = self._loss_scale_state(saved["x_last"].device) if dt == torch.float16 else None
+        self._guard_on = c.gscale is not None
+        c.gmax = c.gscale[2:] if c.gscale is not None else None      # the overflow guard: raised by every LayerNorm backward below
+        linear_head = sp.head_kind in LINEAR_HEADS
+        # ArcFace: the margin form, with the label column's cosine and the labels the forward saved
+        margin = {}
+        if sp.head_kind == "arcface":
+            margin = dict(head_kind="arcface", m=sp.cos_m, easy_margin=sp.easy_margin, cos_y=saved["cos_y"], label=saved["label"])
+        return (ops.head_bwd_margin if margin else ops.head_bwd)(
+            dlogits, demb, saved["x_last"], c.B, saved["Th"], c.D, sp.final_ln.weight.detach(), saved["meanh"], saved["rstdh"],
+            saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=c.p_drop, seed=c.seed,
+            site=(4 * (len(saved["layers"]) - 1) + 2) | c.sflag, linear=linear_head, pool_mean=(sp.pool == "mean"),
+            stream_dtype=dt if (dt in OP16 and GRAD_STREAM_BF16) else torch.float32,
+            compact=(sp.pool == "cls"), gscale=c.gscale, target_exp=GRAD_TARGET_EXP, **margin)
+
+    def _lgrad(self, c, Y, U, G, gsn, gsj, rr):
+        """One LoRA-gradient reduction: deferred to the batched launch pair of _flush where it fits, issued now otherwise."""
+        if Y.shape[0] < LGRAD_BATCH_MAX_ROWS and c.M < LGRAD_BATCH_MAX_ROWS and ops.lora_grad_batchable(Y, U, rr):
+            c.pending.append((Y, U, G, gsn, gsj, rr, True))
+        else:
+            ops.lora_grad(Y, U, G, gsn, gsj, rr, gscale=c.gscale)
+
+    def _flush(self, c):
+        ops.lora_grad_batch(c.pending, gscale=c.gscale)
+        c.pending.clear()
+
+    def _grads_done(self, c, i):
+        """The LoRA gradients of block i are complete: the hook hands finished gradient slices to the all-reduce."""
+        if self.grad_hook is not None:
+            self._flush(c)
+            self.grad_hook(i)
+
+    def _bwd_ffn_lora(self, c, i, blk, st, dyb, gather):
+        """FFN sub-layer with live adapters: y = x1 + drop(W2' h + b2), h = drop(gelu(W1' xn2 + b1)). The four LoRA gradients, then
+        -> dxn2 (None for block 0, where the chain ends)."""
+        dt, D, r, s_lora, dev, p_drop, gv = c.dt, c.D, c.r, c.s_lora, c.dev, c.p_drop, c.gv
+        l1, l2 = blk.l1, blk.l2
+        mlp = l1.weight.shape[0]
+        if not st["lora_on"]:
+            raise RuntimeError("backward with merged LoRA weights is undefined (model.train() un-merges)")
+        if gather:
+            xn2, h, gp, u1, u2 = (_cls_rows(c, st["xn2"], D), _cls_rows(c, st["h"], mlp), _gp_rows(c, st["gp"], mlp),
+                                  _cls_rows(c, st["u1"], PADK), _cls_rows(c, st["u2"], PADK))
+        else:
+            xn2, h, gp, u1, u2 = st["xn2"], st["h"], st["gp"], st["u1"], st["u2"]
+        u1c = None if gather else st.get("u1c")      # the compact [M, 16] form of u1 (16-bit modes, full-size blocks)
+        Mrows = dyb.shape[0]
+        ink = self.lora_in_kernel(dt, Mrows, mlp)       # FFN2-dX (N = mlp)
+        ink1 = self.lora_in_kernel(dt, Mrows, D)        # FFN1-dX (N = dim)
+        epi_mul = L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL      # g' as the 8-bit code of the forward (decode scale from p_drop)
+        v2 = torch.empty(Mrows, PADK, device=dev, dtype=dt)
+        da = torch.empty(Mrows, mlp, device=dev, dtype=dt)
+        fused_grads = ink and FUSE_LORA_GRAD and Mrows >= INK_MIN_ROWS      # the gradient-fused epilogue lives on the 8-phase kernel
+        if fused_grads:
+            # v2 = s*dy*B2 is produced inside the dX GEMM, and the two gradient reductions that contract over the rows of its
+            # [M, mlp] tiles (dB1 from the da it produces, dA2 from h and the v2 it holds) ride in its epilogue
+            ops.gemm_nt_lora_mulgrad(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
+                                     self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, gp,
+                                     (u1c if u1c is not None else u1), gv[id(l1.lora_B)], (r, 1), h, gv[id(l2.lora_A)], (1, mlp), r, tag="ffn2dx", p_drop=p_drop,
+                                     gscale=c.gscale)
+        elif ink:    # v2 = s*dy*B2 is produced inside the dX GEMM
+            ops.gemm_nt_lora(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
+                             self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, epilogue=epi_mul, aux=gp, p_drop=p_drop)
+        else:
+            ops.gemm_nt(dyb, self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows", dt), v2, alpha=s_lora)
+            ops.gemm_nt(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=epi_mul, A2=v2,
+                        W2=self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols", dt), aux=gp, p_drop=p_drop)
+        self._lgrad(c, dyb, u2, gv[id(l2.lora_B)], r, 1, r)                        # dB2[c, j]
+        if not fused_grads:
+            self._lgrad(c, h, v2, gv[id(l2.lora_A)], 1, mlp, r)                    # dA2[j, hid]
+        v1 = torch.empty(Mrows, PADK, device=dev, dtype=dt)
+        dxn2 = None
+        if ink1 and i > 0:   # v1 = s*da*B1 is produced inside the FFN1-dX GEMM
             dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
-            ops.gemm_nt(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
-            del da
-            n2 = blk.ln2
-            if sparse and not tail:
-                dx1, dx1b = ops.layernorm_bwd(dxn2, st["x1"], T * D, n2.weight.detach(), cls_rows(st["mean2"].view(-1, 1), 1).view(-1),
-                                              cls_rows(st["rstd2"].view(-1, 1), 1).view(-1), dx,
-                                              p_drop=p_drop, seed=seed, site=(4 * i) | sflag, drop_row_stride=T * D, gmax=gmax)
-            else:
-                dx1, dx1b = ops.layernorm_bwd(dxn2, st["x1"], D, n2.weight.detach(), st["mean2"], st["rstd2"], dx,
-                                              p_drop=p_drop, seed=seed, site=(4 * i) | sflag, gmax=gmax)
-            del dxn2
-            # ---- attention sub-layer with the q / k / v adapters
-            d_o = torch.empty(Mrows, H * 64, device=dev, dtype=dt)
-            ops.gemm_nt(dx1b, self.wT(f"wo{i}", blk.out.weight, dt), d_o)
-            if sparse:
-                dqkv = ops.attention_bwd_cls(st["qkv"], st["o"], d_o, st["lse"], B, T, H, sp.attn_scale, layout=st["qkv_hm"])
-            else:
-                dqkv = ops.attention_bwd(st["qkv"], st["o"], d_o, st["lse"], B, T, H, sp.attn_scale, layout=st["qkv_hm"])
-            del d_o, dx1b
-            qo = self.qkv_lora_ops(i, ml, dt)
-            v = torch.empty(B * T, PADK, device=dev, dtype=dt)
-            ops.gemm_nt(dqkv, qo["BblkT"], v, alpha=s_lora)                      # v[:, g*r+j] = s * dqkv_g . B_g[:, j]
-            ng, inner = len(ml.enable_lora), H * 64
-            gA, gB = gv[id(ml.lora_A)], gv[id(ml.lora_B)]
-            for g in range(ng):
-                ops.lora_grad(st["xn"], v[:, g * r:], gA[g * r:(g + 1) * r], 1, D, r, gscale=gscale)                       # dA_g[j, c]
-                ops.lora_grad(dqkv[:, g * inner:(g + 1) * inner], st["uq"][:, g * r:], gB[g * inner:(g + 1) * inner], r, 1, r, gscale=gscale)   # dB_g[n, j]
-            if self.grad_hook is not None:
-                self.grad_hook(i)
-            if i == 0:
-                break      # nothing below the block-0 QKV projection is trainable
-            dxn1 = torch.empty(B * T, D, device=dev, dtype=dt)
-            ops.gemm_nt(dqkv, self.wT(f"qkv{i}", blk.qkv_w, dt), dxn1, A2=v, W2=qo["AT"])
-            del dqkv, v
-            n1 = blk.ln1
-            dx, dxb = ops.layernorm_bwd(dxn1, st["x"], D, n1.weight.detach(), st["mean1"], st["rstd1"], dx1,
-                                        p_drop=p_drop, seed=seed, site=(4 * (i - 1) + 2) | sflag,
-                                        dres_cls_T=T if sparse else 0, gmax=gmax)      # after the cls-row-only block dx1 is compact [B, D]
-            saved["layers"][i] = None
+            ops.gemm_nt_lora(da, self.wT(f"w1_{i}", l1.weight, dt), self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows16", dt),
+                             self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols32", dt), s_lora, v1, dxn2)
+        else:
+            ops.gemm_nt(da, self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows", dt), v1, alpha=s_lora)
+        if not fused_grads:
+            self._lgrad(c, da, u1, gv[id(l1.lora_B)], r, 1, r)                     # dB1[hid, j]
+        self._lgrad(c, xn2, v1, gv[id(l1.lora_A)], 1, D, r)                        # dA1[j, c]
+        self._grads_done(c, i)
+        if i == 0:
+            self._flush(c)
+            return None
+        if dxn2 is None:
+            dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
+            ops.gemm_nt(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2, A2=v1,
+                        W2=self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols", dt))
+        return dxn2
+
+    def _bwd_ffn_frozen(self, c, i, blk, st, dyb, gather):
+        """FFN sub-layer without live adapters (attention site): dX only. -> dxn2"""
+        dt, l1, l2 = c.dt, blk.l1, blk.l2
+        if st["uq"] is None:
+            raise RuntimeError("backward with merged LoRA weights is undefined (model.train() un-merges)")
+        mlp = l1.weight.shape[0]
+        gp = _gp_rows(c, st["gp"], mlp) if gather else st["gp"]
+        da = torch.empty(dyb.shape[0], mlp, device=c.dev, dtype=dt)
+        ops.gemm_nt(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
+                    p_drop=c.p_drop)
+        dxn2 = torch.empty(dyb.shape[0], c.D, device=c.dev, dtype=dt)
+        ops.gemm_nt(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
+        return dxn2
+
+    def _bwd_ln2(self, c, i, blk, st, dxn2, dx, gather):
+        """LayerNorm 2 backward -> (dx1, dx1b): the stream gradient at x1 and its operand-format copy with the out-proj dropout mask."""
+        gamma, kw = blk.ln2.weight.detach(), dict(p_drop=c.p_drop, seed=c.seed, site=(4 * i) | c.sflag, gmax=c.gmax)
+        if gather:   # compact in, compact out: the cls rows of x1 are T*D apart, the dropout counters are those of the dense tensor
+            return ops.layernorm_bwd(dxn2, st["x1"], c.T * c.D, gamma, _cls_rows(c, st["mean2"].view(-1, 1), 1).view(-1),
+                                     _cls_rows(c, st["rstd2"].view(-1, 1), 1).view(-1), dx, drop_row_stride=c.T * c.D, **kw)
+        return ops.layernorm_bwd(dxn2, st["x1"], c.D, gamma, st["mean2"], st["rstd2"], dx, **kw)
+
+    def _bwd_attention(self, c, st, d_o, sparse):
+        """Attention backward -> dqkv [B*T, 3*inner], or (dkv [B*T, 2*inner], dq_cls [B, inner]) where the forward projected Q for the
+        cls rows only (layout 2). sparse: the cls-query form of the last block."""
+        if sparse:
+            return ops.attention_bwd_cls(st["qkv"], st["o"], d_o, st["lse"], c.B, c.T, c.H, c.sp.attn_scale, layout=st["qkv_hm"], q_cls=st["q_cls"])
+        return ops.attention_bwd(st["qkv"], st["o"], d_o, st["lse"], c.B, c.T, c.H, c.sp.attn_scale, layout=st["qkv_hm"])
+
+    def _bwd_qkv_frozen(self, c, i, blk, st, d_o, sparse):
+        """Attention backward and the dX of the frozen QKV projection (FFN site). -> dxn1"""
+        dt, D, inner = c.dt, c.D, c.H * 64
+        dxn1 = torch.empty(c.M, D, device=c.dev, dtype=dt)
+        dqkv = self._bwd_attention(c, st, d_o, sparse)
+        wt = self.wT(f"qkv{i}", blk.qkv_w, dt)                         # [dim, 3*inner]
+        if st["q_cls"] is None:
+            ops.gemm_nt(dqkv, wt, dxn1)
+        else:      # Q was projected for the cls rows only: dX contracts over K | V, the cls rows get dQ W_q on top
+            dkv, dq_cls = dqkv
+            ops.gemm_nt(dkv, wt[:, inner:], dxn1)
+            rows = dxn1.view(c.B, c.T * D)[:, :D]                      # the cls rows of dxn1, T*D apart: updated in place
+            ops.gemm_nt(dq_cls, wt[:, :inner], rows, epilogue=_res_epilogue(dt), bias=self._zeros(D, c.dev), res=rows)
+        return dxn1
+
+    def _bwd_qkv_lora(self, c, i, blk, st, dqkv):
+        """QKV projection with the q / k / v adapters (attention site): their gradients, then -> dxn1 with the adapter segment (None for
+        block 0, where the chain ends). Same kernels as the FFN-site path."""
+        dt, D, r, ml = c.dt, c.D, c.r, blk.qkv_lora
+        qo = self.qkv_lora_ops(i, ml, dt)
+        v = torch.empty(c.M, PADK, device=c.dev, dtype=dt)
+        ops.gemm_nt(dqkv, qo["BblkT"], v, alpha=c.s_lora)                      # v[:, g*r+j] = s * dqkv_g . B_g[:, j]
+        ng, inner = len(ml.enable_lora), c.H * 64
+        gA, gB = c.gv[id(ml.lora_A)], c.gv[id(ml.lora_B)]
+        for g in range(ng):
+            ops.lora_grad(st["xn"], v[:, g * r:], gA[g * r:(g + 1) * r], 1, D, r, gscale=c.gscale)                       # dA_g[j, c]
+            ops.lora_grad(dqkv[:, g * inner:(g + 1) * inner], st["uq"][:, g * r:], gB[g * inner:(g + 1) * inner], r, 1, r, gscale=c.gscale)   # dB_g[n, j]
+        self._grads_done(c, i)
+        if i == 0:
+            return None
+        dxn1 = torch.empty(c.M, D, device=c.dev, dtype=dt)
+        ops.gemm_nt(dqkv, self.wT(f"qkv{i}", blk.qkv_w, dt), dxn1, A2=v, W2=qo["AT"])
+        return dxn1
