@@ -4,7 +4,7 @@
 //       ArcFace departs from the reference in one place: sine = sqrt(max(1 - cos^2, 0)) and its derivative divides by max(sine, 1e-6),
 //       where the reference's sqrt returns NaN at |cos| > 1 (rounding) and an infinite gradient at |cos| = 1.
 //   K11 mean cross-entropy + top-1 (engine_cl.py:65-78, util/utils.py:354-368) fwd / bwd
-//   K13 prototype KL (engine_cl.py:571-603) fwd / bwd
+//   K13 prototype KL (engine_cl.py:571-603) fwd / bwd; K13b prototype l2 (engine_cl.py:593-594) fwd / bwd; K11b precision@k
 // All are tiny next to the GEMMs; they exist so that a step needs no host sync and no [B,C]-sized
 // PyTorch elementwise chain. Upstream gradient scalars arrive as DEVICE pointers (coef).
 #include <cmath>
@@ -932,6 +932,108 @@ extern "C" int gsl_proto_kl_bwd(const float* emb, const int64_t* labels, const f
   return check_launch("gsl_proto_kl_bwd");
 }
 
+// ------------------------------------------------------------------ K13b prototype l2 (engine_cl.py:593-594, engine.py:712-713)
+// torch.mean((output - prototype_tensor) ** 2) in the SUM form of the KL pair above: row i holds (1/D) sum_d (emb - proto[y_i])^2, the
+// entry point their sum; divided by the row count it is the reference's mean. One wave per row, lane-strided, explicit fmaf so that the
+// one-launch loss tail (loss_tail_kernel<true>) repeats the row value bit for bit.
+__device__ __forceinline__ float l2_grad_scale(int D) { return 2.0f / (float)D; }
+
+__global__ __launch_bounds__(256) void proto_l2_rows_kernel(const float* __restrict__ emb, const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ proto, float* __restrict__ rows, int B, int D, int C) {
+  fp16_sat_on();
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const float* a = emb + (size_t)r * D;
+  const long y = (long)labels[r];
+  if (y < 0 || y >= C) { if (lane == 0) rows[r] = __int_as_float(0x7fc00000); return; }      // see proto_kl_rows_kernel
+  const float* t = proto + (size_t)y * D;
+  float acc = 0.f;
+  for (int d = lane; d < D; d += 64) {
+    const float df = a[d] - t[d];
+    acc = fmaf(df, df, acc);
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) rows[r] = acc / (float)D;
+}
+extern "C" int gsl_proto_l2_fwd(const float* emb, const int64_t* labels, const float* proto, float* out1, float* row_ws, int B,
+                                int D, int C, gsl_stream_t s) {
+  GSL_CHECK_ARG(emb && labels && proto && out1 && row_ws && B > 0 && D > 0 && C > 0, "null/size");
+  hipLaunchKernelGGL(proto_l2_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(s), emb, labels, proto, row_ws, B, D, C);
+  hipLaunchKernelGGL(sum_rows_kernel, dim3(1), dim3(256), 0, as_stream(s), row_ws, out1, B, 1);
+  return check_launch("gsl_proto_l2_fwd");
+}
+
+__global__ __launch_bounds__(256) void proto_l2_bwd_kernel(const float* __restrict__ emb, const int64_t* __restrict__ labels,
+                                                           const float* __restrict__ proto, const float* __restrict__ coef,
+                                                           float scale, float* demb, int B, int D, int C, int accumulate) {
+  fp16_sat_on();
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const float* a = emb + (size_t)r * D;
+  const long y = (long)labels[r];
+  if (y < 0 || y >= C) {       // see proto_kl_rows_kernel
+    for (int d = lane; d < D; d += 64) demb[(size_t)r * D + d] = __int_as_float(0x7fc00000);
+    return;
+  }
+  const float* t = proto + (size_t)y * D;
+  const float k = coef[0] * scale;
+  const float s2 = l2_grad_scale(D);
+  for (int d = lane; d < D; d += 64) {
+    const float g = k * (s2 * (a[d] - t[d]));
+    float* o = demb + (size_t)r * D + d;
+    *o = accumulate ? (*o + g) : g;
+  }
+}
+extern "C" int gsl_proto_l2_bwd(const float* emb, const int64_t* labels, const float* proto, const float* coef, float scale,
+                                float* demb, int B, int D, int C, int accumulate, gsl_stream_t s) {
+  GSL_CHECK_ARG(emb && labels && proto && coef && demb && B > 0 && D > 0 && C > 0, "null/size");
+  hipLaunchKernelGGL(proto_l2_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(s), emb, labels, proto, coef, scale, demb, B, D, C, accumulate);
+  return check_launch("gsl_proto_l2_bwd");
+}
+
+// ------------------------------------------------------------------ K11b precision@k for several k (util/utils.py:354-368)
+// One launch: a wave per row counts the logits strictly greater than the label's logit; the row is a top-k hit when that count is below
+// k (= the label is among output.topk(k) wherever the k-th place is not tied). Hits are integers: per-block LDS counters, then one
+// integer atomic per k and block, so the result does not depend on the order of the blocks.
+constexpr int TOPK_MAX_K = 16;
+struct TopkKs { int k[TOPK_MAX_K]; };
+__global__ __launch_bounds__(256) void topk_hits_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int B, int C,
+                                                        TopkKs ks, int nk, int* __restrict__ hits) {
+  __shared__ int h_s[TOPK_MAX_K];
+  if (threadIdx.x < TOPK_MAX_K) h_s[threadIdx.x] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r < B) {
+    const long yl = (long)labels[r];
+    if (yl >= 0 && yl < C) {      // an out-of-range label is never a hit (no out-of-bounds read), as in ce_rows_kernel
+      const float* row = logits + (size_t)r * C;
+      const float yv = row[yl];
+      int cnt = 0;
+      for (int c = lane; c < C; c += 64) cnt += row[c] > yv ? 1 : 0;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      if (lane < nk && cnt < ks.k[lane]) atomicAdd(&h_s[lane], 1);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < nk && h_s[threadIdx.x] > 0) atomicAdd(hits + threadIdx.x, h_s[threadIdx.x]);
+}
+extern "C" int gsl_topk_max_k(void) { return TOPK_MAX_K; }
+extern "C" int gsl_topk_hits(const float* logits, const int64_t* labels, int B, int C, const int* ks_host, int nk, int* hits, gsl_stream_t s) {
+  GSL_CHECK_ARG(logits && labels && ks_host && hits && B > 0 && C > 0 && nk > 0 && nk <= TOPK_MAX_K, "null/size (1 <= nk <= 16 values of k)");
+  TopkKs ks = {};
+  for (int i = 0; i < nk; ++i) {
+    GSL_CHECK_ARG(ks_host[i] > 0, "k > 0");
+    ks.k[i] = ks_host[i];
+  }
+  if (hipMemsetAsync(hits, 0, sizeof(int) * (size_t)nk, as_stream(s)) != hipSuccess) return check_launch("gsl_topk_hits (clearing the counters)");
+  hipLaunchKernelGGL(topk_hits_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(s), logits, labels, B, C, ks, nk, hits);
+  return check_launch("gsl_topk_hits");
+}
+
 // =====================================================================================
 // The scalar tail of the step (engine_cl.py:65-125): total = beta*relu(BND - CE_f) + CE_r + alpha*L_s + w_f*relu(BND_pro - KL_f)
 // + w_r*KL_r from the SUMS produced by the kernels above, the 8 meter values, and the 5 partial derivatives the backward hands
@@ -1032,6 +1134,9 @@ __device__ __forceinline__ float lt_lse(const float v[LT_V], int n, int lane) { 
   for (int i = 0; i < LT_V; ++i) if (lane + 64 * i < n) se += expf(v[i] - m);
   return m + logf(wave_sum(se));
 }
+// L2: the prototype term is the l2 distance (proto_l2_rows_kernel / proto_l2_bwd_kernel) instead of the KL (gsl_loss_tail_l2); the
+// instantiation with L2 = false is the kernel gsl_loss_tail has always launched
+template <bool L2>
 __global__ __launch_bounds__(1024) void loss_tail_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int N, int nr,
                                                          int C, const float* __restrict__ emb, const float* __restrict__ proto, int D,
                                                          int Cp, const float* structure, float beta, float BND, float alpha, float w_f,
@@ -1068,6 +1173,17 @@ __global__ __launch_bounds__(1024) void loss_tail_kernel(const float* __restrict
       float a[LT_V], t[LT_V];
       lt_load(emb + (size_t)r * D, D, lane, a);
       lt_load(proto + (size_t)yl * D, D, lane, t);
+      if constexpr (L2) {
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < LT_V; ++i) if (lane + 64 * i < D) {
+          const float df = a[i] - t[i];
+          acc = fmaf(df, df, acc);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) kl_s[r] = acc / (float)D;
+        continue;
+      }
       const float la = lt_lse(a, D, lane), lt = lt_lse(t, D, lane);
       float acc = 0.f;
 #pragma unroll
@@ -1130,8 +1246,14 @@ __global__ __launch_bounds__(1024) void loss_tail_kernel(const float* __restrict
       float a[LT_V], t[LT_V];
       lt_load(emb + (size_t)r * D, D, lane, a);
       lt_load(proto + (size_t)yl * D, D, lane, t);
-      const float la = la_s[r], lt = lt_s[r];
       const float kk = coef_s[r < nr ? 3 : 2] * 1.0f;
+      if constexpr (L2) {
+        const float s2 = l2_grad_scale(D);
+#pragma unroll
+        for (int i = 0; i < LT_V; ++i) { const int d = lane + 64 * i; if (d < D) demb[(size_t)r * D + d] = kk * (s2 * (a[i] - t[i])); }
+        continue;
+      }
+      const float la = la_s[r], lt = lt_s[r];
 #pragma unroll
       for (int i = 0; i < LT_V; ++i) { const int d = lane + 64 * i; if (d < D) demb[(size_t)r * D + d] = kk * (expf(a[i] - la) - expf(t[i] - lt)); }
     }
@@ -1144,7 +1266,18 @@ extern "C" int gsl_loss_tail(const float* logits, const int64_t* labels, int N, 
   GSL_CHECK_ARG(logits && labels && out14 && dlogits && N > 0 && N <= LT_MAX && nr > 0 && nr < N && C > 0 && C <= 64 * LT_V && D <= 64 * LT_V,
                 "null/size (0 < nr < N <= 256 rows, C and D <= 1024)");
   GSL_CHECK_ARG(!emb || (proto && demb && D > 0 && Cp > 0), "prototype term: emb, proto and demb together");
-  hipLaunchKernelGGL(loss_tail_kernel, dim3(1), dim3(1024), 0, as_stream(s), logits, labels, N, nr, C, emb, proto, D, Cp, structure, beta, BND,
+  hipLaunchKernelGGL(loss_tail_kernel<false>, dim3(1), dim3(1024), 0, as_stream(s), logits, labels, N, nr, C, emb, proto, D, Cp, structure, beta, BND,
                      alpha, w_f, w_r, BND_pro, out14, dlogits, demb);
   return check_launch("gsl_loss_tail");
+}
+// gsl_loss_tail with the l2 prototype distance (engine_cl.py:593-594); the prototype term is required here (without one, gsl_loss_tail)
+extern "C" int gsl_loss_tail_l2(const float* logits, const int64_t* labels, int N, int nr, int C, const float* emb, const float* proto, int D,
+                                int Cp, const float* structure, float beta, float BND, float alpha, float w_f, float w_r, float BND_pro,
+                                float* out14, float* dlogits, float* demb, gsl_stream_t s) {
+  GSL_CHECK_ARG(logits && labels && out14 && dlogits && N > 0 && N <= LT_MAX && nr > 0 && nr < N && C > 0 && C <= 64 * LT_V && D <= 64 * LT_V,
+                "null/size (0 < nr < N <= 256 rows, C and D <= 1024)");
+  GSL_CHECK_ARG(emb && proto && demb && D > 0 && Cp > 0, "prototype term: emb, proto and demb are required");
+  hipLaunchKernelGGL(loss_tail_kernel<true>, dim3(1), dim3(1024), 0, as_stream(s), logits, labels, N, nr, C, emb, proto, D, Cp, structure, beta, BND,
+                     alpha, w_f, w_r, BND_pro, out14, dlogits, demb);
+  return check_launch("gsl_loss_tail_l2");
 }

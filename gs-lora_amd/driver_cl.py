@@ -74,6 +74,8 @@ def get_args(argv=None):
     p.add_argument("--pro_f_weight", type=float, default=0.01)
     p.add_argument("--cl_prof_list", nargs="*", default=[], type=float, help="per-task pro_f_weight (util/args.py:347; :1001-1002)")
     p.add_argument("--pro_r_weight", type=float, default=0.01)
+    p.add_argument("--pro_distance", default="kl", choices=["kl", "l2"],
+                   help="distance of the prototype term (get_prototype_loss, engine_cl.py:571-603): kl | l2")
     p.add_argument("--lora_rank", type=int, default=8)
     p.add_argument("--dropout", type=float, default=0.1)
     p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 (16-bit MFMA operands) | fp32 (parity mode)")
@@ -155,7 +157,8 @@ def run_tasks(model, args, task_data, dev, out, depth, cfg=None, after_reinit=No
     after_reinit(model, task_i): hook behind reinitialize_lora_parameters (tests install seeded adapter matrices: kaiming_uniform_ draws
     from the device RNG). after_task(task_i, model, ema_model, record): hook behind the task's checkpoint (model in train mode)."""
     os.makedirs(os.path.join(out, "task-level"), exist_ok=True)
-    cfg = cfg or {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": "VIT"}
+    cfg = cfg or {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": "VIT",
+                  "PROTO_DISTANCE": getattr(args, "pro_distance", "kl")}
     ema_model = None
     if args.average_weight:                                   # :502-507: a deep copy taken in eval() — its adapters are flagged MERGED
         model.eval()
@@ -276,7 +279,8 @@ def main(argv=None):
             print(f"[task {task_i}] verification on {args.verify_pairs} pairs: accuracy {acc:.4f} +- {std:.4f}, xnorm {xnorm:.3f}, "
                   f"best threshold {thr:.3f}")
 
-    cfg = {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net}
+    cfg = {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net,
+           "PROTO_DISTANCE": args.pro_distance}
     report, ema_model = run_tasks(model, args, task_data, dev, out, geo["depth"], cfg=cfg, after_task=after_task)
     return report, out, (model if ema_model is None else (model, ema_model))
 

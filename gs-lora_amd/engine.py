@@ -37,6 +37,7 @@ def train_one_epoch(model: torch.nn.Module, dataloader_forget, dataloader_remain
                   losses_prototype_forget=losses_prototype_forget, losses_prototype_remain=losses_prototype_remain)
     queue = MeterQueue()
     proto_table = _losses.prototype_table(prototype_dict, device) if use_prototype else None
+    proto_distance = _losses.check_proto_distance(cfg.get("PROTO_DISTANCE", "kl"))      # "kl" | "l2" (get_prototype_loss :690-722)
     use_structure = not (epoch < cfg.get("ALPHA_EPOCH", 0))
     group_type = cfg.get("GROUP_TYPE", "block")
     _check_group_pos(model, cfg.get("GROUP_POS", "FFN"))
@@ -51,7 +52,7 @@ def train_one_epoch(model: torch.nn.Module, dataloader_forget, dataloader_remain
         stepper = pick_stepper(model, optimizer, criterion, cfg, x_r.size(0) + x_f.size(0))    # HIP graph for launch-bound batches
         pack = stepper(x_r, y_r, x_f, y_f, beta=beta, alpha=alpha, BND=BND, use_structure=use_structure, group_type=group_type,
                        use_prototype=use_prototype, proto_table=proto_table, w_f=prototype_weight_forget,
-                       w_r=prototype_weight_remain, BND_pro=PROTO_BND)
+                       w_r=prototype_weight_remain, BND_pro=PROTO_BND, proto_distance=proto_distance)
         queue.push(pack, x_r.size(0), x_f.size(0))
         if ((batch + 1) % DISP_FREQ == 0) and batch != 0:
             queue.flush(meters)

@@ -51,6 +51,7 @@ def train_one_epoch(model: torch.nn.Module, dataloader_forget, dataloader_remain
                   losses_prototype_forget=losses_prototype_forget, losses_prototype_remain=losses_prototype_remain)
     queue = MeterQueue()
     proto_table = _losses.prototype_table(prototype_dict, device) if use_prototype else None
+    proto_distance = _losses.check_proto_distance(cfg.get("PROTO_DISTANCE", "kl"))      # "kl" | "l2" (get_prototype_loss :571-603)
     # cfg["DATA_ROOT"] == "./data/imagenet100/" selects the 12 ViT-B/16 block groups in the reference (:84); here the
     # groups come from the model's own LoRA bucket (6 for ViT_face, 12 for ModifiedViT), so no switch is needed.
     forget_iter = data_prefetcher(dataloader_forget, device, prefetch=True)
@@ -61,7 +62,7 @@ def train_one_epoch(model: torch.nn.Module, dataloader_forget, dataloader_remain
         stepper = pick_stepper(model, optimizer, criterion, cfg, x_r.size(0) + x_f.size(0))
         pack = stepper(x_r, y_r, x_f, y_f, beta=beta, alpha=alpha, BND=BND, use_structure=True, group_type="block",
                        use_prototype=use_prototype, proto_table=proto_table, w_f=prototype_weight_forget,
-                       w_r=prototype_weight_remain, BND_pro=cfg.get("BND_pro", 0.0))
+                       w_r=prototype_weight_remain, BND_pro=cfg.get("BND_pro", 0.0), proto_distance=proto_distance)
         queue.push(pack, x_r.size(0), x_f.size(0))
 
         if ((batch + 1) % DISP_FREQ == 0) and batch != 0:
@@ -220,11 +221,13 @@ def get_structure_loss(model: torch.nn.Module, imagenet=False):
 
 
 def get_prototype_loss(output, labels, prototype_dict, distance="kl"):
-    """KL(softmax(prototype[label]) || softmax(feature)), batchmean (reference :571-603)."""
-    if distance != "kl":
-        raise NotImplementedError("gs-lora_amd implements the 'kl' prototype distance the engines use")
+    """distance="kl": KL(softmax(prototype[label]) || softmax(feature)), batchmean; distance="l2": mean((feature - prototype[label])^2)
+    (reference :571-603). Differentiable with respect to `output`. Any other string returns the reference's initial value 0.0 (:586, :603)."""
+    if distance not in _losses.PROTO_DISTANCES:
+        return 0.0
     table = _losses.prototype_table(prototype_dict, output.device)
-    return _losses.proto_kl_sum(output, labels, table) / output.shape[0]
+    proto_sum = _losses.proto_l2_sum if distance == "l2" else _losses.proto_kl_sum
+    return proto_sum(output, labels, table) / output.shape[0]
 
 
 def get_reg_loss(*args, **kwargs):

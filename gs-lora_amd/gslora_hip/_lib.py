@@ -66,6 +66,11 @@ SIGNATURES = {
     "gsl_loss_tail_max_rows": [],
     "gsl_loss_tail": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp],
     "gsl_proto_kl_bwd": [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
+    "gsl_proto_l2_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "gsl_proto_l2_bwd": [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
+    "gsl_loss_tail_l2": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp],
+    "gsl_topk_max_k": [],
+    "gsl_topk_hits": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp],
     "gsl_group_norms_fwd": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gsl_group_norms_bwd": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp],
     "gsl_adamw_flat": [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp, _vp],

@@ -2,6 +2,7 @@
 
   ce_sum_top1      — nn.CrossEntropyLoss (sum form) + top-1 count     (engine_cl.py:65-78)
   proto_kl_sum     — get_prototype_loss 'kl' (sum form)                (engine_cl.py:571-603)
+  proto_l2_sum     — get_prototype_loss 'l2' (sum of the row means)    (engine_cl.py:593-594)
   structure_loss   — group-lasso over LoRA groups                      (engine_cl.py:349-432)
 Upstream gradients arrive as 0-dim device tensors and are handed to the kernels as device
 pointers, so the whole loss graph runs without a host sync.
@@ -112,6 +113,63 @@ class _ProtoKLSum(torch.autograd.Function):
 
 def proto_kl_sum(emb, labels, table):
     return _ProtoKLSum.apply(emb, labels, table)
+
+
+class _ProtoL2SumSplit(torch.autograd.Function):
+    """proto_l2_sum of rows [nr, N) (forget) and rows [0, nr) (remain) of one embedding tensor; one demb buffer in backward."""
+
+    @staticmethod
+    def forward(ctx, emb, labels, table, nr):
+        emb = emb.contiguous().float()
+        labels = labels.to(device=emb.device, dtype=torch.int64).contiguous()
+        ctx.save_for_backward(emb, labels, table)
+        ctx.nr = nr
+        return ops.proto_l2_fwd(emb[nr:], labels[nr:], table)[0], ops.proto_l2_fwd(emb[:nr], labels[:nr], table)[0]
+
+    @staticmethod
+    def backward(ctx, g_f, g_r):
+        emb, labels, table = ctx.saved_tensors
+        nr = ctx.nr
+        de = torch.empty_like(emb)
+        for g, sl in ((g_r, slice(0, nr)), (g_f, slice(nr, None))):
+            if g is None:
+                de[sl].zero_()
+            else:
+                ops.proto_l2_bwd(emb[sl], labels[sl], table, g.reshape(1).float().contiguous(), 1.0, demb=de[sl], accumulate=False)
+        return de, None, None, None
+
+
+def proto_l2_sum_split(emb, labels, table, nr):
+    """-> (l2 sum of the forget rows [nr, N), l2 sum of the remain rows [0, nr)); see proto_l2_sum."""
+    return _ProtoL2SumSplit.apply(emb, labels, table, int(nr))
+
+
+class _ProtoL2Sum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, labels, table):
+        emb = emb.contiguous().float()
+        labels = labels.to(device=emb.device, dtype=torch.int64).contiguous()
+        ctx.save_for_backward(emb, labels, table)
+        return ops.proto_l2_fwd(emb, labels, table)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        emb, labels, table = ctx.saved_tensors
+        return ops.proto_l2_bwd(emb, labels, table, g.reshape(1).float().contiguous(), 1.0), None, None
+
+
+def proto_l2_sum(emb, labels, table):
+    """sum_i mean_d (emb[i] - table[labels[i]])^2: divided by the row count, the reference's torch.mean((output - prototype_tensor) ** 2)."""
+    return _ProtoL2Sum.apply(emb, labels, table)
+
+
+PROTO_DISTANCES = ("kl", "l2")
+
+
+def check_proto_distance(distance):
+    if distance not in PROTO_DISTANCES:
+        raise ValueError(f"proto_distance must be one of {PROTO_DISTANCES}, got {distance!r}")
+    return distance
 
 
 class _Combine(torch.autograd.Function):

@@ -438,6 +438,21 @@ def loss_tail(logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, 
     return out[0], out[1:9], out[9:14], dlogits, demb
 
 
+def loss_tail_l2(logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro):
+    """loss_tail with the l2 prototype distance (gsl_loss_tail_l2; the prototype term is required): same five results."""
+    if emb is None or proto is None:
+        raise RuntimeError("gslora_hip: loss_tail_l2 needs the embeddings and the prototype table (without a prototype term use loss_tail)")
+    _need(logits, labels, emb, proto, structure)
+    N, C = logits.shape
+    out = torch.empty(14, device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits)
+    demb = torch.empty_like(emb)
+    L.check(L.load().gsl_loss_tail_l2(_p(logits), _p(labels), N, int(nr), C, _p(emb), _p(proto), emb.shape[1], proto.shape[0],
+                                      _p(structure), float(beta), float(BND), float(alpha), float(w_f), float(w_r), float(BND_pro),
+                                      _p(out), _p(dlogits), _p(demb), _stream()), "gsl_loss_tail_l2")
+    return out[0], out[1:9], out[9:14], dlogits, demb
+
+
 def loss_combine_pack(pack8, structure, has_proto, beta, BND, alpha, w_f, w_r, BND_pro):
     """Data-parallel scalar tail from the all-reduced 8-float pack -> (total [0-dim], meters [8], coefs [5]) — see gsl_loss_combine_pack."""
     _need(pack8, structure)
@@ -562,6 +577,42 @@ def proto_kl_bwd(emb, labels, proto, coef, scale, demb=None, accumulate=None):
     L.check(L.load().gsl_proto_kl_bwd(_p(emb), _p(labels), _p(proto), _p(coef), float(scale), _p(demb), emb.shape[0],
                                       emb.shape[1], proto.shape[0], 1 if acc else 0, _stream()), "gsl_proto_kl_bwd")
     return demb
+
+
+def proto_l2_fwd(emb, labels, proto):
+    """-> [1] f32: sum_i mean_d (emb[i] - proto[labels[i]])^2 (gsl_proto_l2_fwd)."""
+    _need(emb, labels, proto)
+    out = torch.empty(1, device=emb.device, dtype=torch.float32)
+    ws = torch.empty(emb.shape[0], device=emb.device, dtype=torch.float32)
+    L.check(L.load().gsl_proto_l2_fwd(_p(emb), _p(labels), _p(proto), _p(out), _p(ws), emb.shape[0], emb.shape[1], proto.shape[0],
+                                      _stream()), "gsl_proto_l2_fwd")
+    return out
+
+
+def proto_l2_bwd(emb, labels, proto, coef, scale, demb=None, accumulate=None):
+    _need(emb, labels, proto, coef, demb)
+    acc = (demb is not None) if accumulate is None else bool(accumulate)
+    if demb is None:
+        demb = torch.empty_like(emb)
+    L.check(L.load().gsl_proto_l2_bwd(_p(emb), _p(labels), _p(proto), _p(coef), float(scale), _p(demb), emb.shape[0],
+                                      emb.shape[1], proto.shape[0], 1 if acc else 0, _stream()), "gsl_proto_l2_bwd")
+    return demb
+
+
+def topk_max_k():
+    return int(L.load().gsl_topk_max_k())
+
+
+def topk_hits(logits, labels, ks):
+    """-> int32 [len(ks)] device tensor: for each k the number of rows whose label is among the k largest logits (gsl_topk_hits, one launch)."""
+    _need(logits, labels)
+    ks = [int(k) for k in ks]
+    if not ks or len(ks) > topk_max_k() or min(ks) < 1:
+        raise ValueError(f"topk_hits: between 1 and {topk_max_k()} positive values of k, got {ks}")
+    hits = torch.empty(len(ks), device=logits.device, dtype=torch.int32)
+    arr = (ctypes.c_int * len(ks))(*ks)
+    L.check(L.load().gsl_topk_hits(_p(logits), _p(labels), logits.shape[0], logits.shape[1], arr, len(ks), _p(hits), _stream()), "gsl_topk_hits")
+    return hits
 
 
 def group_norms_fwd(flat, toff, tnumel, tgroup, ngroups, tau=0.0):

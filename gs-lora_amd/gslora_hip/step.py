@@ -3,6 +3,7 @@
 Reference loop body: engine_cl.py:59-125 / engine.py:237-330 —
     total = beta * relu(BND - CE_forget) + CE_remain + alpha * L_structure
             + w_f * relu(BND_pro - KL_forget) + w_r * KL_remain
+(proto_distance="l2": the two KL terms are the reference's l2 prototype distance, engine_cl.py:593-594, in the same places)
 Data parallel (one process per GPU, torch.distributed over RCCL): the two hinge arguments are
 batch MEANS, so their global values are all-reduced (one packed 8-float message) before the
 hinges are evaluated — that keeps the single-GPU / nn.DataParallel semantics of the reference —
@@ -63,10 +64,13 @@ class HipBackend:
     proto_kl_sum = staticmethod(losses.proto_kl_sum)
     ce_sum_top1_split = staticmethod(losses.ce_sum_top1_split)
     proto_kl_sum_split = staticmethod(losses.proto_kl_sum_split)
+    proto_l2_sum = staticmethod(losses.proto_l2_sum)
+    proto_l2_sum_split = staticmethod(losses.proto_l2_sum_split)
     structure_loss = staticmethod(losses.structure_loss)
     combine = staticmethod(losses.combine)
     combine_pack = staticmethod(losses.combine_pack)
     loss_tail = staticmethod(ops.loss_tail)
+    loss_tail_l2 = staticmethod(ops.loss_tail_l2)
     loss_tail_max_rows = staticmethod(ops.loss_tail_max_rows)
 
     @staticmethod
@@ -218,11 +222,16 @@ def _model_input(net, x):
 
 def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha, BND, use_structure=True,
                  group_type="block", use_prototype=False, proto_table=None, w_f=0.0, w_r=0.0, BND_pro=0.0,
-                 backend=HipBackend, fuse_batches=True, _comm=_EagerComm):
+                 backend=HipBackend, fuse_batches=True, _comm=_EagerComm, proto_distance="kl"):
     """Runs forward x2, the three-term loss, backward, gradient all-reduce and optimizer.step().
     Returns a packed DEVICE tensor of the 8 meter values (no host sync here):
       [beta*loss_forget, loss_remain, total, alpha*structure, top1_forget%, top1_remain%,
-       w_f*relu(BND_pro-KL_f), w_r*KL_r]"""
+       w_f*relu(BND_pro-KL_f), w_r*KL_r]
+    proto_distance: "kl" (default) or "l2" — the distance of the prototype term (get_prototype_loss, engine_cl.py:571-603); the l2 sums take
+    the places of the KL sums in the scalar tail and in the data-parallel pack."""
+    l2 = losses.check_proto_distance(proto_distance) == "l2" and use_prototype
+    if l2 and not hasattr(backend, "proto_l2_sum"):
+        raise RuntimeError("gs_lora_step: this backend has no l2 prototype distance")
     _check_not_replicated(model)
     net = model.module if isinstance(model, nn.DataParallel) else model
     world = _world()
@@ -248,7 +257,8 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
         out_r, emb_r = model(_model_input(net, x_r), y_r)
         out_f, emb_f = model(_model_input(net, x_f), y_f)
     n_r, n_f = float(x_r.size(0)), float(x_f.size(0))
-    if (split is not None and LOSS_TAIL and not _dp_active() and hasattr(backend, "loss_tail") and out.dtype == torch.float32
+    if (split is not None and LOSS_TAIL and not _dp_active() and hasattr(backend, "loss_tail_l2" if l2 else "loss_tail")
+            and out.dtype == torch.float32
             and out.is_contiguous() and out.dim() == 2 and 0 < nr < out.shape[0] <= min(LOSS_TAIL_ROWS, backend.loss_tail_max_rows()) and out.shape[1] <= 1024
             and (not use_prototype or emb.shape[1] <= 1024)
             and y_all.dtype == torch.int64 and y_all.device == out.device
@@ -257,10 +267,11 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
         # backward down to dlogits / demb — is ONE launch (gsl_loss_tail) instead of ~20; the gradients enter the network's autograd
         # node directly, the group-lasso node gets its coefficient alpha. Same values as the multi-launch path below, bit for bit.
         structure = backend.structure_loss(net, group_type, grad_scale=1.0) if use_structure else None
-        total, meters, coefs, dlogits, demb = backend.loss_tail(out.detach(), y_all, nr, emb.detach() if use_prototype else None,
-                                                                proto_table if use_prototype else None,
-                                                                None if structure is None else structure.detach(), beta, BND, alpha,
-                                                                w_f, w_r, BND_pro)
+        tail = backend.loss_tail_l2 if l2 else backend.loss_tail
+        total, meters, coefs, dlogits, demb = tail(out.detach(), y_all, nr, emb.detach() if use_prototype else None,
+                                                   proto_table if use_prototype else None,
+                                                   None if structure is None else structure.detach(), beta, BND, alpha,
+                                                   w_f, w_r, BND_pro)
         optimizer.zero_grad()
         roots, grads = [out], [dlogits]
         if use_prototype:
@@ -284,10 +295,11 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
         hit_r = backend.ce_sum_top1(out_r.detach(), y_r)[1]
         hit_f = backend.ce_sum_top1(out_f.detach(), y_f)[1]
     if use_prototype and split is not None:
-        kl_f_sum, kl_r_sum = backend.proto_kl_sum_split(split[1], split[2], proto_table, split[3])
+        kl_f_sum, kl_r_sum = (backend.proto_l2_sum_split if l2 else backend.proto_kl_sum_split)(split[1], split[2], proto_table, split[3])
     elif use_prototype:
-        kl_f_sum = backend.proto_kl_sum(emb_f, y_f, proto_table)
-        kl_r_sum = backend.proto_kl_sum(emb_r, y_r, proto_table)
+        proto_sum = backend.proto_l2_sum if l2 else backend.proto_kl_sum
+        kl_f_sum = proto_sum(emb_f, y_f, proto_table)
+        kl_r_sum = proto_sum(emb_r, y_r, proto_table)
     else:
         kl_f_sum = kl_r_sum = None
     # the scalar tail (hinges, weighted sum, meters, the five upstream gradients) is ONE kernel forward and one 5-element multiply
@@ -381,7 +393,7 @@ class GraphedStep:
     bound by the ~370 kernel launches it makes from Python (4.7 ms at batch 4+4 and 5.9 ms at the reference's batch 48+48 on
     MI355X), not by the GPU. Everything that varies from step to step is read from device memory by the captured kernels: the batch
     (static input buffers), the dropout seed (GSL_SEED_ON_DEVICE), AdamW's step count and learning rate (gsl_adamw_flat_dev).
-    Everything else is part of the key — shapes, the loss hyper-parameters, the prototype table, train/eval state, the versions of
+    Everything else is part of the key — shapes, the loss hyper-parameters, the prototype table and distance, train/eval state, the versions of
     the frozen weights (eval()/train() merge round trips, load_state_dict) — and a key change falls back to one eager step (which
     also refreshes the operand caches) followed by a fresh capture. Replays are bit-identical to eager steps (same kernels, same
     seeds; tests/test_hip_graph.py). Under torch.distributed (one process per GPU) the step is captured as three graph segments

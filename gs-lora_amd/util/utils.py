@@ -34,12 +34,20 @@ class AverageMeter(object):
 
 
 def train_accuracy(output, target, topk=(1,)):
-    """top-1 precision in percent (the engines only ever ask for topk=(1,)); one fused HIP launch."""
-    if tuple(topk) != (1,):
-        raise NotImplementedError("gs-lora_amd train_accuracy implements topk=(1,) (all the engines use)")
+    """precision@k in percent. topk=(1,) (all the engines ask for): the 0-dim tensor of the fused CE / top-1 launch. Any other tuple: a
+    list with one 0-dim tensor per k, in the order given, from one HIP launch (gsl_topk_hits: a row is a hit when fewer than k logits are
+    strictly greater than its label's — output.topk(maxk) wherever the k-th place is not tied). The reference computes the same list and
+    returns its first entry alone (:368); the first entry here is that value."""
+    topk = tuple(int(k) for k in topk)
     from gslora_hip import ops
-    out = ops.ce_fwd(output.detach().float().contiguous(), target.to(output.device, torch.int64).contiguous())
-    return out[1] * (100.0 / target.size(0))
+    if topk == (1,):
+        out = ops.ce_fwd(output.detach().float().contiguous(), target.to(output.device, torch.int64).contiguous())
+        return out[1] * (100.0 / target.size(0))
+    if not topk or min(topk) < 1 or max(topk) > output.size(1):
+        raise ValueError(f"train_accuracy: every k of topk must lie in [1, {output.size(1)}] (the number of classes), got {topk}")
+    hits = ops.topk_hits(output.detach().float().contiguous(), target.to(output.device, torch.int64).contiguous(), topk)
+    pct = hits.to(torch.float32) * (100.0 / target.size(0))
+    return [pct[i] for i in range(len(topk))]
 
 
 def count_trainable_parameters(model):

@@ -288,6 +288,23 @@ GSL_API int gsl_proto_kl_fwd(const float* emb, const int64_t* labels, const floa
 GSL_API int gsl_proto_kl_bwd(const float* emb, const int64_t* labels, const float* proto, const float* coef,
                      float scale, float* demb, int B, int D, int C, int accumulate, gsl_stream_t s);
 
+/* ---- K13b prototype l2 (engine_cl.py:593-594, engine.py:712-713: torch.mean((output - prototype_tensor) ** 2)), in the sum form of the
+ * KL pair: out1[0] = sum_i (1/D) sum_d (emb[i,d] - proto[y_i,d])^2 — divided by the row count it is the reference's mean, and it takes the
+ * place of the KL sums in gsl_loss_combine / gsl_loss_combine_pack. f32 accumulation, one wave per row, fixed-order row sum through
+ * row_ws [B]. A label outside [0, C) or a NaN table row (a class without a prototype) gives a NaN sum. */
+GSL_API int gsl_proto_l2_fwd(const float* emb, const int64_t* labels, const float* proto, float* out1, float* row_ws /*[B]*/,
+                     int B, int D, int C, gsl_stream_t s);
+/* demb (+)= coef[0] * scale * (2/D) * (emb - proto[y]) ; coef is a DEVICE scalar (no host sync). */
+GSL_API int gsl_proto_l2_bwd(const float* emb, const int64_t* labels, const float* proto, const float* coef,
+                     float scale, float* demb, int B, int D, int C, int accumulate, gsl_stream_t s);
+
+/* ---- K11b precision@k for several k in one launch (util/utils.py:354-368): hits[j] = number of rows whose label is among the ks[j]
+ * largest logits, counted as "fewer than ks[j] logits are strictly greater than the label's" (equal to output.topk(ks[j]) wherever the
+ * ks[j]-th place is not tied). ks: HOST array of nk <= gsl_topk_max_k() positive ints (it travels in the kernel arguments);
+ * hits: DEVICE int32 [nk], cleared by the call. An out-of-range label is never a hit. */
+GSL_API int gsl_topk_max_k(void);
+GSL_API int gsl_topk_hits(const float* logits, const int64_t* labels, int B, int C, const int* ks, int nk, int* hits, gsl_stream_t s);
+
 /* ---- scalar tail of the step (engine_cl.py:65-125, single process): from the batch SUMS of the kernels above
  *   total = beta*relu(BND - ce_f_sum/n_f) + ce_r_sum/n_r + alpha*structure + w_f*relu(BND_pro - kl_f_sum/n_f) + w_r*kl_r_sum/n_r
  * meters8 = [beta*loss_forget, loss_remain, total, alpha*structure, top1_forget %, top1_remain %, proto_f, proto_r],
@@ -310,6 +327,12 @@ GSL_API int gsl_loss_combine_pack(const float* pack8, const float* structure, in
  * ranges. 0 < nr < N <= gsl_loss_tail_max_rows(). structure (nullable): device scalar, the group-lasso value. */
 GSL_API int gsl_loss_tail_max_rows(void);
 GSL_API int gsl_loss_tail(const float* logits, const int64_t* labels, int N, int nr, int C, const float* emb, const float* proto, int D,
+                  int Cp, const float* structure, float beta, float BND, float alpha, float w_f, float w_r, float BND_pro,
+                  float* out14, float* dlogits, float* demb, gsl_stream_t s);
+/* gsl_loss_tail with the l2 prototype distance (engine_cl.py:593-594) in place of the KL: emb, proto and demb are required. Coefficients
+ * and gradients bit-identical to (meters within an ulp of) gsl_ce_fwd + gsl_proto_l2_fwd + gsl_loss_combine + gsl_ce_bwd + gsl_proto_l2_bwd
+ * on the two row ranges. */
+GSL_API int gsl_loss_tail_l2(const float* logits, const int64_t* labels, int N, int nr, int C, const float* emb, const float* proto, int D,
                   int Cp, const float* structure, float beta, float BND, float alpha, float w_f, float w_r, float BND_pro,
                   float* out14, float* dlogits, float* demb, gsl_stream_t s);
 
