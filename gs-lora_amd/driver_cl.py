@@ -89,6 +89,9 @@ def get_args(argv=None):
                         "instead of a ToTensor() dataset transform on the host")
     p.add_argument("--verify_pairs", type=int, default=0,
                    help="after each task, face verification (util.utils.perform_val) on this many synthetic same / different pairs; 0: off")
+    p.add_argument("--per_class", default=False, action="store_true",
+                   help="after each task, per-class accuracy of the forget / remain test sets and, for every forgotten class, its three "
+                        "most frequent predictions (engine_cl.eval_data_per_class; test/test_own.py:99-144)")
     p.add_argument("--outdir", default=None)
     p.add_argument("--seed", type=int, default=1337)
     p.add_argument("--average_weight", default=False, action="store_true", help="EMA model of the reference (:502-507, :1058-1098)")
@@ -150,12 +153,30 @@ def subset(x, y, classes):
     return TensorDataset(x[m], y[m])
 
 
-def run_tasks(model, args, task_data, dev, out, depth, cfg=None, after_reinit=None, after_task=None):
+def per_class_record(model, te_f, te_r, dev, task_i, forget_cls=None):
+    """The --per_class part of a task record: per-class accuracy (percent; None for a class the set does not hold) of the forget and the
+    remain test set, and for each forgotten class (forget_cls, or the classes the forget set holds) its three most frequent predictions
+    [(class, samples), ...] from its row of the confusion matrix — where the forgotten samples fall."""
+    f = engine_cl.eval_data_per_class(model, te_f, dev, f"forget-{task_i}-per-class", confusion=True)
+    r = engine_cl.eval_data_per_class(model, te_r, dev, f"remain-{task_i}-per-class")
+    table = lambda e: {c: a for c, (a, n) in enumerate(zip(e["class_accuracy"].tolist(), e["class_total"].tolist())) if n}
+    classes = [int(c) for c in forget_cls] if forget_cls is not None else sorted(table(f))
+    top3 = {}
+    for c in classes:
+        row = f["confusion"][c]
+        order = torch.argsort(row, descending=True, stable=True)[:3].tolist()      # ties: the lower class first
+        top3[c] = [(p, int(row[p])) for p in order if int(row[p]) > 0]
+    return dict(forget=table(f), remain=table(r), forget_top3=top3)
+
+
+def run_tasks(model, args, task_data, dev, out, depth, cfg=None, after_reinit=None, after_task=None, per_class=None):
     """The reference's task loop on a model that is already LoRA-marked and on the device.
     task_data(task_i, model) -> dict(loader_f, loader_r, te_f, te_r, protos): the task's train / test loaders and prototype dict (called
     after the reload + re-initialisation of the task, so it may run calculate_prototypes on the model).
     after_reinit(model, task_i): hook behind reinitialize_lora_parameters (tests install seeded adapter matrices: kaiming_uniform_ draws
-    from the device RNG). after_task(task_i, model, ema_model, record): hook behind the task's checkpoint (model in train mode)."""
+    from the device RNG). after_task(task_i, model, ema_model, record): hook behind the task's checkpoint (model in train mode).
+    per_class (default: args.per_class): add record["per_class"] = per_class_record(...) after the task's last evaluation."""
+    per_class = bool(getattr(args, "per_class", False)) if per_class is None else bool(per_class)
     os.makedirs(os.path.join(out, "task-level"), exist_ok=True)
     cfg = cfg or {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": "VIT",
                   "PROTO_DISTANCE": getattr(args, "pro_distance", "kl")}
@@ -217,6 +238,7 @@ def run_tasks(model, args, task_data, dev, out, depth, cfg=None, after_reinit=No
         norms = [float(v) for v in get_norm_of_lora(model, type="L2", group_num=depth, group_type="block")]   # :1100-1106
         forget_after = engine_cl.eval_data(model, te_f, dev, f"forget-{task_i}-after")
         remain_after = engine_cl.eval_data(model, te_r, dev, f"remain-{task_i}-after")
+        per_class_rec = per_class_record(model, te_f, te_r, dev, task_i, td.get("info", {}).get("forget_cls")) if per_class else None
         model.eval()                                          # :1696-1705: checkpoints hold MERGED weights
         torch.save(model.state_dict(), os.path.join(out, "task-level", f"Backbone_task_{task_i}.pth"))
         model.train()
@@ -224,6 +246,8 @@ def run_tasks(model, args, task_data, dev, out, depth, cfg=None, after_reinit=No
                    total_loss=ret[6].avg if (ret is not None and ret[6].count) else None,
                    forget_before=forget_before, forget_after=forget_after, remain_before=remain_before, remain_after=remain_after,
                    ema_acc=ema_accs[-1] if ema_accs else None, ema_accs=ema_accs, **td.get("info", {}))
+        if per_class_rec is not None:
+            rec["per_class"] = per_class_rec
         if after_task is not None:
             after_task(task_i, model, ema_model, rec)
         report.append(rec)

@@ -14,6 +14,7 @@ import loralib as _lora
 import util.utils as util
 from engine_cl import DISP_FREQ, VER_FREQ, _log, _unwrap  # noqa: F401
 from engine_cl import eval_data as _eval_data_cl
+from engine_cl import eval_data_per_class as _eval_data_per_class_cl
 from util.utils import get_time
 from gslora_hip import losses as _losses
 from gslora_hip.step import MeterQueue, gs_lora_step, pick_stepper  # noqa: F401
@@ -141,6 +142,13 @@ def eval_data(model, dataloader, device, mode: str, batch: int = 0):
     """Reference engine.py:501-529: accuracy (0-100) of a copy of the model in eval mode; the caller's model keeps its mode and weights."""
     with _evaluation_copy(model) as m:
         return _eval_data_cl(m, dataloader, device, mode, batch)
+
+
+def eval_data_per_class(model, dataloader, device, mode: str, batch: int = 0, num_classes=None, confusion: bool = False):
+    """engine_cl.eval_data_per_class (per-class totals, corrects, accuracies and the confusion matrix; test/test_own.py:99-144) of a copy of
+    the model in eval mode, as eval_data above: the caller's model keeps its mode and weights."""
+    with _evaluation_copy(model) as m:
+        return _eval_data_per_class_cl(m, dataloader, device, mode, batch, num_classes=num_classes, confusion=confusion)
 
 
 def _check_group_pos(model, group_pos):

@@ -5,7 +5,8 @@ libgslora_hip.so via gslora_hip.step.gs_lora_step. Differences that are delibera
   * one deferred host sync per display interval instead of >= 8 `.item()` per step (meter values
     are identical);
   * under torch.distributed (one process per GPU) the step is data-parallel (see gslora_hip/step.py);
-  * `train_one_epoch_regularzation` / `get_reg_loss` (EWC/MAS/L2 baselines) keep their names only.
+  * `train_one_epoch_regularzation` / `get_reg_loss` (EWC/MAS/L2 baselines) keep their names only;
+  * `eval_data_per_class` is an addition: eval_data with the per-class table of the reference's test/test_own.py:99-144.
 """
 import os
 
@@ -207,6 +208,50 @@ def eval_data(model, dataloader, device, mode: str, batch: int = 0):
     print("Test {} Accuracy:{:2f}%".format(mode, accuracy))
     _log({"Test {} Accuracy".format(mode): accuracy})
     return accuracy
+
+
+def eval_data_per_class(model, dataloader, device, mode: str, batch: int = 0, num_classes=None, confusion: bool = False):
+    """eval_data with the per-class table of the reference's test/test_own.py:99-144: a dict of
+      accuracy        float, 0-100: the number eval_data returns for the same loader (the same integer hit count over the same logits)
+      class_total     int64 [C]: samples of each class             class_correct   int64 [C]: of them, predicted as their class
+      class_accuracy  float64 [C]: 100 * correct / total, NaN for a class without samples (util.utils.write_class_accuracy writes the file)
+      confusion       int32 [C, C], row = label, column = prediction (only with confusion=True)
+    as CPU tensors. The prediction is torch.max(outputs, 1)'s (first maximum). Eval mode, evaluation dtype and their restoration are
+    eval_data's; the counters stay on the device (gsl_class_stats per batch, any batch size, ragged tail included) and are read once at the
+    end. C is the width of the logits; num_classes, when given, must be that width. A label outside [0, C) is an error."""
+    from gslora_hip import ops
+    model.eval()
+    net = _unwrap(model)
+    eval_dt, train_dt = util._eval_dtype_of(net), getattr(net, "compute_dtype", None)
+    if eval_dt:
+        net.set_compute_dtype(eval_dt)
+    stats, total = None, 0
+    try:
+        with torch.no_grad():
+            for images, labels in dataloader:
+                images, labels = images.to(device), labels.to(device).long()
+                outputs, _ = model(images, labels)
+                if stats is None:
+                    if num_classes is not None and int(num_classes) != outputs.shape[1]:
+                        raise ValueError(f"eval_data_per_class: num_classes={num_classes}, but the model has {outputs.shape[1]} logits per image")
+                    stats = ops.ClassStats(outputs.shape[1], outputs.device, confusion=confusion)
+                stats.add(outputs.float(), labels.contiguous())
+                total += labels.size(0)
+    finally:
+        if eval_dt:
+            net.set_compute_dtype(train_dt)
+    if stats is None:
+        raise ValueError("eval_data_per_class: the loader is empty")
+    res = stats.finish()
+    if res["bad"]:
+        raise ValueError(f"eval_data_per_class: {res['bad']} labels lie outside [0, {stats.C})")
+    accuracy = 100 * float(res["hit"].sum().item()) / max(total, 1)
+    print("Test {} Accuracy:{:2f}%".format(mode, accuracy))
+    _log({"Test {} Accuracy".format(mode): accuracy})
+    out = dict(accuracy=accuracy, class_accuracy=res["acc"], class_total=res["count"], class_correct=res["hit"])
+    if confusion:
+        out["confusion"] = res["confusion"]
+    return out
 
 
 def get_structure_loss(model: torch.nn.Module, imagenet=False):

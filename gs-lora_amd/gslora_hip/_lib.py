@@ -83,6 +83,9 @@ SIGNATURES = {
     "gsl_verif_pair_dist": [_vp, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "gsl_verif_fold_counts": [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp],
     "gsl_verif_select": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "gsl_class_stats": [_vp, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "gsl_class_embed_sum": [_vp, _l, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "gsl_class_finish": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"gsl_last_error": C.c_char_p, "gsl_lora_grad_ws_elems": C.c_long, "gsl_gemm_mulgrad_ws_elems": C.c_long,
              "gsl_lora_grad_batch_ws_elems": C.c_long}

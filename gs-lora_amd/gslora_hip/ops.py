@@ -615,6 +615,99 @@ def topk_hits(logits, labels, ks):
     return hits
 
 
+# ---- per-class evaluation (csrc/classstat.hip; engine_cl.eval_data_per_class, util.utils.calculate_prototypes)
+class ClassStats:
+    """The per-class counters of one evaluation, in ONE zeroed int64 device buffer so that one host read serves it:
+    count [C] | hit [C] | bad [1] | acc [C] (f64 bits, written by finish()) | confusion [C, C] (int32 pairs, only if asked for).
+    The views are plain integer buffers: under data parallelism one sum all_reduce of `buf` would combine the ranks."""
+
+    def __init__(self, C, device, confusion=False):
+        self.C = C = int(C)
+        if C <= 0:
+            raise ValueError(f"ClassStats: the number of classes must be positive, got {C}")
+        self.buf = torch.zeros(3 * C + 1 + ((C * C + 1) // 2 if confusion else 0), device=device, dtype=torch.int64)
+        _need(self.buf)
+        self.count, self.hit, self.bad = self.buf[:C], self.buf[C:2 * C], self.buf[2 * C:2 * C + 1]
+        self.acc = self.buf[2 * C + 1:3 * C + 1].view(torch.float64)
+        self.confusion = self.buf[3 * C + 1:].view(torch.int32)[:C * C].view(C, C) if confusion else None
+
+    def add(self, logits, labels):
+        class_stats(logits, labels, self.count, self.hit, self.bad, self.confusion)
+
+    def finish(self):
+        """-> dict of CPU tensors (count, hit int64 [C]; acc f64 [C], NaN where count == 0; confusion int32 [C, C] or None) and bad (int)."""
+        class_finish(self.count, self.hit, acc=self.acc)
+        host, C = self.buf.cpu(), self.C
+        return dict(count=host[:C], hit=host[C:2 * C], bad=int(host[2 * C]), acc=host[2 * C + 1:3 * C + 1].view(torch.float64),
+                    confusion=host[3 * C + 1:].view(torch.int32)[:C * C].view(C, C) if self.confusion is not None else None)
+
+
+def _labels_i64(labels, n, what):
+    _need(labels)
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != n:
+        raise RuntimeError(f"gslora_hip: {what} takes int64 labels [{n}], got {labels.dtype} {tuple(labels.shape)}")
+    return labels
+
+
+def _counter(t, n, dtype, what):
+    _need(t)
+    if t.dtype != dtype or t.numel() != n:
+        raise RuntimeError(f"gslora_hip: {what} must be a contiguous {dtype} device buffer of {n} elements")
+    return t
+
+
+def class_stats(logits, labels, count, hit, bad, confusion=None):
+    """count[label] += 1, hit[label] += (first arg-max of the row == label), confusion[label, arg-max] += 1 for one batch of f32 logits
+    [B, C] (row slices are taken with their stride); labels outside [0, C) add to bad[0] only (gsl_class_stats). In place; returns None."""
+    logits = _rows_f32(logits, "logits")
+    B, C = logits.shape
+    _labels_i64(labels, B, "class_stats")
+    _counter(count, C, torch.int64, "count"), _counter(hit, C, torch.int64, "hit"), _counter(bad, 1, torch.int64, "bad")
+    if confusion is not None:
+        _counter(confusion, C * C, torch.int32, "confusion")
+    if B == 0:
+        return
+    L.check(L.load().gsl_class_stats(_p(logits), logits.stride(0), _p(labels), B, C, _p(count), _p(hit), _p(bad), _p(confusion), _stream()),
+            "gsl_class_stats")
+
+
+def class_embed_sum(emb, labels, sums, count, bad):
+    """sums[c] += emb[i] over the rows with labels[i] == c in increasing i (sequential f32 adds: the reference's summation order), count[c]
+    += their number; labels outside [0, C) add to bad[0] only (gsl_class_embed_sum). In place; returns None."""
+    emb = _rows_f32(emb, "emb")
+    B, D = emb.shape
+    _need(sums)
+    if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[1] != D:
+        raise RuntimeError(f"gslora_hip: class_embed_sum takes sums f32 [C, {D}], got {sums.dtype} {tuple(sums.shape)}")
+    C = sums.shape[0]
+    _labels_i64(labels, B, "class_embed_sum")
+    _counter(count, C, torch.int64, "count"), _counter(bad, 1, torch.int64, "bad")
+    if B == 0:
+        return
+    L.check(L.load().gsl_class_embed_sum(_p(emb), emb.stride(0), _p(labels), B, D, C, _p(sums), _p(count), _p(bad), _stream()),
+            "gsl_class_embed_sum")
+
+
+def class_finish(count, hit=None, sums=None, acc=None, proto=None):
+    """acc [C] f64 = 100 * hit / count and / or proto [C, D] f32 = sums / count, NaN for a class without samples (gsl_class_finish). The
+    outputs are allocated when not given; returns (acc, proto) with None for the one not asked for (acc needs hit, proto needs sums)."""
+    _need(count, hit, sums, acc, proto)
+    C = count.numel()
+    _counter(count, C, torch.int64, "count")
+    if hit is not None:
+        _counter(hit, C, torch.int64, "hit")
+        acc = _counter(acc, C, torch.float64, "acc") if acc is not None else torch.empty(C, device=count.device, dtype=torch.float64)
+    D = 0
+    if sums is not None:
+        if sums.dtype != torch.float32 or sums.dim() != 2 or sums.shape[0] != C:
+            raise RuntimeError(f"gslora_hip: class_finish takes sums f32 [{C}, D], got {sums.dtype} {tuple(sums.shape)}")
+        D = sums.shape[1]
+        proto = _counter(proto, C * D, torch.float32, "proto") if proto is not None else torch.empty_like(sums)
+    L.check(L.load().gsl_class_finish(_p(count), _p(hit), _p(sums), C, D, _p(acc) if hit is not None else None,
+                                      _p(proto) if sums is not None else None, _stream()), "gsl_class_finish")
+    return (acc if hit is not None else None), (proto if sums is not None else None)
+
+
 def group_norms_fwd(flat, toff, tnumel, tgroup, ngroups, tau=0.0):
     _need(flat, toff, tnumel, tgroup)
     dev = flat.device

@@ -2,7 +2,8 @@
 (AverageMeter :316-332, train_accuracy :354-368, count_trainable_parameters :423-425,
 reinitialize_lora_parameters :428-441, calculate_prototypes :502-549, replace_ffn_with_lora :552-577,
 modify_head :580-621, resume_head :623-636, create_few_shot_dataset :457-499, get_unique_classes :444-454) and its face verification
-(perform_val :167-230, buffer_val :298-314), backed by the HIP model and the HIP metric kernels (util/verification.py).
+(perform_val :167-230, buffer_val :298-314), backed by the HIP model and the HIP metric kernels (util/verification.py);
+write_class_accuracy writes the per-class accuracy file of test/test_own.py:140-143.
 Data plumbing (load_bin / get_val_pair: mxnet, bcolz) and perform_val_deit are out of scope."""
 import copy
 import datetime
@@ -70,9 +71,11 @@ def reinitialize_lora_parameters(model):
 
 def calculate_prototypes(backbone, dataset, batch_size=32, device="cuda", aug_num=0):
     """Per-class mean embedding in eval (merged-LoRA) mode; leaves the model in eval() like the
-    reference does. Class sums are accumulated on the device (one index_add per batch) instead of a
-    per-sample Python loop; the result dict holds CPU tensors as before."""
+    reference does. Class sums are accumulated on the device, one gsl_class_embed_sum launch per batch: each class adds its embeddings
+    one by one in sample order, the reference's `embeds_sum[label] += embed` (:540-542), so the f32 sums do not depend on the batch size
+    or on the run. The result dict holds CPU tensors, for the classes that occur, as before."""
     from torch.utils.data import ConcatDataset, DataLoader
+    from gslora_hip import ops
     backbone.eval()
     backbone.to(device)
     if aug_num != 0:
@@ -102,11 +105,28 @@ def calculate_prototypes(backbone, dataset, batch_size=32, device="cuda", aug_nu
                 else:
                     ncls = int(labels.max().item()) + 1
                 sums = torch.zeros(ncls, emb.shape[1], device=emb.device)
-                counts = torch.zeros(ncls, device=emb.device)
-            sums.index_add_(0, labels, emb)
-            counts.index_add_(0, labels, torch.ones_like(labels, dtype=torch.float32))
-    sums, counts = sums.cpu(), counts.cpu()
-    return {int(c): (sums[c] / counts[c]) for c in torch.nonzero(counts).flatten().tolist()}
+                counts = torch.zeros(ncls + 1, device=emb.device, dtype=torch.int64)      # [ncls] class counts | labels outside [0, ncls)
+            ops.class_embed_sum(emb.float(), labels.contiguous(), sums, counts[:ncls], counts[ncls:])
+    if sums is None:
+        return {}
+    protos = ops.class_finish(counts[:ncls], sums=sums)[1].cpu()      # sums / counts, the f32 division of :547
+    counts = counts.cpu()
+    if int(counts[ncls]):
+        raise ValueError(f"calculate_prototypes: {int(counts[ncls])} labels lie outside [0, {ncls}), the classes of the model's head")
+    return {int(c): protos[c] for c in torch.nonzero(counts[:ncls]).flatten().tolist()}
+
+
+def write_class_accuracy(path, class_correct, class_total):
+    """The reference's per-class accuracy file (test/test_own.py:140-143, `class_accuracy40.txt`): one line "%4.4f %%" of
+    100 * correct / total per class, in class order. class_correct / class_total: sequences or tensors of one length (the `class_correct`
+    and `class_total` of eval_data_per_class). A class without samples, where the reference divides by zero, is written as the format renders NaN (" nan %")."""
+    correct, total = [float(v) for v in class_correct], [float(v) for v in class_total]
+    if len(correct) != len(total):
+        raise ValueError(f"write_class_accuracy: {len(correct)} corrects for {len(total)} totals")
+    with open(path, "w") as f:
+        for c, t in zip(correct, total):
+            f.write("%4.4f %%" % (100 * c / t if t else float("nan")))
+            f.write("\n")
 
 
 def _eval_dtype_of(net):

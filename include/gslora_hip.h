@@ -397,6 +397,26 @@ GSL_API int gsl_verif_fold_counts(const float* dist, const uint8_t* issame, int 
 GSL_API int gsl_verif_select(const int* counts, const int* fold_tot, const double* thresholds, int Tn, int nrof_folds, const float* xnorm,
                      double* out, gsl_stream_t s);
 
+/* ---- per-class evaluation (test/test_own.py:99-144 per-class accuracy, util/utils.py:527-547 class prototypes); csrc/classstat.hip.
+ * All buffers are DEVICE buffers of the caller that persist across batches (clear them once, call per batch, finish once); no call
+ * allocates, synchronises or uses a floating-point atomic, so every one of them can be captured in a HIP graph.
+ * S1 (test_own.py:120-130): logits f32 [B, C] with row stride ld (elements), labels int64 [B]. Per row the prediction is the FIRST arg-max
+ * of the row as torch.max(outputs, 1) returns it (a NaN ranks above every number); count[label] += 1, hit[label] += (prediction == label),
+ * and, when confusion (int32 [C, C], nullable) is given, confusion[label][prediction] += 1 (a cell holds < 2^31 samples). count, hit: int64
+ * [C]. A label outside [0, C) adds one to bad[0] (int64) and touches nothing else. Integer adds: independent of the order of the rows. */
+GSL_API int gsl_class_stats(const float* logits, long ld, const int64_t* labels, int B, int C, int64_t* count, int64_t* hit, int64_t* bad,
+                    int* confusion, gsl_stream_t s);
+/* S2 (util/utils.py:540-542, `embeds_sum[label] += embed; embeds_count[label] += 1`): emb f32 [B, D] with row stride ld, sum f32 [C, D],
+ * count int64 [C]. sum[c, :] += emb[i, :] for the rows with labels[i] == c in increasing i, one plain f32 add per row on top of the value
+ * already in sum: over any split of a data set into batches the result is the reference's sequential sum bit for bit. count[c] += the
+ * number of such rows; labels outside [0, C) are counted in bad[0] and skipped. D <= 2^20. */
+GSL_API int gsl_class_embed_sum(const float* emb, long ld, const int64_t* labels, int B, int D, int C, float* sum, int64_t* count,
+                        int64_t* bad, gsl_stream_t s);
+/* S3: acc f64 [C] (nullable; needs hit) = 100 * hit / count, the f64 division of test_own.py:134 / :142; proto f32 [C, D] (nullable; needs
+ * sum) = sum / count, the f32 division of util/utils.py:547. Classes with count == 0 hold NaN. */
+GSL_API int gsl_class_finish(const int64_t* count, const int64_t* hit, const float* sum, int C, int D, double* acc, float* proto,
+                     gsl_stream_t s);
+
 /* dropout keep-mask as the kernels compute it (for tests): keep[i] = 1/0 for element index i. */
 GSL_API int gsl_dropout_mask(uint8_t* keep, long n, float p_drop, uint64_t seed, uint32_t site, gsl_stream_t s);
 
