@@ -14,7 +14,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
-SOURCES = ["gemm.hip", "norm.hip", "lora.hip", "head.hip", "attention.hip", "verif.hip", "classstat.hip"]
+SOURCES = ["gemm.hip", "norm.hip", "lora.hip", "patch.hip", "head.hip", "loss.hip", "attention.hip", "verif.hip", "classstat.hip"]
 # translation units that are compiled a second time with -DGSL_OP_F16: the same kernels with IEEE fp16 MFMA operands (dtype GSL_F16), in
 # namespace gsl_h16, behind hidden h16_<entry> symbols that the exported entry points forward to (csrc/gsl_common.h, csrc/gsl_h16.h)
 SOURCES_F16 = ["gemm.hip", "attention.hip"]

@@ -12,155 +12,83 @@ import torch
 from . import ops
 
 
-class _CESum(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels):
-        logits = logits.contiguous().float()
-        labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
-        out = ops.ce_fwd(logits, labels)
-        ctx.save_for_backward(logits, labels)
-        ctx.mark_non_differentiable(out[1])
-        return out[0], out[1]
+class _RowSum(torch.autograd.Function):
+    """Sum over the rows of a per-row loss: fwd(x, labels[, table]) -> the sums (the first is the loss, `nondiff` names the others, such as
+    CE's hit count); backward is bwd(x, labels[, table], coef, 1.0) with the upstream gradient as a device scalar."""
 
     @staticmethod
-    def backward(ctx, g_sum, _g_cnt):
-        logits, labels = ctx.saved_tensors
-        coef = g_sum.reshape(1).float().contiguous()
-        return ops.ce_bwd(logits, labels, coef, 1.0), None
+    def forward(ctx, x, labels, table, fwd, bwd, nondiff):
+        x = x.contiguous().float()
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+        extra = () if table is None else (table,)
+        ctx.save_for_backward(x, labels, *extra)
+        ctx.bwd = bwd
+        res = tuple(fwd(x, labels, *extra))
+        ctx.mark_non_differentiable(*(res[i] for i in nondiff))
+        return res
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return (ctx.bwd(*ctx.saved_tensors, g.reshape(1).float().contiguous(), 1.0),) + (None,) * 5
+
+
+class _RowSumSplit(torch.autograd.Function):
+    """_RowSum of the remain rows [0, nr) and the forget rows [nr, N) of ONE tensor (the step runs both batches as one forward); `order`
+    ("rf" or "fr") is the order of the two ranges in the outputs. Backward writes the two row ranges of a single gradient buffer — slicing
+    the tensor in Python instead would make autograd build two zero-filled full-size gradients and add them (10 extra one-off kernels per
+    step)."""
+
+    @staticmethod
+    def forward(ctx, x, labels, table, nr, fwd, bwd, nondiff, order):
+        x = x.contiguous().float()
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+        extra = () if table is None else (table,)
+        ctx.save_for_backward(x, labels, *extra)
+        ctx.bwd, ctx.order, ctx.ranges = bwd, order, {"r": slice(0, nr), "f": slice(nr, None)}
+        res = tuple(v for k in order for v in fwd(x[ctx.ranges[k]], labels[ctx.ranges[k]], *extra))
+        ctx.mark_non_differentiable(*(res[i] for i in nondiff))
+        return res
+
+    @staticmethod
+    def backward(ctx, *gs):
+        x, labels, *extra = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        for k in "rf":
+            g, sl = gs[ctx.order.index(k) * (len(gs) // 2)], ctx.ranges[k]
+            if g is None:
+                dx[sl].zero_()
+            else:
+                ctx.bwd(x[sl], labels[sl], *extra, g.reshape(1).float().contiguous(), 1.0, dx[sl], False)
+        return (dx,) + (None,) * 7
 
 
 def ce_sum_top1(logits, labels):
     """-> (sum_i CE_i, number of top-1 hits), both 0-dim f32 device tensors."""
-    return _CESum.apply(logits, labels)
-
-
-class _CESumSplit(torch.autograd.Function):
-    """ce_sum_top1 of the remain rows [0, nr) and the forget rows [nr, N) of ONE logits tensor (the step runs both batches as one
-    forward). Backward writes the two row ranges of a single dlogits buffer — slicing the logits in Python instead would make
-    autograd build two zero-filled full-size gradients and add them (10 extra one-off kernels per step)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, nr):
-        logits = logits.contiguous().float()
-        labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
-        out_r, out_f = ops.ce_fwd(logits[:nr], labels[:nr]), ops.ce_fwd(logits[nr:], labels[nr:])
-        ctx.save_for_backward(logits, labels)
-        ctx.nr = nr
-        res = (out_r[0], out_r[1], out_f[0], out_f[1])
-        ctx.mark_non_differentiable(res[1], res[3])
-        return res
-
-    @staticmethod
-    def backward(ctx, g_r, _c_r, g_f, _c_f):
-        logits, labels = ctx.saved_tensors
-        nr = ctx.nr
-        dl = torch.empty_like(logits)
-        for g, sl in ((g_r, slice(0, nr)), (g_f, slice(nr, None))):
-            if g is None:
-                dl[sl].zero_()
-            else:
-                ops.ce_bwd(logits[sl], labels[sl], g.reshape(1).float().contiguous(), 1.0, dlogits=dl[sl], accumulate=False)
-        return dl, None, None
+    return _RowSum.apply(logits, labels, None, ops.ce_fwd, ops.ce_bwd, (1,))
 
 
 def ce_sum_top1_split(logits, labels, nr):
     """-> (CE sum, top-1 hits) of rows [0, nr) and of rows [nr, N): four 0-dim f32 device tensors."""
-    return _CESumSplit.apply(logits, labels, int(nr))
+    return _RowSumSplit.apply(logits, labels, None, int(nr), ops.ce_fwd, ops.ce_bwd, (1, 3), "rf")
 
 
-class _ProtoKLSumSplit(torch.autograd.Function):
-    """proto_kl_sum of rows [nr, N) (forget) and rows [0, nr) (remain) of one embedding tensor; one demb buffer in backward."""
-
-    @staticmethod
-    def forward(ctx, emb, labels, table, nr):
-        emb = emb.contiguous().float()
-        labels = labels.to(device=emb.device, dtype=torch.int64).contiguous()
-        ctx.save_for_backward(emb, labels, table)
-        ctx.nr = nr
-        return ops.proto_kl_fwd(emb[nr:], labels[nr:], table)[0], ops.proto_kl_fwd(emb[:nr], labels[:nr], table)[0]
-
-    @staticmethod
-    def backward(ctx, g_f, g_r):
-        emb, labels, table = ctx.saved_tensors
-        nr = ctx.nr
-        de = torch.empty_like(emb)
-        for g, sl in ((g_r, slice(0, nr)), (g_f, slice(nr, None))):
-            if g is None:
-                de[sl].zero_()
-            else:
-                ops.proto_kl_bwd(emb[sl], labels[sl], table, g.reshape(1).float().contiguous(), 1.0, demb=de[sl], accumulate=False)
-        return de, None, None, None
+def proto_kl_sum(emb, labels, table):
+    return _RowSum.apply(emb, labels, table, ops.proto_kl_fwd, ops.proto_kl_bwd, ())[0]
 
 
 def proto_kl_sum_split(emb, labels, table, nr):
     """-> (KL sum of the forget rows [nr, N), KL sum of the remain rows [0, nr))."""
-    return _ProtoKLSumSplit.apply(emb, labels, table, int(nr))
-
-
-class _ProtoKLSum(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, emb, labels, table):
-        emb = emb.contiguous().float()
-        labels = labels.to(device=emb.device, dtype=torch.int64).contiguous()
-        ctx.save_for_backward(emb, labels, table)
-        return ops.proto_kl_fwd(emb, labels, table)[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        emb, labels, table = ctx.saved_tensors
-        return ops.proto_kl_bwd(emb, labels, table, g.reshape(1).float().contiguous(), 1.0), None, None
-
-
-def proto_kl_sum(emb, labels, table):
-    return _ProtoKLSum.apply(emb, labels, table)
-
-
-class _ProtoL2SumSplit(torch.autograd.Function):
-    """proto_l2_sum of rows [nr, N) (forget) and rows [0, nr) (remain) of one embedding tensor; one demb buffer in backward."""
-
-    @staticmethod
-    def forward(ctx, emb, labels, table, nr):
-        emb = emb.contiguous().float()
-        labels = labels.to(device=emb.device, dtype=torch.int64).contiguous()
-        ctx.save_for_backward(emb, labels, table)
-        ctx.nr = nr
-        return ops.proto_l2_fwd(emb[nr:], labels[nr:], table)[0], ops.proto_l2_fwd(emb[:nr], labels[:nr], table)[0]
-
-    @staticmethod
-    def backward(ctx, g_f, g_r):
-        emb, labels, table = ctx.saved_tensors
-        nr = ctx.nr
-        de = torch.empty_like(emb)
-        for g, sl in ((g_r, slice(0, nr)), (g_f, slice(nr, None))):
-            if g is None:
-                de[sl].zero_()
-            else:
-                ops.proto_l2_bwd(emb[sl], labels[sl], table, g.reshape(1).float().contiguous(), 1.0, demb=de[sl], accumulate=False)
-        return de, None, None, None
-
-
-def proto_l2_sum_split(emb, labels, table, nr):
-    """-> (l2 sum of the forget rows [nr, N), l2 sum of the remain rows [0, nr)); see proto_l2_sum."""
-    return _ProtoL2SumSplit.apply(emb, labels, table, int(nr))
-
-
-class _ProtoL2Sum(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, emb, labels, table):
-        emb = emb.contiguous().float()
-        labels = labels.to(device=emb.device, dtype=torch.int64).contiguous()
-        ctx.save_for_backward(emb, labels, table)
-        return ops.proto_l2_fwd(emb, labels, table)[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        emb, labels, table = ctx.saved_tensors
-        return ops.proto_l2_bwd(emb, labels, table, g.reshape(1).float().contiguous(), 1.0), None, None
+    return _RowSumSplit.apply(emb, labels, table, int(nr), ops.proto_kl_fwd, ops.proto_kl_bwd, (), "fr")
 
 
 def proto_l2_sum(emb, labels, table):
     """sum_i mean_d (emb[i] - table[labels[i]])^2: divided by the row count, the reference's torch.mean((output - prototype_tensor) ** 2)."""
-    return _ProtoL2Sum.apply(emb, labels, table)
+    return _RowSum.apply(emb, labels, table, ops.proto_l2_fwd, ops.proto_l2_bwd, ())[0]
+
+
+def proto_l2_sum_split(emb, labels, table, nr):
+    """-> (l2 sum of the forget rows [nr, N), l2 sum of the remain rows [0, nr)); see proto_l2_sum."""
+    return _RowSumSplit.apply(emb, labels, table, int(nr), ops.proto_l2_fwd, ops.proto_l2_bwd, (), "fr")
 
 
 PROTO_DISTANCES = ("kl", "l2")

@@ -409,6 +409,11 @@ def lora_grad_batch(entries, gscale=None):
     L.check(lib.gsl_lora_grad_batch(arr, len(entries), _p(ws), code(entries[0][0].dtype), _p(gscale), _stream()), "gsl_lora_grad_batch")
 
 
+def _tail14(out):
+    """The 14 floats every form of the scalar tail writes -> (total [0-dim], meters [8], coefs [5])."""
+    return out[0], out[1:9], out[9:14]
+
+
 def loss_combine(ce_r_sum, ce_f_sum, kl_f_sum, kl_r_sum, structure, hit_r, hit_f, n_r, n_f, beta, BND, alpha, w_f, w_r, BND_pro):
     """-> (total [0-dim], meters [8], coefs [5]) — see gsl_loss_combine."""
     _need(ce_r_sum, ce_f_sum, kl_f_sum, kl_r_sum, structure, hit_r, hit_f)
@@ -418,39 +423,36 @@ def loss_combine(ce_r_sum, ce_f_sum, kl_f_sum, kl_r_sum, structure, hit_r, hit_f
                                       float(n_r), float(n_f), float(beta), float(BND), float(alpha), float(w_f), float(w_r),
                                       float(BND_pro), out.data_ptr(), out.data_ptr() + 4, out.data_ptr() + 36, _stream()),
             "gsl_loss_combine")
-    return out[0], out[1:9], out[9:14]
+    return _tail14(out)
 
 
 def loss_tail_max_rows():
     return int(L.load().gsl_loss_tail_max_rows())
 
 
-def loss_tail(logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro):
-    """The loss section of a single-process step in one launch (gsl_loss_tail): -> (total, meters [8], coefs [5], dlogits, demb or None)."""
+def _loss_tail(entry, logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro):
+    """gsl_loss_tail or gsl_loss_tail_l2 (same arguments): -> (total, meters [8], coefs [5], dlogits, demb or None)."""
     _need(logits, labels, emb, proto, structure)
     N, C = logits.shape
     out = torch.empty(14, device=logits.device, dtype=torch.float32)
     dlogits = torch.empty_like(logits)
     demb = None if emb is None else torch.empty_like(emb)
-    L.check(L.load().gsl_loss_tail(_p(logits), _p(labels), N, int(nr), C, _p(emb), _p(proto), 0 if emb is None else emb.shape[1],
-                                   0 if proto is None else proto.shape[0], _p(structure), float(beta), float(BND), float(alpha), float(w_f),
-                                   float(w_r), float(BND_pro), _p(out), _p(dlogits), _p(demb), _stream()), "gsl_loss_tail")
-    return out[0], out[1:9], out[9:14], dlogits, demb
+    L.check(getattr(L.load(), entry)(_p(logits), _p(labels), N, int(nr), C, _p(emb), _p(proto), 0 if emb is None else emb.shape[1],
+                                     0 if proto is None else proto.shape[0], _p(structure), float(beta), float(BND), float(alpha), float(w_f),
+                                     float(w_r), float(BND_pro), _p(out), _p(dlogits), _p(demb), _stream()), entry)
+    return _tail14(out) + (dlogits, demb)
+
+
+def loss_tail(logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro):
+    """The loss section of a single-process step in one launch (gsl_loss_tail): -> (total, meters [8], coefs [5], dlogits, demb or None)."""
+    return _loss_tail("gsl_loss_tail", logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro)
 
 
 def loss_tail_l2(logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro):
     """loss_tail with the l2 prototype distance (gsl_loss_tail_l2; the prototype term is required): same five results."""
     if emb is None or proto is None:
         raise RuntimeError("gslora_hip: loss_tail_l2 needs the embeddings and the prototype table (without a prototype term use loss_tail)")
-    _need(logits, labels, emb, proto, structure)
-    N, C = logits.shape
-    out = torch.empty(14, device=logits.device, dtype=torch.float32)
-    dlogits = torch.empty_like(logits)
-    demb = torch.empty_like(emb)
-    L.check(L.load().gsl_loss_tail_l2(_p(logits), _p(labels), N, int(nr), C, _p(emb), _p(proto), emb.shape[1], proto.shape[0],
-                                      _p(structure), float(beta), float(BND), float(alpha), float(w_f), float(w_r), float(BND_pro),
-                                      _p(out), _p(dlogits), _p(demb), _stream()), "gsl_loss_tail_l2")
-    return out[0], out[1:9], out[9:14], dlogits, demb
+    return _loss_tail("gsl_loss_tail_l2", logits, labels, nr, emb, proto, structure, beta, BND, alpha, w_f, w_r, BND_pro)
 
 
 def loss_combine_pack(pack8, structure, has_proto, beta, BND, alpha, w_f, w_r, BND_pro):
@@ -460,7 +462,7 @@ def loss_combine_pack(pack8, structure, has_proto, beta, BND, alpha, w_f, w_r, B
     L.check(L.load().gsl_loss_combine_pack(_p(pack8), _p(structure), 1 if has_proto else 0, float(beta), float(BND), float(alpha),
                                            float(w_f), float(w_r), float(BND_pro), out.data_ptr(), out.data_ptr() + 4,
                                            out.data_ptr() + 36, _stream()), "gsl_loss_combine_pack")
-    return out[0], out[1:9], out[9:14]
+    return _tail14(out)
 
 
 def cosface_prep(W):
@@ -560,43 +562,41 @@ def ce_bwd(logits, labels, coef, scale, dlogits=None, accumulate=None):
     return dlogits
 
 
-def proto_kl_fwd(emb, labels, proto):
+def _proto_fwd(entry, emb, labels, proto):
+    """gsl_proto_kl_fwd or gsl_proto_l2_fwd (same arguments) -> [1] f32, the sum of the row distances."""
     _need(emb, labels, proto)
     out = torch.empty(1, device=emb.device, dtype=torch.float32)
     ws = torch.empty(emb.shape[0], device=emb.device, dtype=torch.float32)
-    L.check(L.load().gsl_proto_kl_fwd(_p(emb), _p(labels), _p(proto), _p(out), _p(ws), emb.shape[0], emb.shape[1], proto.shape[0],
-                                      _stream()), "gsl_proto_kl_fwd")
+    L.check(getattr(L.load(), entry)(_p(emb), _p(labels), _p(proto), _p(out), _p(ws), emb.shape[0], emb.shape[1], proto.shape[0], _stream()), entry)
     return out
 
 
-def proto_kl_bwd(emb, labels, proto, coef, scale, demb=None, accumulate=None):
+def _proto_bwd(entry, emb, labels, proto, coef, scale, demb, accumulate):
+    """gsl_proto_kl_bwd or gsl_proto_l2_bwd (same arguments); a passed demb is accumulated into unless accumulate says otherwise."""
     _need(emb, labels, proto, coef, demb)
     acc = (demb is not None) if accumulate is None else bool(accumulate)
     if demb is None:
         demb = torch.empty_like(emb)
-    L.check(L.load().gsl_proto_kl_bwd(_p(emb), _p(labels), _p(proto), _p(coef), float(scale), _p(demb), emb.shape[0],
-                                      emb.shape[1], proto.shape[0], 1 if acc else 0, _stream()), "gsl_proto_kl_bwd")
+    L.check(getattr(L.load(), entry)(_p(emb), _p(labels), _p(proto), _p(coef), float(scale), _p(demb), emb.shape[0], emb.shape[1],
+                                     proto.shape[0], 1 if acc else 0, _stream()), entry)
     return demb
+
+
+def proto_kl_fwd(emb, labels, proto):
+    return _proto_fwd("gsl_proto_kl_fwd", emb, labels, proto)
+
+
+def proto_kl_bwd(emb, labels, proto, coef, scale, demb=None, accumulate=None):
+    return _proto_bwd("gsl_proto_kl_bwd", emb, labels, proto, coef, scale, demb, accumulate)
 
 
 def proto_l2_fwd(emb, labels, proto):
     """-> [1] f32: sum_i mean_d (emb[i] - proto[labels[i]])^2 (gsl_proto_l2_fwd)."""
-    _need(emb, labels, proto)
-    out = torch.empty(1, device=emb.device, dtype=torch.float32)
-    ws = torch.empty(emb.shape[0], device=emb.device, dtype=torch.float32)
-    L.check(L.load().gsl_proto_l2_fwd(_p(emb), _p(labels), _p(proto), _p(out), _p(ws), emb.shape[0], emb.shape[1], proto.shape[0],
-                                      _stream()), "gsl_proto_l2_fwd")
-    return out
+    return _proto_fwd("gsl_proto_l2_fwd", emb, labels, proto)
 
 
 def proto_l2_bwd(emb, labels, proto, coef, scale, demb=None, accumulate=None):
-    _need(emb, labels, proto, coef, demb)
-    acc = (demb is not None) if accumulate is None else bool(accumulate)
-    if demb is None:
-        demb = torch.empty_like(emb)
-    L.check(L.load().gsl_proto_l2_bwd(_p(emb), _p(labels), _p(proto), _p(coef), float(scale), _p(demb), emb.shape[0],
-                                      emb.shape[1], proto.shape[0], 1 if acc else 0, _stream()), "gsl_proto_l2_bwd")
-    return demb
+    return _proto_bwd("gsl_proto_l2_bwd", emb, labels, proto, coef, scale, demb, accumulate)
 
 
 def topk_max_k():

@@ -214,6 +214,14 @@ def _arm_overflow_guard(net, optimizer):
     optimizer.overflow_guard = g
 
 
+def _backward_and_update(net, optimizer, roots, grads=None):
+    """The end of a single-process step: gradients from the loss (or from several roots with their upstream gradients), then the update."""
+    optimizer.zero_grad()
+    torch.autograd.backward(roots, grads)
+    _arm_overflow_guard(net, optimizer)
+    optimizer.step()
+
+
 def _model_input(net, x):
     """The reference's inputs.float() — except for a uint8 batch of a model that normalises bytes itself (set_input_norm): that one
     stays uint8 up to the patch gather (a cast here would change its values and put four bytes per sub-pixel back on the bus)."""
@@ -272,7 +280,6 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
                                                    proto_table if use_prototype else None,
                                                    None if structure is None else structure.detach(), beta, BND, alpha,
                                                    w_f, w_r, BND_pro)
-        optimizer.zero_grad()
         roots, grads = [out], [dlogits]
         if use_prototype:
             roots.append(emb)
@@ -280,9 +287,7 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
         if structure is not None:
             roots.append(structure)
             grads.append(coefs[4])
-        torch.autograd.backward(roots, grads)
-        _arm_overflow_guard(net, optimizer)
-        optimizer.step()
+        _backward_and_update(net, optimizer, roots, grads)
         return meters
     if split is not None:
         ce_r_sum, hit_r, ce_f_sum, hit_f = backend.ce_sum_top1_split(split[0], split[2], split[3])
@@ -308,10 +313,7 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
         structure = backend.structure_loss(net, group_type, grad_scale=1.0) if use_structure else None
         total, meters = backend.combine(ce_r_sum, ce_f_sum, kl_f_sum, kl_r_sum, structure, hit_r, hit_f, n_r, n_f, beta, BND, alpha,
                                         w_f, w_r, BND_pro)
-        optimizer.zero_grad()
-        total.backward()
-        _arm_overflow_guard(net, optimizer)
-        optimizer.step()
+        _backward_and_update(net, optimizer, total)
         return meters
     # data parallel: the eight batch sums travel in ONE packed all-reduce, so the hinges see the GLOBAL batch means. Every entry is
     # detached: the collective must not become a node of the autograd graph. The two batch sizes ride along as device scalars.

@@ -1182,10 +1182,14 @@ def test_lora_grad_batch_equals_the_single_reductions(ops):
 
 
 @pytest.mark.parametrize("N,nr,C,D,proto,struct", [(8, 4, 100, 512, True, True), (96, 48, 100, 768, True, False), (37, 5, 12, 128, False, True),
-                                                  (256, 255, 100, 512, True, True)])
+                                                  (256, 255, 100, 512, True, True),
+                                                  # a wave owns two rows, a one-row remain range, a one-element tail of the lane stride; then a full
+                                                  # last register slot with a ragged 4-row block of the stand-alone kernels
+                                                  (17, 1, 65, 65, True, True), (5, 4, 1024, 1024, True, True)])
 def test_loss_tail_equals_the_separate_kernels(ops, N, nr, C, D, proto, struct):
     """gsl_loss_tail (the loss section of a single-process step in one launch) against gsl_ce_fwd / gsl_proto_kl_fwd / gsl_loss_combine /
-    gsl_ce_bwd / gsl_proto_kl_bwd on the two row ranges: the same meters, bit-identical coefficients and gradients, for active and inactive hinges."""
+    gsl_ce_bwd / gsl_proto_kl_bwd on the two row ranges: every output bit-identical (both forms instantiate the same row functions and the
+    same scalar tail, csrc/loss.hip), for active and inactive hinges."""
     logits = (rnd(N, C, seed=1, scale=3.0)).cuda()
     labels = torch.randint(0, C, (N,), generator=torch.Generator().manual_seed(2)).cuda()
     emb = rnd(N, D, seed=3).cuda() if proto else None
@@ -1198,8 +1202,7 @@ def test_loss_tail_equals_the_separate_kernels(ops, N, nr, C, D, proto, struct):
         kf = ops.proto_kl_fwd(emb[nr:], labels[nr:], table)[0] if proto else None
         kr = ops.proto_kl_fwd(emb[:nr], labels[:nr], table)[0] if proto else None
         t0, m0, c0 = ops.loss_combine(cr[0], cf[0], kf, kr, st, cr[1], cf[1], float(nr), float(N - nr), **hyper)
-        # (the scalar tail is compiled twice: an fma contraction may differ in the last bit of the total; coefficients and gradients are exact)
-        assert torch.allclose(total, t0, rtol=3e-7, atol=0) and torch.allclose(meters, m0, rtol=3e-7, atol=0) and torch.equal(coefs, c0)
+        assert torch.equal(total, t0) and torch.equal(meters, m0) and torch.equal(coefs, c0)
         dl0 = torch.empty_like(logits)
         ops.ce_bwd(logits[:nr], labels[:nr], c0[0:1].contiguous(), 1.0, dlogits=dl0[:nr], accumulate=False)
         ops.ce_bwd(logits[nr:], labels[nr:], c0[1:2].contiguous(), 1.0, dlogits=dl0[nr:], accumulate=False)
@@ -1211,6 +1214,54 @@ def test_loss_tail_equals_the_separate_kernels(ops, N, nr, C, D, proto, struct):
             assert torch.equal(de, de0)
         else:
             assert de is None
+
+
+@pytest.mark.parametrize("proto", [True, False])
+def test_loss_combine_equals_loss_combine_pack(ops, proto):
+    """The two stand-alone forms of the scalar tail (pointers to the sums, or the data-parallel pack) fed the same six sums and sizes:
+    all 14 outputs bit-identical, with and without the prototype term, for active and inactive hinges."""
+    n_r, n_f = 5.0, 3.0
+    ce_r, ce_f, kl_f, kl_r, hit_r, hit_f = (torch.tensor(v, device="cuda") for v in (11.37, 7.91, 4.83, 6.29, 4.0, 1.0))
+    st = torch.tensor(13.5, device="cuda")
+    pack = torch.stack([ce_r, ce_f, hit_r, hit_f, torch.tensor(n_r, device="cuda"), torch.tensor(n_f, device="cuda"), kl_f, kl_r])
+    for BND, BND_pro in ((105.0, 50.0), (0.5, 1e-4)):      # hinges active / inactive
+        hyper = dict(beta=0.15, BND=BND, alpha=1e-2, w_f=0.05, w_r=0.1, BND_pro=BND_pro)
+        for structure in (st, None):
+            a = ops.loss_combine(ce_r, ce_f, kl_f if proto else None, kl_r if proto else None, structure, hit_r, hit_f, n_r, n_f, **hyper)
+            b = ops.loss_combine_pack(pack, structure, proto, **hyper)
+            assert all(torch.equal(x, y) for x, y in zip(a, b)) and torch.isfinite(torch.cat([t.reshape(-1) for t in a])).all()
+            assert (a[2][1] != 0) == (BND == 105.0) and (a[2][2] != 0) == (proto and BND_pro == 50.0)
+
+
+def test_losses_beyond_the_register_row_width(ops):
+    """C = D = 1025: one element more than a register row of the one-launch tail holds, so the row functions run their global-memory form
+    over a 17th lane-stride pass. CE, prototype KL and prototype l2 against float64 torch, within the tolerances of test_head_and_losses
+    and tests/test_hip_proto_l2.py::test_proto_l2_fwd_bwd_match_float64."""
+    B, C = 5, 1025
+    logits, emb, table = rnd(B, C, seed=1, scale=3.0).cuda(), rnd(B, C, seed=2).cuda(), rnd(C, C, seed=3).cuda()
+    y = torch.tensor([0, 1024, 64, 960, 1024]).cuda()
+    coef = torch.tensor([0.7], device="cuda")
+    l64 = logits.double().requires_grad_(True)
+    ce = F.cross_entropy(l64, y, reduction="sum")
+    out2 = ops.ce_fwd(logits, y)
+    assert abs(out2[0].item() - ce.item()) < 1e-3 * max(1, ce.item())
+    assert out2[1].item() == (logits.argmax(1) == y).sum().item()
+    (gref,) = torch.autograd.grad(ce * (0.7 / B), l64)
+    dl = ops.ce_bwd(logits, y, coef, 1.0 / B)
+    assert (dl.double() - gref).abs().max() < 2e-5 * max(1.0, gref.abs().max().item())
+    e64 = emb.double().requires_grad_(True)
+    kl_ref = F.kl_div(F.log_softmax(e64, 1), F.log_softmax(table.double()[y], 1), reduction="sum", log_target=True)
+    kl = ops.proto_kl_fwd(emb, y, table)
+    assert abs(kl.item() - kl_ref.item()) < 1e-4 * max(1, abs(kl_ref.item()))
+    (gref,) = torch.autograd.grad(kl_ref * (0.7 / B), e64)
+    de = ops.proto_kl_bwd(emb, y, table, coef, 1.0 / B)
+    assert (de.double() - gref).abs().max() < 2e-5 * max(1.0, gref.abs().max().item())
+    l2_ref = ((e64 - table.double()[y]) ** 2).mean(1).sum()
+    l2 = ops.proto_l2_fwd(emb, y, table)
+    assert abs(l2.item() - l2_ref.item()) <= 1e-6 * abs(l2_ref.item())
+    (gref,) = torch.autograd.grad(l2_ref * (0.7 * 1.5), e64)
+    g = ops.proto_l2_bwd(emb, y, table, coef, 1.5)
+    assert (g.double() - gref).abs().max().item() <= 1e-6 * gref.abs().max().item()
 
 
 @pytest.mark.parametrize("r", [8, 16])
