@@ -16,6 +16,7 @@
 //   stores. gsl_gemm_nt_lora_mulgrad (end of file) is the FFN2-dX GEMM with the two LoRA-gradient reductions of its tiles fused
 //   into the epilogue. What was tried and measured is in profiles/r01_gemm_ab.md and DESIGN.md section 4.
 // f32 path (parity mode): 64x64x16 tile, 4x4 outputs per thread, sequential fmaf over k.
+// f32x3 path (dtype GSL_F32X3): f32 tensors, each product as six bf16 MFMAs on a three-piece split of both operands (gemm_f32x3_mfma_kernel).
 #include <stdlib.h>
 
 #include "gsl_common.h"
@@ -2024,6 +2025,140 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------ f32x3: f32 tensors, f32-accurate products on the bf16 matrix cores (dtype GSL_F32X3)
+// gfx950 has no xf32; the exact-f32 MFMA above runs at 1/16 of the bf16 matrix rate. An f32 value is exactly the sum of three bf16 values,
+//   hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid)       (bf16() = round to nearest even, v_cvt_pk_bf16_f32; both subtractions are exact;
+//   under the FP16_OVFL mode bit that every kernel of this file sets on entry the conversion SATURATES: a finite value that would round up to Inf
+//   becomes the largest finite bf16, so the split is exact up to FLT_MAX — tests/test_hip_f32x3.py plants such values)
+// and the six largest of the nine piece products — hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi — carry the f32 product to about 2^-26 of |a w|
+// (|mid| <= 2^-9 |x|, |lo| <= 2^-18 |x|: the dropped mid.lo, lo.mid, lo.lo are <= 2^-26), below the rounding of the k-ordered fmaf chain itself. Six
+// v_mfma_f32_16x16x32_bf16 replace eight v_mfma_f32_16x16x4_f32 of twice their duration: a ceiling of 16 / 6 = 2.67 x the exact kernel's matrix rate.
+// The result is NOT the fmaf chain bit for bit (the parity goldens hold to their tolerances, not to the bit); it is deterministic: per K tile of 32
+// one accumulator per output takes lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi in that order (small terms first), K tiles ascending over [A1 | A2].
+// Signature, tile, LDS-DMA staging, swizzle and epilogues are gemm_f32_mfma_kernel's: a K tile of 32 floats is one k-step of the bf16 instruction,
+// lane (fr, fc) supplies k = 8 fc .. 8 fc + 7 — the two 16-byte chunks 2 fc, 2 fc + 1 of its row — and splits them in registers (per wave, on the
+// fragments it has just read). The K2 segment (the LoRA up-projection, new every step) is split like the rest.
+// Non-finite operands: a 16-bit MFMA drops the k-group of a NaN operand and clamps Inf (tools/probes/nan_probe.py), so the split — which sees every
+// element — keeps a flag per operand row: x - hi is NaN exactly when x is NaN or Inf (Inf - Inf), and finite otherwise; 0 * (x - hi) is then NaN
+// and +-0 otherwise, and the sum of these over the row's K elements is added to the row's outputs: a non-finite element in row m of A (row n of W)
+// makes output row m (column n) NaN, everything else is untouched.
+#if GSL_HAS_F32
+typedef __attribute__((ext_vector_type(8))) __bf16 x3_bf16x8_t;
+typedef __attribute__((ext_vector_type(4))) uint32_t x3_u32x4_t;
+struct X3Frag { x3_bf16x8_t hi, mid, lo; };
+// One element pair: 13 VALU instructions (3 v_cvt_pk_bf16_f32, 2 + 2 to widen hi and mid again, 4 subtractions, 2 flag FMAs). The subtractions and the
+// flag FMAs are written as instructions: left to the compiler they are SLP-vectorised into v_pk_add_f32 / v_pk_fma_f32 on operand pairs gathered with
+// v_mov (112 moves per K tile) — measured on the QKV shape 1.22 x the exact kernel against 1.41 x in this form, and 1.29 x with the pairs packed by hand
+// (packed f32 VALU beside MFMAs is slower than two scalar instructions): profiles/f32x3.md.
+__device__ __forceinline__ float x3_sub(float a, float b) { float r; asm("v_sub_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ void x3_split2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l, float& nf) {
+  h = pack2bf(x0, x1);
+  const float r0 = x3_sub(x0, __uint_as_float(h << 16)), r1 = x3_sub(x1, __uint_as_float(h & 0xffff0000u));
+  m = pack2bf(r0, r1);
+  const float s0 = x3_sub(r0, __uint_as_float(m << 16)), s1 = x3_sub(r1, __uint_as_float(m & 0xffff0000u));
+  l = pack2bf(s0, s1);
+  asm("v_fmac_f32_e32 %0, 0, %1" : "+v"(nf) : "v"(r0));      // nf += 0 * (x - hi): NaN once x or hi is not finite, +-0 otherwise
+  asm("v_fmac_f32_e32 %0, 0, %1" : "+v"(nf) : "v"(r1));
+}
+// the 8 floats k = 8 fc .. 8 fc + 7 of a row of the swizzled tile -> the three bf16 operands of the row; nf collects the row's non-finite flag
+__device__ __forceinline__ void x3_load_split(const float* tile, int row, int fc, X3Frag& f, float& nf) {
+  const float4 a = *reinterpret_cast<const float4*>(tile + row * FBK + (((2 * fc) ^ (row & 7)) << 2));
+  const float4 b = *reinterpret_cast<const float4*>(tile + row * FBK + (((2 * fc + 1) ^ (row & 7)) << 2));
+  x3_u32x4_t h, m, l;
+  uint32_t th, tm, tl;
+  x3_split2(a.x, a.y, th, tm, tl, nf); h[0] = th; m[0] = tm; l[0] = tl;
+  x3_split2(a.z, a.w, th, tm, tl, nf); h[1] = th; m[1] = tm; l[1] = tl;
+  x3_split2(b.x, b.y, th, tm, tl, nf); h[2] = th; m[2] = tm; l[2] = tl;
+  x3_split2(b.z, b.w, th, tm, tl, nf); h[3] = th; m[3] = tm; l[3] = tl;
+  f.hi = __builtin_bit_cast(x3_bf16x8_t, h); f.mid = __builtin_bit_cast(x3_bf16x8_t, m); f.lo = __builtin_bit_cast(x3_bf16x8_t, l);
+}
+#define GSL_X3_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16      // (not GSL_MFMA16: this kernel means bf16 pieces whatever the file's operand format)
+
+template <int EPI>
+__global__ __launch_bounds__(256) void gemm_f32x3_mfma_kernel(const float* __restrict__ A1, int lda1,
+                                                              const float* __restrict__ W1, int ldw1, int K1,
+                                                              const float* __restrict__ A2, int lda2,
+                                                              const float* __restrict__ W2, int ldw2, int K2, EpiArgs e) {
+  GSL_OP16_KERNEL_ENTRY();
+  resolve_drop(e.drop);
+  __shared__ __attribute__((aligned(16))) float smem[2][2][BM * FBK];      // [buffer][A | W][128 rows x 32 floats] = 64 KB
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int nbn = (e.N + BN - 1) / BN;
+  const int tile = e.remap ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int m0 = (tile / nbn) * BM, n0 = (tile % nbn) * BN;
+  const int nk1 = K1 / FBK, nk = nk1 + K2 / FBK;
+  const int lrow = lane >> 3, lc = lane & 7;
+  auto issue = [&](int kt, int buf) {
+    const float* Ab; const float* Wb; int lda, ldw, k0;
+    if (kt < nk1) { Ab = A1; Wb = W1; lda = lda1; ldw = ldw1; k0 = kt * FBK; }
+    else { Ab = A2; Wb = W2; lda = lda2; ldw = ldw2; k0 = (kt - nk1) * FBK; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int rb = wave * 4 + i;                 // 8-row block: one 1 KB DMA per wave-instruction
+      const int row = rb * 8 + lrow;
+      const int c = lc ^ (row & 7);
+      const int gm = min(m0 + row, e.M - 1), gn = min(n0 + row, e.N - 1);
+      __builtin_amdgcn_global_load_lds((gptr_t)(Ab + (size_t)gm * lda + k0 + c * 4), (lptr_t)(&smem[buf][0][rb * 8 * FBK]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(Wb + (size_t)gn * ldw + k0 + c * 4), (lptr_t)(&smem[buf][1][rb * 8 * FBK]), 16, 0, 0);
+    }
+  };
+  f32x4_t acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float nfa[4] = {0.f, 0.f, 0.f, 0.f}, nfw[4] = {0.f, 0.f, 0.f, 0.f};      // non-finite flags of this lane's A rows (fragment i) and W rows (fragment j)
+  const int fr = lane & 15, fc = lane >> 4;
+  issue(0, 0);
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) { issue(kt + 1, buf ^ 1); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const float* As = smem[buf][0];
+    const float* Ws = smem[buf][1];
+    X3Frag wf[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x3_load_split(Ws, wn * 64 + j * 16 + fr, fc, wf[j], nfw[j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      X3Frag af;
+      x3_load_split(As, wm * 64 + i * 16 + fr, fc, af, nfa[i]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = GSL_X3_MFMA(wf[j].lo, af.hi, acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = GSL_X3_MFMA(wf[j].hi, af.lo, acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = GSL_X3_MFMA(wf[j].mid, af.mid, acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = GSL_X3_MFMA(wf[j].mid, af.hi, acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = GSL_X3_MFMA(wf[j].hi, af.mid, acc[i][j], 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = GSL_X3_MFMA(wf[j].hi, af.hi, acc[i][j], 0, 0, 0);
+    }
+    __builtin_amdgcn_s_barrier();      // every wave is done with this buffer before the next iteration's DMA overwrites it
+  }
+  // the flags of a row: over the four fc lane groups that split its k range (NaN + anything = NaN; +-0 otherwise)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    nfa[i] += __shfl_xor(nfa[i], 16, 64); nfa[i] += __shfl_xor(nfa[i], 32, 64);
+    nfw[i] += __shfl_xor(nfw[i], 16, 64); nfw[i] += __shfl_xor(nfw[i], 32, 64);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = acc[i][j][q] + (nfa[i] + __shfl(nfw[j], fc * 4 + q, 64));      // output column fc * 4 + q of fragment j: W row fc * 4 + q
+      epilogue4<EPI, float>(e, m0 + wm * 64 + i * 16 + fr, n0 + wn * 64 + j * 16 + fc * 4, v);
+    }
+}
+#endif
+
 // Launch knobs. The product library has none: block-id remap on, K rotation off, non-temporal output stores, no stamps, and the
 // tile is chosen from the shape alone. The development build (-DGSL_DEV -> libgslora_hip_dev.so, selected with GSLORA_HIP_LIB) reads
 // the ablation / variant knobs of tools/bench_gemm*.py and tools/probes/ from the environment.
@@ -2238,8 +2373,12 @@ static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int 
       EpiArgs ef = e;
       ef.remap = 1;
       const int nblk = ((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
-      hipLaunchKernelGGL(gemm_f32_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
-                         ldw1, K1, (const float*)A2, lda2, (const float*)W2, ldw2, K2, ef);
+      if (dtype == GSL_F32X3)      // the same tiles with the products on the bf16 matrix cores (three-piece split, six products: the kernel's comment)
+        hipLaunchKernelGGL(gemm_f32x3_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
+                           ldw1, K1, (const float*)A2, lda2, (const float*)W2, ldw2, K2, ef);
+      else
+        hipLaunchKernelGGL(gemm_f32_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
+                           ldw1, K1, (const float*)A2, lda2, (const float*)W2, ldw2, K2, ef);
     } else {
       const int nblk = ((e.M + 63) / 64) * ((e.N + 63) / 64);
       hipLaunchKernelGGL(gemm_f32_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
@@ -2317,7 +2456,7 @@ static int gemm_nt_rows(const void* A1, int lda1, const void* W1, int ldw1, int 
                         const float* bias, const void* res, const void* aux, void* out, void* out2, int ldo,
                         const float* pos, const float* cls, int T, float p_drop, uint64_t seed, uint32_t site,
                         gsl_stream_t s, int mbase) {
-  GSL_CHECK_ARG((GSL_HAS_F32 && dtype == GSL_F32) || dtype == GSL_OP16, "dtype");
+  GSL_CHECK_ARG((GSL_HAS_F32 && (dtype == GSL_F32 || dtype == GSL_F32X3)) || dtype == GSL_OP16, "dtype");
   GSL_CHECK_ARG(M > 0 && N > 0 && (N % 4) == 0, "M>0, N>0, N%4==0");
   GSL_CHECK_ARG(K1 > 0 && (K1 % 64) == 0 && K2 >= 0 && (K2 % 64) == 0, "K1,K2 multiples of 64");
   GSL_CHECK_ARG(A1 && W1 && out && (K2 == 0 || (A2 && W2)), "null operand");
@@ -2333,7 +2472,7 @@ static int gemm_nt_rows(const void* A1, int lda1, const void* W1, int ldw1, int 
   hipStream_t st = as_stream(s);
   switch (epilogue) {
     case GSL_EPI_STORE:
-      if (out2) GSL_CHECK_ARG(dtype != GSL_F32 && N >= 16 && N <= 128 && !bias, "STORE with out2 (compact [M,16] copy of columns 0..15): 16-bit operands, 16 <= N <= 128, no bias");
+      if (out2) GSL_CHECK_ARG(dtype == GSL_OP16 && N >= 16 && N <= 128 && !bias, "STORE with out2 (compact [M,16] copy of columns 0..15): 16-bit operands, 16 <= N <= 128, no bias");
       return launch_gemm<GSL_EPI_STORE>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
     case GSL_EPI_STORE_F32: return launch_gemm<GSL_EPI_STORE_F32>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
     case GSL_EPI_STORE_QKV_HM_LN:

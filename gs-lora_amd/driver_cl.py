@@ -78,7 +78,7 @@ def get_args(argv=None):
                    help="distance of the prototype term (get_prototype_loss, engine_cl.py:571-603): kl | l2")
     p.add_argument("--lora_rank", type=int, default=8)
     p.add_argument("--dropout", type=float, default=0.1)
-    p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 (16-bit MFMA operands) | fp32 (parity mode)")
+    p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 (16-bit MFMA operands) | fp32 (parity mode) | fp32x3 (f32 tensors, GEMMs as three bf16 pieces on the bf16 matrix cores: f32 accuracy)")
     p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
     p.add_argument("-n", "--net", default="VIT", choices=["VIT", "VITs"],
                    help="backbone (util/args.py -n): ViT_face, or ViTs_face with 12 x 12 windows at stride 8, pad 4 (train_own_forget_cl.py:222-236)")

@@ -107,7 +107,8 @@ def train_one_epoch(model: torch.nn.Module, dataloader_forget, dataloader_remain
             meters["losses_prototype_remain"])
 
 
-# dtype eval_data() evaluates in: "fp32" (default: the reference's arithmetic), "bf16", or "model" (the model's own training mode)
+# dtype eval_data() evaluates in: "fp32" (default: the reference's arithmetic), "fp32x3" (f32 tensors, the GEMMs on the bf16 matrix cores at f32
+# accuracy), "fp16" / "bf16", or "model" (the model's own training mode)
 EVAL_DTYPE = os.environ.get("GSLORA_EVAL_DTYPE", "fp32").lower()
 _EVAL_SAME = ("model", "train", "same", "")
 if EVAL_DTYPE not in _EVAL_SAME:      # validated at import (a typo must not surface at the first evaluate(), an eval interval into the run)
@@ -188,7 +189,7 @@ def eval_data(model, dataloader, device, mode: str, batch: int = 0):
     # forward-only on the test set; its cost is in bench.py's `--eval` leg. GSLORA_EVAL_DTYPE=model evaluates in the model's training
     # mode instead (bf16 speed), =bf16 / =fp32 force a mode.
     net = _unwrap(model)
-    eval_dt, train_dt = EVAL_DTYPE, getattr(net, "compute_dtype", None)
+    eval_dt, train_dt = EVAL_DTYPE, util._compute_mode_of(net)      # (the mode NAME: the torch dtype alone would bring an 'fp32x3' model back as 'fp32')
     if eval_dt in _EVAL_SAME or not hasattr(net, "set_compute_dtype"):
         eval_dt = None
     if eval_dt:
@@ -222,7 +223,7 @@ def eval_data_per_class(model, dataloader, device, mode: str, batch: int = 0, nu
     from gslora_hip import ops
     model.eval()
     net = _unwrap(model)
-    eval_dt, train_dt = util._eval_dtype_of(net), getattr(net, "compute_dtype", None)
+    eval_dt, train_dt = util._eval_dtype_of(net), util._compute_mode_of(net)
     if eval_dt:
         net.set_compute_dtype(eval_dt)
     stats, total = None, 0

@@ -46,6 +46,60 @@ def code(dtype):
         raise RuntimeError(f"gslora_hip: unsupported compute dtype {dtype}")
 
 
+F32_MODES = (None, "x3")      # how a GEMM multiplies float32 tensors: None = the exact-f32 kernels, "x3" = GSL_F32X3
+
+
+def gemm_code(dtype, f32_mode=None):
+    """The gsl_dtype of a gsl_gemm_nt call on tensors of `dtype` under `f32_mode`."""
+    if f32_mode is None:
+        return code(dtype)
+    if f32_mode != "x3":
+        raise ValueError(f"gslora_hip: unknown f32_mode {f32_mode!r}; allowed: {F32_MODES}")
+    if dtype != torch.float32:
+        raise RuntimeError(f"gslora_hip: f32_mode='x3' multiplies float32 tensors, not {dtype} (the 16-bit modes are matrix-core modes already)")
+    return L.F32X3
+
+
+def f32x3_split_reference(x):
+    """The split rule of GSL_F32X3 (include/gslora_hip.h, gsl_dtype), restated on the host: x (float32 numpy array or CPU tensor) ->
+    (hi, mid, lo), float32 arrays whose values are bf16-representable, with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) and
+    bf16() = round to nearest even, saturating (a finite value that would round up to Inf, |x| >= 2^128 - 2^119, becomes the largest finite bf16:
+    what the kernel's conversion does under the FP16_OVFL mode bit). Both subtractions are exact in f32, and hi + mid + lo == x bit for bit for 0 and
+    every finite |x| >= 2^-110 (smaller magnitudes: to 2^-134 absolute, bf16's denormal grid). Inf and NaN stay themselves in hi, and mid = x - hi is
+    then NaN — the flag the kernel keeps per operand row."""
+    import numpy as np
+    x = np.ascontiguousarray(x.numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float32)
+
+    def bf16_rne(v):
+        u = v.view(np.uint32).astype(np.uint64)
+        r = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32)
+        r = np.where(np.isfinite(v) & ((r & 0x7FFFFFFF) == 0x7F800000), (r & 0x80000000) | 0x7F7F0000, r)              # finite overflow saturates
+        r = np.where(np.isnan(v), (v.view(np.uint32) | np.uint32(0x00400000)) & np.uint32(0xFFFF0000), r)      # a NaN stays a (quiet) NaN
+        return r.astype(np.uint32).view(np.float32)
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        hi = bf16_rne(x)
+        r1 = (x - hi).astype(np.float32)
+        mid = bf16_rne(r1)
+        lo = bf16_rne((r1 - mid).astype(np.float32))
+    return hi, mid, lo
+
+
+# the piece products GSL_F32X3 adds up, (piece of A, piece of W), and the five-product set without mid * mid (the yardstick of the tests: one product
+# too few is visible at f32 accuracy)
+F32X3_PRODUCTS = (("hi", "hi"), ("hi", "mid"), ("mid", "hi"), ("mid", "mid"), ("hi", "lo"), ("lo", "hi"))
+F32X3_FIVE = tuple(p for p in F32X3_PRODUCTS if p != ("mid", "mid"))
+
+
+def f32x3_product_reference(A, W, products=F32X3_PRODUCTS):
+    """Host emulation of a piece-product set: sum over `products` of piece(A) @ piece(W)^T, accumulated in float64 (what the choice of products
+    costs, without what an f32 accumulator adds). A [M, K], W [N, K] float32 -> float64 numpy [M, N]."""
+    import numpy as np
+    pa = dict(zip(("hi", "mid", "lo"), (t.astype(np.float64) for t in f32x3_split_reference(A))))
+    pw = dict(zip(("hi", "mid", "lo"), (t.astype(np.float64) for t in f32x3_split_reference(W))))
+    return sum(pa[a] @ pw[w].T for a, w in products)
+
+
 # ---- uint8 image batches (gsl_patchify_u8 / gsl_unfold_patches_u8): ToTensor() + Normalize(mean, std) happen inside the gather
 # named (mean, std) pairs: the face drivers use ToTensor() alone, the ImageNet-100 driver the ImageNet constants
 INPUT_NORM_TOTENSOR = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
@@ -196,7 +250,9 @@ def _gemm_shape(A, W, *a, A2=None, **kw):
 
 @_profiled(None, _gemm_shape)
 def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, bias=None, res=None, aux=None, out2=None,
-            pos=None, cls=None, T=0, p_drop=0.0, seed=0, site=0, tag=None):
+            pos=None, cls=None, T=0, p_drop=0.0, seed=0, site=0, tag=None, f32_mode=None):
+    """f32_mode: None, or "x3" — float32 tensors only: the products as three bf16 pieces per operand on the bf16 matrix cores (GSL_F32X3;
+    f32x3_split_reference states the split). Same tensors, epilogues and dropout masks as the exact-f32 call."""
     _need(A2, W2, bias, aux, out2, pos, cls)
     _need(A1, W1, out, res, rows_ok=True)      # lda1 / ldw1 / ldo travel with the call (res shares ldo with out)
     if res is not None and res.shape[0] > 1 and res.stride(0) != out.stride(0):
@@ -205,7 +261,7 @@ def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, b
     N = W1.shape[0]
     K2 = 0 if A2 is None else A2.shape[1]
     L.check(L.load().gsl_gemm_nt(_p(A1), A1.stride(0), _p(W1), W1.stride(0), K1, _p(A2), 0 if A2 is None else A2.stride(0),
-                                 _p(W2), 0 if W2 is None else W2.stride(0), K2, M, N, code(A1.dtype), epilogue, float(alpha),
+                                 _p(W2), 0 if W2 is None else W2.stride(0), K2, M, N, gemm_code(A1.dtype, f32_mode), epilogue, float(alpha),
                                  _p(bias), _p(res), _p(aux), _p(out), _p(out2), out.stride(0), _p(pos), _p(cls), int(T),
                                  float(p_drop), int(seed), int(site), _stream()), "gsl_gemm_nt")
     return out

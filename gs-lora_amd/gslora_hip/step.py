@@ -419,7 +419,7 @@ class GraphedStep:
         # optimizer's betas / eps / weight decay and the dropout rates (lr and the step count are read from device memory)
         hyper = tuple((g["betas"], g["eps"], g["weight_decay"]) for g in self.optimizer.param_groups)
         drop = (getattr(self.net, "dropout_p", None), getattr(self.net, "emb_dropout_p", None))
-        return (tuple(x_r.shape), tuple(x_f.shape), x_r.dtype, y_r.dtype, self.net.training, self.net.compute_dtype,
+        return (tuple(x_r.shape), tuple(x_f.shape), x_r.dtype, y_r.dtype, self.net.training, self.net.compute_dtype, getattr(self.net, "gemm_mode", None),
                 sum(p._version for p in self._frozen), None if pt is None else (pt.data_ptr(), tuple(pt.shape)),
                 tuple(sorted((k, v) for k, v in kw.items() if k != "proto_table")), hyper, drop, getattr(self.net, "input_norm", None),
                 tuple(x.stride() for x in (x_r, x_f)))      # (the normalisation and the byte layout are baked into the captured gathers)

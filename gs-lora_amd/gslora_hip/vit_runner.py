@@ -195,10 +195,11 @@ class _Pass:
     """What every step of one pass reads, computed once by the forward; the backward of the same pass goes on with it (`saved["ctx"]`)
     and adds its own state: the loss scale and its overflow guard, the gradient views, the deferred LoRA-gradient reductions."""
     __slots__ = ("sp", "dt", "xdt", "epi_res", "epi_patch", "B", "T", "D", "H", "M", "dev", "seed", "sflag", "p_drop", "p_emb", "r",
-                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending")
+                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending", "f32_mode")
 
-    def __init__(self, sp, dt, B, dev, training, seed, sflag, save):
+    def __init__(self, sp, dt, B, dev, training, seed, sflag, save, f32_mode=None):
         self.sp, self.dt, self.dev, self.seed, self.sflag, self.save = sp, dt, dev, seed, sflag, save
+        self.f32_mode = f32_mode if dt == torch.float32 else None      # "x3" (the 'fp32x3' mode): every GEMM of the pass multiplies on the bf16 matrix cores
         self.B, self.T, self.D, self.H, self.M = B, sp.num_tokens, sp.dim, sp.heads, B * sp.num_tokens
         self.p_drop = sp.dropout_p if training else 0.0
         self.p_emb = sp.emb_dropout_p if training else 0.0
@@ -210,6 +211,12 @@ class _Pass:
         self.xdt = (torch.float16 if xf16 else torch.bfloat16) if xbf else torch.float32            # dtype of the residual stream
         self.epi_res = _res_epilogue(self.xdt)
         self.epi_patch = (L.EPI_PATCH_F16 if xf16 else L.EPI_PATCH_BF16) if xbf else L.EPI_PATCH
+
+
+    def gemm(self, *a, **kw):
+        """ops.gemm_nt in the pass's GEMM mode: every GEMM of the forward and the backward goes through here. (Attention, LayerNorm, head, losses,
+        LoRA-gradient reductions and AdamW have no such mode: in 'fp32x3' they are the f32 kernels of 'fp32'.)"""
+        return ops.gemm_nt(*a, f32_mode=self.f32_mode, **kw)
 
 
 def _cls_rows(c, t, w):
@@ -505,7 +512,7 @@ class ViTRunner:
             seed, sflag = self.seed_dev.data_ptr(), L.SEED_ON_DEVICE
         else:
             seed, sflag = (self.drop_seed << 20) + self.drop_calls, 0
-        c = _Pass(sp, m.compute_dtype, sum(t.shape[0] for t in parts), img.device, m.training, seed, sflag, save)
+        c = _Pass(sp, m.compute_dtype, sum(t.shape[0] for t in parts), img.device, m.training, seed, sflag, save, getattr(m, "gemm_mode", None))
         self.ensure_bucket(sp)
         if c.r > 0 and not c.attn_site:
             self.refresh_lora_packs(c.dt)
@@ -527,7 +534,7 @@ class ViTRunner:
             patches = ops.patchify(parts, sp.patch_size, dt, table=u8tab)
             pw = self.w_conv("pe", sp.patch_w, dt) if sp.patch_is_conv else self.w("pe", sp.patch_w, dt)
         x = torch.empty(c.M, c.D, device=c.dev, dtype=c.xdt)
-        ops.gemm_nt(patches, pw, x, epilogue=c.epi_patch, bias=sp.patch_b.detach(), pos=sp.pos.detach()[0, :c.T].contiguous(),
+        c.gemm(patches, pw, x, epilogue=c.epi_patch, bias=sp.patch_b.detach(), pos=sp.pos.detach()[0, :c.T].contiguous(),
                     cls=sp.cls.detach().reshape(-1), T=c.T, p_drop=c.p_emb, seed=c.seed, site=SITE_EMB | c.sflag)
         return x
 
@@ -550,7 +557,7 @@ class ViTRunner:
         if c.attn_site and not blk.qkv_lora.merged:      # q / k / v adapters: one block-diagonal LoRA K segment
             qo = self.qkv_lora_ops(i, blk.qkv_lora, dt)
             uq = torch.empty(M, PADK, device=c.dev, dtype=dt)
-            ops.gemm_nt(xn, qo["A_rows"], uq, alpha=c.s_lora)
+            c.gemm(xn, qo["A_rows"], uq, alpha=c.s_lora)
             lora = dict(A2=uq, W2=qo["Bblk"])
         # operand, weight, bias and epilogue: the stream itself with W' = W * gamma, d = W beta (+ bias) and the row statistics finishing
         # the normalisation in the epilogue (aux = rowsum(W')), or LayerNorm 1's output with the weight as it is
@@ -561,15 +568,15 @@ class ViTRunner:
         if not qsplit:
             hm = 1 if (QKV_HEAD_MAJOR and dt in OP16) else 0
             epi = (L.EPI_STORE_QKV_HM_LN if hm else L.EPI_STORE_LN) if fold else (L.EPI_STORE_QKV_HM if hm else L.EPI_STORE)
-            ops.gemm_nt(a, w, qkv, epilogue=epi, T=T, aux=cw, bias=b, **lora, **ln)
+            c.gemm(a, w, qkv, epilogue=epi, T=T, aux=cw, bias=b, **lora, **ln)
             return qkv, None, uq, hm
         # K and V for every token, Q for the cls rows only: rows inner .. 3*inner of the fused weight (and of W', c, d) are K | V
         rows = lambda t, s: None if t is None else t[s]
         kv, q = slice(inner, None), slice(None, inner)
         epi = L.EPI_STORE_LN if fold else L.EPI_STORE
-        ops.gemm_nt(a, w[kv], qkv, epilogue=epi, aux=rows(cw, kv), bias=rows(b, kv), **ln)
+        c.gemm(a, w[kv], qkv, epilogue=epi, aux=rows(cw, kv), bias=rows(b, kv), **ln)
         q_cls = torch.empty(B, inner, device=c.dev, dtype=dt)
-        ops.gemm_nt(a.view(B, T * D)[:, :D], w[q], q_cls, epilogue=epi, T=T if fold else 0,      # A = the cls rows, T*D apart (T: their statistics, T apart)
+        c.gemm(a.view(B, T * D)[:, :D], w[q], q_cls, epilogue=epi, T=T if fold else 0,      # A = the cls rows, T*D apart (T: their statistics, T apart)
                     aux=rows(cw, q), bias=rows(b, q), **ln)
         return qkv, q_cls, None, 2
 
@@ -583,7 +590,7 @@ class ViTRunner:
             o, lse = ops.attention_fwd(qkv, B, T, c.H, sp.attn_scale, layout=hm)
             xres = x
         x1 = torch.empty(xres.shape[0], D, device=c.dev, dtype=c.xdt)
-        ops.gemm_nt(o, self.w(f"wo{i}", blk.out.weight, c.dt), x1, epilogue=c.epi_res,
+        c.gemm(o, self.w(f"wo{i}", blk.out.weight, c.dt), x1, epilogue=c.epi_res,
                     bias=blk.out.bias.detach(), res=xres, p_drop=c.p_drop, seed=c.seed, site=(4 * i) | c.sflag)
         return o, lse, x1
 
@@ -626,15 +633,15 @@ class ViTRunner:
                     # (16-bit modes: the GEMM also writes u1's first 16 columns as a compact [M, 16] tensor — the operand form the
                     #  gradient-fused FFN2-dX epilogue reads 32 rows of with one contiguous 1 KB load; rank <= 16)
                     u1c = torch.empty(Mr, 16, device=dev, dtype=dt) if (save and dt in OP16 and r <= 16 and Mr >= INK_MIN_ROWS) else None
-                    ops.gemm_nt(xn2, self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), u1, alpha=s_lora, out2=u1c)
-                ops.gemm_nt(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, A2=u1,
+                    c.gemm(xn2, self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), u1, alpha=s_lora, out2=u1c)
+                c.gemm(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, A2=u1,
                             W2=self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols", dt), bias=l1.bias.detach(), out2=gp,
                             p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
             u2 = torch.empty(Mr, PADK, device=dev, dtype=dt)
             if not self.lora_in_kernel(dt, Mr, D):
-                ops.gemm_nt(h, self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows", dt), u2, alpha=s_lora)
+                c.gemm(h, self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows", dt), u2, alpha=s_lora)
         else:
-            ops.gemm_nt(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, bias=l1.bias.detach(),
+            c.gemm(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, bias=l1.bias.detach(),
                         out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag)
         x2 = torch.empty(Mr, D, device=dev, dtype=c.xdt)
         if lora_on and self.lora_in_kernel(dt, Mr, D):
@@ -642,7 +649,7 @@ class ViTRunner:
                              self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols32", dt), s_lora, u2, x2, epilogue=c.epi_res,
                              bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
         else:
-            ops.gemm_nt(h, self.w(f"w2_{i}", l2.weight, dt), x2, epilogue=c.epi_res, A2=u2,
+            c.gemm(h, self.w(f"w2_{i}", l2.weight, dt), x2, epilogue=c.epi_res, A2=u2,
                         W2=self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols", dt) if lora_on else None,
                         bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
         return x2, (dict(mean2=mean2, rstd2=rstd2, xn2=xn2, u1=u1, u1c=u1c, h=h, gp=gp, u2=u2, lora_on=lora_on) if save else None)
@@ -702,7 +709,7 @@ class ViTRunner:
             del dxn2
             # ---- attention sub-layer: x1 = x + drop(Wo o + bo) -------------------------------------
             d_o = torch.empty(dx1b.shape[0], c.H * 64, device=c.dev, dtype=c.dt)
-            ops.gemm_nt(dx1b, self.wT(f"wo{i}", blk.out.weight, c.dt), d_o)
+            c.gemm(dx1b, self.wT(f"wo{i}", blk.out.weight, c.dt), d_o)
             if c.attn_site:
                 dqkv = self._bwd_attention(c, st, d_o, sparse)
                 del d_o, dx1b
@@ -796,8 +803,8 @@ class ViTRunner:
             ops.gemm_nt_lora(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
                              self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, epilogue=epi_mul, aux=gp, p_drop=p_drop)
         else:
-            ops.gemm_nt(dyb, self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows", dt), v2, alpha=s_lora)
-            ops.gemm_nt(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=epi_mul, A2=v2,
+            c.gemm(dyb, self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows", dt), v2, alpha=s_lora)
+            c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=epi_mul, A2=v2,
                         W2=self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols", dt), aux=gp, p_drop=p_drop)
         self._lgrad(c, dyb, u2, gv[id(l2.lora_B)], r, 1, r)                        # dB2[c, j]
         if not fused_grads:
@@ -809,7 +816,7 @@ class ViTRunner:
             ops.gemm_nt_lora(da, self.wT(f"w1_{i}", l1.weight, dt), self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows16", dt),
                              self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols32", dt), s_lora, v1, dxn2)
         else:
-            ops.gemm_nt(da, self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows", dt), v1, alpha=s_lora)
+            c.gemm(da, self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows", dt), v1, alpha=s_lora)
         if not fused_grads:
             self._lgrad(c, da, u1, gv[id(l1.lora_B)], r, 1, r)                     # dB1[hid, j]
         self._lgrad(c, xn2, v1, gv[id(l1.lora_A)], 1, D, r)                        # dA1[j, c]
@@ -819,7 +826,7 @@ class ViTRunner:
             return None
         if dxn2 is None:
             dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
-            ops.gemm_nt(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2, A2=v1,
+            c.gemm(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2, A2=v1,
                         W2=self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols", dt))
         return dxn2
 
@@ -831,10 +838,10 @@ class ViTRunner:
         mlp = l1.weight.shape[0]
         gp = _gp_rows(c, st["gp"], mlp) if gather else st["gp"]
         da = torch.empty(dyb.shape[0], mlp, device=c.dev, dtype=dt)
-        ops.gemm_nt(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
+        c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
                     p_drop=c.p_drop)
         dxn2 = torch.empty(dyb.shape[0], c.D, device=c.dev, dtype=dt)
-        ops.gemm_nt(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
+        c.gemm(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
         return dxn2
 
     def _bwd_ln2(self, c, i, blk, st, dxn2, dx, gather):
@@ -859,12 +866,12 @@ class ViTRunner:
         dqkv = self._bwd_attention(c, st, d_o, sparse)
         wt = self.wT(f"qkv{i}", blk.qkv_w, dt)                         # [dim, 3*inner]
         if st["q_cls"] is None:
-            ops.gemm_nt(dqkv, wt, dxn1)
+            c.gemm(dqkv, wt, dxn1)
         else:      # Q was projected for the cls rows only: dX contracts over K | V, the cls rows get dQ W_q on top
             dkv, dq_cls = dqkv
-            ops.gemm_nt(dkv, wt[:, inner:], dxn1)
+            c.gemm(dkv, wt[:, inner:], dxn1)
             rows = dxn1.view(c.B, c.T * D)[:, :D]                      # the cls rows of dxn1, T*D apart: updated in place
-            ops.gemm_nt(dq_cls, wt[:, :inner], rows, epilogue=_res_epilogue(dt), bias=self._zeros(D, c.dev), res=rows)
+            c.gemm(dq_cls, wt[:, :inner], rows, epilogue=_res_epilogue(dt), bias=self._zeros(D, c.dev), res=rows)
         return dxn1
 
     def _bwd_qkv_lora(self, c, i, blk, st, dqkv):
@@ -873,7 +880,7 @@ class ViTRunner:
         dt, D, r, ml = c.dt, c.D, c.r, blk.qkv_lora
         qo = self.qkv_lora_ops(i, ml, dt)
         v = torch.empty(c.M, PADK, device=c.dev, dtype=dt)
-        ops.gemm_nt(dqkv, qo["BblkT"], v, alpha=c.s_lora)                      # v[:, g*r+j] = s * dqkv_g . B_g[:, j]
+        c.gemm(dqkv, qo["BblkT"], v, alpha=c.s_lora)                      # v[:, g*r+j] = s * dqkv_g . B_g[:, j]
         ng, inner = len(ml.enable_lora), c.H * 64
         gA, gB = c.gv[id(ml.lora_A)], c.gv[id(ml.lora_B)]
         for g in range(ng):
@@ -883,5 +890,5 @@ class ViTRunner:
         if i == 0:
             return None
         dxn1 = torch.empty(c.M, D, device=c.dev, dtype=dt)
-        ops.gemm_nt(dqkv, self.wT(f"qkv{i}", blk.qkv_w, dt), dxn1, A2=v, W2=qo["AT"])
+        c.gemm(dqkv, self.wT(f"qkv{i}", blk.qkv_w, dt), dxn1, A2=v, W2=qo["AT"])
         return dxn1

@@ -137,6 +137,12 @@ def _eval_dtype_of(net):
     return engine_cl.EVAL_DTYPE
 
 
+def _compute_mode_of(net):
+    """What set_compute_dtype takes to bring `net` back to its current mode after an evaluation in another one: the mode's name ('fp16' | 'bf16' |
+    'fp32' | 'fp32x3') where the model has one — its torch dtype cannot tell 'fp32x3' from 'fp32' — else the torch dtype (None: no switch)."""
+    return getattr(net, "compute_mode", None) or getattr(net, "compute_dtype", None)
+
+
 def pair_embeddings(device, embedding_size, batch_size, backbone, data_set):
     """The embedding pass of perform_val (reference :187-203): data_set = [images, flipped images], each [2P, C, H, W] (float, or uint8
     bytes for a model that was given set_input_norm). Batches of batch_size with the ragged tail; the original and the flipped batch of
@@ -184,7 +190,7 @@ def perform_val(multi_gpu, device, embedding_size, batch_size, backbone, data_se
     backbone = backbone.to(device)
     verification.fold_bounds(len(issame), nrof_folds)      # argument errors before any GPU work
     was_training = backbone.training
-    eval_dt, own_dt = _eval_dtype_of(backbone), getattr(backbone, "compute_dtype", None)
+    eval_dt, own_dt = _eval_dtype_of(backbone), _compute_mode_of(backbone)
     backbone.eval()
     if eval_dt:
         backbone.set_compute_dtype(eval_dt)

@@ -108,7 +108,7 @@ class ModifiedViT(HipModelMixin, nn.Module):
         self.class_token = vit_model.class_token
         self.encoder = vit_model.encoder
         self.heads = vit_model.heads
-        self.compute_dtype = compute_dtype_of(os.environ.get("GSLORA_DTYPE", DEFAULT_DTYPE))
+        self.set_compute_dtype(os.environ.get("GSLORA_DTYPE", DEFAULT_DTYPE))
         self._runner = None
         self.hip_spec()      # validate the geometry once, loudly
 

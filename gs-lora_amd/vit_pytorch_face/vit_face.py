@@ -26,16 +26,35 @@ _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp16": torch.flo
            "fp32": torch.float32, "f32": torch.float32, "float32": torch.float32}
 
 
+# "fp32x3": float32 tensors and kernels like "fp32", with the GEMMs' products on the bf16 matrix cores (GSL_F32X3: three bf16 pieces per operand, six
+# products, f32-accurate — include/gslora_hip.h). The torch dtype of the mode is float32; the GEMM mode travels beside it (gemm_mode_of / compute_mode).
+_GEMM_MODES = {"fp32x3": "x3", "f32x3": "x3", "float32x3": "x3"}
+_MODE_NAMES = {torch.float16: "fp16", torch.bfloat16: "bf16", torch.float32: "fp32"}
+
+
 def compute_dtype_of(name):
-    """'fp16' | 'bf16' | 'fp32' (and their aliases) or a torch dtype -> torch dtype; ValueError lists the allowed names."""
+    """'fp16' | 'bf16' | 'fp32' | 'fp32x3' (and their aliases) or a torch dtype -> torch dtype ('fp32x3' is torch.float32: gemm_mode_of has the
+    rest); ValueError lists the allowed names."""
     if not isinstance(name, str):
         if name in (torch.float32, torch.bfloat16, torch.float16):
             return name
         raise ValueError(f"gs-lora_amd: compute dtype must be torch.float32 / bfloat16 / float16, not {name!r}")
+    if name.lower() in _GEMM_MODES:
+        return torch.float32
     try:
         return _DTYPES[name.lower()]
     except KeyError:
-        raise ValueError(f"gs-lora_amd: unknown compute dtype {name!r}; allowed: {sorted(_DTYPES)}") from None
+        raise ValueError(f"gs-lora_amd: unknown compute dtype {name!r}; allowed: {sorted(_DTYPES) + sorted(_GEMM_MODES)}") from None
+
+
+def gemm_mode_of(name):
+    """The f32_mode of gslora_hip.ops.gemm_nt that a compute-dtype name selects: "x3" for 'fp32x3', None for every other name or torch dtype."""
+    return _GEMM_MODES.get(name.lower()) if isinstance(name, str) else None
+
+
+def compute_mode_name(dtype, gemm_mode=None):
+    """(torch dtype, f32_mode) -> 'fp16' | 'bf16' | 'fp32' | 'fp32x3': the name that set_compute_dtype takes back."""
+    return "fp32x3" if (dtype == torch.float32 and gemm_mode == "x3") else _MODE_NAMES[dtype]
 
 
 class CosFace(nn.Module):
@@ -195,14 +214,22 @@ class HipModelMixin:
     """Shared by the model families that run on ViTRunner (ViT_face, ModifiedViT): compute-dtype switch, the lazily built
     runner / flat LoRA bucket, and the one-autograd-node call."""
     _runner = None
+    gemm_mode = None                # f32_mode of the GEMMs (gslora_hip.ops.gemm_nt): "x3" in the 'fp32x3' mode, None otherwise
     input_norm = None               # (mean, std) once set_input_norm() was called: uint8 batches are raw bytes normalised in the patch gather
     accepts_batch_tuple = True      # forward(img) also takes a tuple of image batches, processed as one batch (gslora_hip.step)
 
     def set_compute_dtype(self, name):
         """'fp16' / 'bf16' (speed: 16-bit MFMA operands of that format, f32 accumulate; fp16 runs its backward on loss-scaled gradients)
-        or 'fp32' (parity: exact-f32 kernels)."""
-        self.compute_dtype = compute_dtype_of(name)
+        or 'fp32' (parity: exact-f32 kernels), or 'fp32x3' (float32 tensors and kernels as 'fp32', the GEMMs on the bf16 matrix cores at f32
+        accuracy: compute_dtype is torch.float32, gemm_mode "x3"). A torch dtype selects its plain mode."""
+        self.compute_dtype, self.gemm_mode = compute_dtype_of(name), gemm_mode_of(name)
         return self
+
+    @property
+    def compute_mode(self):
+        """'fp16' | 'bf16' | 'fp32' | 'fp32x3': the name of the current mode. Code that switches the mode for a while (the evaluations) saves
+        THIS and hands it back to set_compute_dtype — compute_dtype alone would turn an 'fp32x3' model into 'fp32'."""
+        return compute_mode_name(self.compute_dtype, self.gemm_mode)
 
     def set_input_norm(self, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0)):
         """Declare that uint8 batches are raw image bytes, to be normalised as the dataset transform ToTensor() + Normalize(mean, std)
@@ -301,7 +328,7 @@ class ViT_face(HipModelMixin, nn.Module):
         self.lora_pos = lora_pos
         self.attn_scale = dim ** -0.5
         self.dropout_p, self.emb_dropout_p = float(dropout), float(emb_dropout)
-        self.compute_dtype = compute_dtype_of(os.environ.get("GSLORA_DTYPE", DEFAULT_DTYPE))
+        self.set_compute_dtype(os.environ.get("GSLORA_DTYPE", DEFAULT_DTYPE))
         self._runner = None
 
     # ---- helpers for the runner -------------------------------------------------------------

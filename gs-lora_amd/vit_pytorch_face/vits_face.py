@@ -69,7 +69,7 @@ class ViTs_face(HipModelMixin, nn.Module):
         self.lora_pos = "FFN"      # the reference's ViTs attention has no lora_pos: FFN adapters only
         self.attn_scale = dim ** -0.5
         self.dropout_p, self.emb_dropout_p = float(dropout), float(emb_dropout)
-        self.compute_dtype = compute_dtype_of(os.environ.get("GSLORA_DTYPE", DEFAULT_DTYPE))
+        self.set_compute_dtype(os.environ.get("GSLORA_DTYPE", DEFAULT_DTYPE))
         self._runner = None
 
     # ---- helpers for the runner (ViT_face's: the module tree behind the patch stage is the same) ----------------------------------

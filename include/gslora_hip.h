@@ -35,7 +35,23 @@ typedef void* gsl_stream_t;
  * an 11-bit significand instead of 8. Activations saturate at +-65504 on store (NaN / Inf stay visible); the backward runs on gradients
  * multiplied by a power-of-two loss scale chosen on the device by gsl_head_bwd (gscale = {S, 1/S}) which the LoRA-gradient reductions
  * divide out again, exactly. As an x_dtype it is also the forward residual stream format of the GSL_BF16 mode (round 4). */
-enum gsl_dtype { GSL_F32 = 0, GSL_BF16 = 1, GSL_F16 = 2 };
+/* GSL_F32X3: a third way to compute on f32 tensors, accepted by gsl_gemm_nt ONLY (every other entry point rejects it with GSL_ERR_ARG). All
+ * tensors are f32 exactly as for GSL_F32 — same shapes, epilogues and dropout masks — but the products run on the bf16 matrix cores at f32
+ * accuracy (gfx950 has no xf32; the exact-f32 MFMA runs at 1/16 of the bf16 rate):
+ *  - split rule: every operand element x is split in registers into three bf16 pieces, hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid),
+ *    bf16() = ROUND TO NEAREST EVEN, SATURATING: a finite value that would round up to Inf (|x| >= 2^128 - 2^119, f32 bits 0x7f7f8000) becomes
+ *    the largest finite bf16 instead (the kernel runs with the wave's FP16_OVFL mode bit set, which governs v_cvt_pk_bf16_f32 too; Inf and NaN
+ *    stay Inf and NaN). Both subtractions are exact and hi + mid + lo == x bit for bit for 0 and every finite |x| >= 2^-110, the largest finite
+ *    values included; below 2^-110 the last piece can fall under bf16's denormal grid of 2^-133, an absolute error <= 2^-134 per element;
+ *  - product set: hi*hi, hi*mid, mid*hi, mid*mid, hi*lo, lo*hi (six bf16 MFMAs per K tile of 32, f32 accumulate). The dropped mid*lo, lo*mid,
+ *    lo*lo are <= 2^-26 |a w|: below the rounding of an f32 accumulation of the same products;
+ *  - the result is NOT the k-ordered fmaf chain of GSL_F32 bit for bit (it is as close to the exact product as that chain is). It is
+ *    deterministic: a fixed order of accumulation, the same bits on every call and under HIP-graph replay;
+ *  - non-finite rule: a NaN or Inf in row m of A1 | A2 makes every element of output row m NaN, one
+ *    in row n of W1 | W2 every element of output column n (NaN also where the f32 kernel would produce Inf); nothing else is touched. (A 16-bit
+ *    MFMA by itself drops a NaN operand's k-group and clamps Inf.)
+ * Shapes outside the matrix-core kernel's (N < 128 or M < 64) run the exact-f32 VALU kernel of GSL_F32. */
+enum gsl_dtype { GSL_F32 = 0, GSL_BF16 = 1, GSL_F16 = 2, GSL_F32X3 = 3 };
 
 enum gsl_status {
   GSL_OK = 0,
@@ -107,7 +123,7 @@ GSL_API int gsl_unfold_patches_u8(const uint8_t* img, int layout, const float* t
 /* ---- K3/K5/K6/K7/K8 dense NT GEMM with an optional second K segment (the LoRA rank-r term)
  * and a fused epilogue. Replaces F.linear + loralib.Linear.forward (vit_face.py:330-334,349-356)
  * and their autograd dX.
- *   A1 [M,K1] (lda1), W1 [N,K1] (ldw1); A2 [M,K2] (lda2), W2 [N,K2] (ldw2)  — all `dtype`;
+ *   A1 [M,K1] (lda1), W1 [N,K1] (ldw1); A2 [M,K2] (lda2), W2 [N,K2] (ldw2)  — all `dtype` (GSL_F32X3: f32 tensors, see gsl_dtype);
  *   K1 % 64 == 0, K2 % 64 == 0 (K2 may be 0). bias/pos/cls f32; res f32 (bf16 for GSL_EPI_BIAS_RES_BF16). out/out2/aux per epilogue.
  *   dropout: p_drop in [0,1); mask = hash(seed, site, m*N+n) (see gsl_dropout_keep in DESIGN.md).
  *   Every (seed, site) pair of this ABI: when bit 31 of `site` (GSL_SEED_ON_DEVICE) is set, `seed` is not the value but a device
