@@ -272,11 +272,6 @@ __device__ __forceinline__ void store_tile_rows(bf16_t* stage, const f32x4_t (&a
   if (r + 8 < nvalid) *reinterpret_cast<uint4*>(gbase + (size_t)(r + 8) * gld + c * 8) = v1;
 }
 
-__device__ __forceinline__ void wg_barrier_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 // FAST: T > (NKT - 2) * 16, so only key tile NKT - 2 needs the per-element validity mask — a compile-time property of the unrolled
 // tile loop. (With the run-time first-partial-tile index the compiler materialises one predicate per element and tile, parks them in
 // VGPR lanes and pays two v_readlane + one v_cndmask per score element: 12 of 29 VALU instructions per tile step.) Key tile NKT - 1

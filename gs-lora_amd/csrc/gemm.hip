@@ -1147,16 +1147,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_glds_kernel(const bf16_t* __res
 #ifndef GSL_SMALL_NSTS
 #define GSL_SMALL_NSTS 3      // stages of the 64x64 ring kernel: 3 x 16 KB = three workgroups per CU (4: two; measured, r03_notes.md)
 #endif
-// Workgroup barrier that PUBLISHES this wave's LDS stores: s_barrier alone only lines the waves up — a ds_write issued in front of it may still be
-// in the LDS queue when another wave, past the barrier, reads the location (gfx950 has the back-off barrier: the compiler inserts no wait in front of a
-// raw s_barrier, and the raw builtin carries no fence). The K loops use the raw barrier on purpose (their LDS-DMA stream must stay in flight; what they
-// publish is retired by a counted vmcnt wait); every hand-over through plain LDS stores uses this one (or __syncthreads()).
-__device__ __forceinline__ void wg_barrier_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 struct LoraInk {
   const bf16_t* P; int ldp;
   const bf16_t* Q; int ldq;

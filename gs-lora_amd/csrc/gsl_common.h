@@ -190,6 +190,17 @@ __device__ __forceinline__ float block_max(float v, float* sm) {
   return t;
 }
 
+// ------------------------------------------------------------------ workgroup barrier for LDS hand-overs
+// Workgroup barrier that PUBLISHES this wave's LDS stores: s_barrier alone only lines the waves up — a ds_write issued in front of it may still be
+// in the LDS queue when another wave, past the barrier, reads the location (gfx950 has the back-off barrier: the compiler inserts no wait in front of a
+// raw s_barrier, and the raw builtin carries no fence). The GEMM K loops use the raw barrier on purpose (their LDS-DMA stream must stay in flight; what they
+// publish is retired by a counted vmcnt wait); every hand-over through plain LDS stores uses this one (or __syncthreads()).
+__device__ __forceinline__ void wg_barrier_lds() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
 // ------------------------------------------------------------------ dropout (counter-based hash)
 // keep(i) for element index i of dropout site `site` under `seed`: a 2-round multiply-xorshift
 // hash of the 64-bit pair counter idx/2 gives two 16-bit samples (elements 2k, 2k+1), each compared

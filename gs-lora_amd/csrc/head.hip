@@ -393,3 +393,182 @@ extern "C" int gsl_head_bwd_margin(const float* dlogits, const float* demb, cons
   return check_launch("gsl_head_bwd_margin");
 }
 #undef GSL_HEAD_BWD_CHECKS
+
+// ------------------------------------------------------------------ K10w head weight gradient (the linear-probe step)
+// d loss / d W of the head from the upstream dlogits: what autograd gives for F.linear(F.normalize(emb), F.normalize(W)) * s with the
+// margin on the label column (vit_face.py:181-207, 117-141), or for the plain nn.Linear of the Softmax head (:47-50). The reference
+// trains this tensor alone in train/backbone_forget_main.py:596-600, 657-670.
+//   G[b,c] = cos_s * dlogits[b,c], the ArcFace label column times arc_dphi(cos_y[b]) — the expression and the label rule of head_bwd_kernel
+//   d What_c = sum_b G[b,c] * emb_b / max(||emb_b||, 1e-12);  dW_c = (d What_c - What_c (What_c . d What_c)) / ||W_c||
+//   ||W_c|| < 1e-12: F.normalize's clamp has derivative 0 there, dW_c = d What_c / 1e-12
+//   linear: dW_c = sum_b dlogits[b,c] * emb_b, dbias_c = sum_b dlogits[b,c]
+// One workgroup of 16 waves per tile of CT classes, all D columns: wave w owns the images w, w + 16, ... in ascending order (a lane holds
+// the columns lane, lane + 64, ... of the image's row, so the row norm is one wave reduction and the row is read once for the CT classes),
+// then the 16 partial sums are added in wave order through LDS. The order of every sum is fixed by (B, C, D): no atomics, bit-repeatable.
+// Nothing in LDS is sized by C; every element of dW (and dbias) is stored.
+constexpr int HEAD_LINEAR = 2;      // head_kind of gsl_head_wgrad only: the plain classifier (no normalisation, no margin)
+constexpr int HW_WAVES = 16;
+
+// KM: the columns a lane holds of one row (D <= 64 * KM), so that D = 512 pays for 8 and not for HEAD_MAXD / 64 = 16.
+template <int KIND, int CT, int KM>
+__global__ __launch_bounds__(1024) void head_wgrad_kernel(const float* __restrict__ dlogits, const float* __restrict__ emb,
+                                                         const float* __restrict__ W, const int64_t* __restrict__ label,
+                                                         const float* __restrict__ cos_y, float* __restrict__ dW,
+                                                         float* __restrict__ dbias, int B, int C, int D, float cs, ArcMargin arc) {
+  constexpr int U = KM > 8 ? 2 : 4;         // images per round: up to 32 row loads of a lane in flight (eight images spill at CT = 2)
+  constexpr int NQ = (KM + 3) / 4;          // 256-column chunks
+  __shared__ float red[HW_WAVES][256];      // one 256-column chunk of every wave's partial sums
+  __shared__ float fin[CT][64 * KM];        // d What (cosine heads) / dW (linear) of the tile's classes
+  __shared__ float sb[HW_WAVES][CT];        // the waves' dbias partial sums
+  __shared__ float sm[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c0 = blockIdx.x * CT;
+  float acc[CT][KM];
+  float gsum[CT];
+#pragma unroll
+  for (int j = 0; j < CT; ++j) {
+    gsum[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < KM; ++k) acc[j][k] = 0.f;
+  }
+  // U images per round (b, b + 16, ...: the wave's ascending order). Every load of the round — the rows, their dlogits, label and cos_y —
+  // is issued before the first use, so a round costs one trip to memory; the work is latency-bound (B / (16 U) rounds per wave).
+  for (int b0 = wave; b0 < B; b0 += U * HW_WAVES) {
+    float e[U][KM], g[U][CT], cy[U];
+    int y[U];      // the label where it lies in [0, C) (head_bwd_kernel's rule), else -1
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int b = b0 + u * HW_WAVES;
+      const bool live = b < B;      // (a dead row adds 0 * 0 to every sum)
+      const float* er = emb + (size_t)(live ? b : b0) * D;
+#pragma unroll
+      for (int k = 0; k < KM; ++k) {
+        const int d = k * 64 + lane;
+        e[u][k] = (live && d < D) ? er[d] : 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < CT; ++j) g[u][j] = (live && c0 + j < C) ? dlogits[(size_t)b * C + c0 + j] : 0.f;
+      y[u] = -1;
+      cy[u] = 0.f;
+      if constexpr (KIND == HEAD_ARCFACE) {
+        if (live) {
+          const int64_t yl = label[b];
+          y[u] = (yl >= 0 && yl < C) ? (int)yl : -1;
+          cy[u] = cos_y[b];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float inv = 1.0f;
+      if constexpr (KIND != HEAD_LINEAR) {
+        float ss = 0.f;
+#pragma unroll
+        for (int k = 0; k < KM; ++k) ss += e[u][k] * e[u][k];
+        inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+      }
+      float dphi = 1.0f;
+      if constexpr (KIND == HEAD_ARCFACE) {
+        if (y[u] >= c0 && y[u] < c0 + CT) dphi = arc_dphi(cy[u], arc);      // (other tiles never use it)
+      }
+#pragma unroll
+      for (int j = 0; j < CT; ++j) {
+        float gv = g[u][j];
+        if constexpr (KIND == HEAD_LINEAR) gsum[j] += gv;
+        if constexpr (KIND != HEAD_LINEAR) gv *= cs;
+        if constexpr (KIND == HEAD_ARCFACE) { if (c0 + j == y[u]) gv *= dphi; }
+        const float gi = gv * inv;
+#pragma unroll
+        for (int k = 0; k < KM; ++k) acc[j][k] += gi * e[u][k];
+      }
+    }
+  }
+  // the 16 waves' partial sums, added in wave order: 256 columns at a time through red[][]
+#pragma unroll
+  for (int j = 0; j < CT; ++j) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q * 256 < D) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (4 * q + i < KM) red[wave][i * 64 + lane] = acc[j][4 * q + i];
+        wg_barrier_lds();
+        if (tid < 256 && q * 256 + tid < 64 * KM) {
+          float s = 0.f;
+#pragma unroll
+          for (int w = 0; w < HW_WAVES; ++w) s += red[w][tid];
+          fin[j][q * 256 + tid] = s;
+        }
+        wg_barrier_lds();
+      }
+    }
+  }
+  if constexpr (KIND == HEAD_LINEAR) {
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < CT; ++j) sb[wave][j] = gsum[j];
+    }
+    wg_barrier_lds();
+    if (dbias && tid < CT && c0 + tid < C) {
+      float s = 0.f;
+      for (int w = 0; w < HW_WAVES; ++w) s += sb[w][tid];
+      dbias[c0 + tid] = s;
+    }
+  }
+  for (int j = 0; j < CT; ++j) {
+    const int c = c0 + j;
+    if (c >= C) break;      // (uniform over the workgroup)
+    const bool in = tid < D;      // D <= 64 * KM <= the workgroup size: a thread finishes one column
+    const float f = in ? fin[j][tid] : 0.f;
+    if constexpr (KIND == HEAD_LINEAR) {
+      if (in) dW[(size_t)c * D + tid] = f;
+    } else {
+      const float w = in ? W[(size_t)c * D + tid] : 0.f;
+      const float raw = sqrtf(block_sum(w * w, sm));
+      const float dot = block_sum(w * f, sm);
+      const float nrm = fmaxf(raw, 1e-12f);
+      if (in) dW[(size_t)c * D + tid] = (raw >= 1e-12f) ? (f - (w / nrm) * (dot / nrm)) / nrm : f / nrm;
+    }
+  }
+}
+
+template <int KIND, int CT>
+static void head_wgrad_launch_ct(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
+                                 float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
+  const dim3 grid((C + CT - 1) / CT), block(HW_WAVES * 64);
+  if (D <= 256)
+    hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 4>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
+  else if (D <= 512)
+    hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 8>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
+  else
+    hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 16>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
+}
+
+template <int KIND>
+static void head_wgrad_launch(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
+                              float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
+  // A workgroup per class up to 256 classes. The cosine heads need every row's norm, so a workgroup reads all of emb whatever part of
+  // dW it owns: splitting the columns over more workgroups would shorten no wave's chain of rounds and multiply the L2 traffic, and
+  // splitting the batch would need a second pass or float atomics. Many classes: two per workgroup, which read every row once for both.
+  if (C <= 256)
+    head_wgrad_launch_ct<KIND, 1>(dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc, s);
+  else
+    head_wgrad_launch_ct<KIND, 2>(dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc, s);
+}
+
+extern "C" int gsl_head_wgrad(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
+                              float* dbias, int B, int C, int D, int head_kind, float cos_s, double m, int easy_margin, gsl_stream_t s) {
+  GSL_CHECK_ARG(head_kind == HEAD_COSFACE || head_kind == HEAD_ARCFACE || head_kind == HEAD_LINEAR, "head_kind: 0 (CosFace), 1 (ArcFace) or 2 (linear)");
+  GSL_CHECK_ARG(dlogits && emb && dW && B > 0 && C > 0, "null/size");
+  GSL_CHECK_ARG(head_kind == HEAD_LINEAR || W, "the cosine heads read W");
+  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD, "D <= 1024");
+  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || (label && cos_y), "ArcFace needs label and cos_y [B]");
+  GSL_CHECK_ARG(head_kind == HEAD_LINEAR || !dbias, "dbias belongs to the linear head");
+  if (head_kind == HEAD_ARCFACE)
+    head_wgrad_launch<HEAD_ARCFACE>(dlogits, emb, W, label, cos_y, dW, nullptr, B, C, D, cos_s, arc_margin(m, easy_margin), s);
+  else if (head_kind == HEAD_LINEAR)
+    head_wgrad_launch<HEAD_LINEAR>(dlogits, emb, W, nullptr, nullptr, dW, dbias, B, C, D, 1.0f, ArcMargin{}, s);
+  else
+    head_wgrad_launch<HEAD_COSFACE>(dlogits, emb, W, nullptr, nullptr, dW, nullptr, B, C, D, cos_s, ArcMargin{}, s);
+  return check_launch("gsl_head_wgrad");
+}

@@ -92,6 +92,9 @@ def get_args(argv=None):
     p.add_argument("--per_class", default=False, action="store_true",
                    help="after each task, per-class accuracy of the forget / remain test sets and, for every forgotten class, its three "
                         "most frequent predictions (engine_cl.eval_data_per_class; test/test_own.py:99-144)")
+    p.add_argument("--probe_epochs", type=int, default=0,
+                   help="after the last task, the linear probe of train/backbone_forget_main.py on a copy of the model: retrain the classifier "
+                        "head alone for this many epochs on forget + remain images and report both accuracies (driver_probe.run_probe); 0: off")
     p.add_argument("--outdir", default=None)
     p.add_argument("--seed", type=int, default=1337)
     p.add_argument("--average_weight", default=False, action="store_true", help="EMA model of the reference (:502-507, :1058-1098)")
@@ -306,6 +309,14 @@ def main(argv=None):
     cfg = {"DATA_ROOT": "./data/synthetic/", "BND_pro": args.BND_pro, "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net,
            "PROTO_DISTANCE": args.pro_distance}
     report, ema_model = run_tasks(model, args, task_data, dev, out, geo["depth"], cfg=cfg, after_task=after_task)
+    if args.probe_epochs > 0:      # can a fresh linear layer read the forgotten identities back out of the forgotten backbone's features?
+        import driver_probe
+        forgotten = [c for r in report for c in r["forget_cls"]]
+        loaders = driver_probe.probe_loaders(x_all, y_all, x_te, y_te, forgotten, [c for c in order if c not in forgotten], args.batch_size,
+                                             args.seed + 100)
+        probe_args = copy.copy(args)
+        probe_args.epochs = args.probe_epochs
+        report[-1]["probe"] = driver_probe.run_probe(copy.deepcopy(model).to(dev), probe_args, loaders, dev)
     return report, out, (model if ema_model is None else (model, ema_model))
 
 

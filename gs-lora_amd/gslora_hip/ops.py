@@ -600,6 +600,40 @@ def head_bwd_margin(dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, Wn, cos_s
                      rstd, emb, Wn, cos_s, dtype, p_drop, seed, site, linear, pool_mean, stream_dtype, compact, gscale, target_exp)
 
 
+HEAD_WGRAD_KINDS = {"cosface": 0, "arcface": 1, "linear": 2, "softmax": 2}      # head_kind of gsl_head_wgrad
+
+
+def head_wgrad(dlogits, emb, W, head_kind, cos_s=64.0, m=0.5, easy_margin=False, label=None, cos_y=None, bias=False, dW=None, dbias=None):
+    """d loss / d W of the head from the upstream dlogits [B, C] (gsl_head_wgrad): emb [B, D] is the head forward's (un-normalised)
+    embedding, W [C, D] the raw weight. head_kind "cosface" | "arcface" (needs the forward's label and cos_y) | "linear" / "softmax"
+    (bias=True: also d loss / d bias). Returns (dW, dbias or None): freshly allocated unless given, every element stored."""
+    kind = HEAD_WGRAD_KINDS[head_kind]
+    _need(dlogits, emb, W, label, cos_y, dW, dbias)
+    B, C = dlogits.shape
+    D = emb.shape[1]
+    if emb.shape[0] != B or tuple(W.shape) != (C, D) or any(t.dtype != torch.float32 for t in (dlogits, emb, W)):
+        raise RuntimeError(f"head_wgrad: float32 dlogits [B, C], emb [B, D], W [C, D] expected, got {tuple(dlogits.shape)}, {tuple(emb.shape)}, {tuple(W.shape)}")
+    if not (dlogits.is_contiguous() and emb.is_contiguous() and W.is_contiguous()):
+        raise RuntimeError("head_wgrad: dlogits, emb and W must be contiguous")
+    if kind == 1 and (label is None or cos_y is None or label.dtype != torch.int64 or label.numel() != B or cos_y.numel() != B
+                      or cos_y.dtype != torch.float32 or not label.is_contiguous() or not cos_y.is_contiguous()):
+        raise RuntimeError("head_wgrad: the ArcFace head needs the forward's contiguous int64 label [B] and float32 cos_y [B]")
+    if dW is None:
+        dW = torch.empty(C, D, device=W.device, dtype=torch.float32)
+    elif tuple(dW.shape) != (C, D) or dW.dtype != torch.float32 or not dW.is_contiguous():      # (the kernel stores all C * D elements)
+        raise RuntimeError(f"head_wgrad: dW must be a contiguous float32 [{C}, {D}] buffer, got {dW.dtype} {tuple(dW.shape)}")
+    if kind == 2 and (bias or dbias is not None):
+        if dbias is None:
+            dbias = torch.empty(C, device=W.device, dtype=torch.float32)
+        elif tuple(dbias.shape) != (C,) or dbias.dtype != torch.float32 or not dbias.is_contiguous():
+            raise RuntimeError(f"head_wgrad: dbias must be a contiguous float32 [{C}] buffer, got {dbias.dtype} {tuple(dbias.shape)}")
+    else:
+        dbias = None
+    L.check(L.load().gsl_head_wgrad(_p(dlogits), _p(emb), _p(W), _p(label) if kind == 1 else None, _p(cos_y) if kind == 1 else None, _p(dW),
+                                    _p(dbias), B, C, D, kind, float(cos_s), float(m), 1 if easy_margin else 0, _stream()), "gsl_head_wgrad")
+    return dW, dbias
+
+
 def ce_fwd(logits, labels):
     _need(logits, labels)
     out = torch.empty(2, device=logits.device, dtype=torch.float32)

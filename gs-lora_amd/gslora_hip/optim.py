@@ -138,6 +138,9 @@ class FusedAdamW(torch.optim.Optimizer):
             old = self._flat.get(gi)
             if old is not None and old.get("ok") and old["n"] == n:
                 ent["m"], ent["v"], ent["step"] = old["m"], old["v"], old["step"]
+                # (a gradient that autograd allocates afresh every step — the classifier head's — changes sig, not the state: the device
+                #  counters of a captured step stay the ones graph_sync() filled)
+                ent.update({k: old[k] for k in ("step_dev", "lr_dev", "step_dev_val", "lr_dev_val") if k in old})
             else:
                 ent["m"] = torch.zeros(n, device=first.device, dtype=torch.float32)
                 ent["v"] = torch.zeros(n, device=first.device, dtype=torch.float32)
@@ -211,12 +214,21 @@ def create_optimizer(args, model):
     opt = getattr(args, "opt", "adamw").lower()
     if opt != "adamw":
         raise NotImplementedError(f"gs-lora_amd implements the AdamW path of timm.create_optimizer, not '{opt}'")
-    decay, no_decay = [], []
+    # the classifier head (the linear probe; names of model.trainable_head) gets param groups of its own behind the LoRA ones: the LoRA
+    # group stays one contiguous range of the flat bucket (one launch), the head weight is a flat range by itself, and a LoRA-only model
+    # gets exactly the groups, in the order, it always got. Same hyper-parameters in a separate group = the same arithmetic.
+    heads = set(getattr(model.module if isinstance(model, torch.nn.DataParallel) else model, "trainable_head", ()))
+    decay, no_decay, head_decay, head_no_decay = [], [], [], []
     for name, p in model.named_parameters():
         if not p.requires_grad:
             continue
-        (no_decay if (p.ndim <= 1 or name.endswith(".bias")) else decay).append(p)
-    groups = [g for g in (dict(params=no_decay, weight_decay=0.0), dict(params=decay, weight_decay=args.weight_decay))
+        nd = p.ndim <= 1 or name.endswith(".bias")      # timm: no decay on biases and 1-D tensors
+        if (name[7:] if name.startswith("module.") else name) in heads:
+            (head_no_decay if nd else head_decay).append(p)
+        else:
+            (no_decay if nd else decay).append(p)
+    groups = [g for g in (dict(params=no_decay, weight_decay=0.0), dict(params=decay, weight_decay=args.weight_decay),
+                          dict(params=head_no_decay, weight_decay=0.0), dict(params=head_decay, weight_decay=args.weight_decay))
               if g["params"]]
     kw = dict(lr=args.lr, eps=getattr(args, "opt_eps", None) or 1e-8)
     betas = getattr(args, "opt_betas", None)

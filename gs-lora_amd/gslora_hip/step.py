@@ -228,6 +228,43 @@ def _model_input(net, x):
     return x if (x.dtype == torch.uint8 and getattr(net, "input_norm", None) is not None) else x.float()
 
 
+def _head_trains(net):
+    """A parameter of the classifier head requires a gradient (HIP models only: the names of net.trainable_head)."""
+    heads = getattr(net, "trainable_head", ())
+    return bool(heads) and any(p.requires_grad for n, p in net.named_parameters() if n in heads)
+
+
+def head_probe_step(model, optimizer, criterion, x, y):
+    """One step of the linear probe — the loop body of the reference's train/backbone_forget_main.py:657-670: forward, mean cross-entropy,
+    top-1, backward, optimizer.step(). The trainable parameters are whatever requires a gradient; with the head alone (the reference's rule,
+    :596-600: names containing "loss") the forward keeps no activation and the backward is one gsl_head_wgrad launch.
+    Returns a DEVICE tensor [loss, prec1 %] (no host sync). Single process: the head's gradient is not all-reduced.
+    Capturable with torch.cuda.graph under optimizer.graph_mode / graph_sync() and the runner's seed_dev, like the GS-LoRA step: dropout
+    seed, lr and step count are then read from device memory."""
+    if _world() > 1:
+        raise RuntimeError("gs-lora_amd: head_probe_step runs in one process (the head gradient is not reduced across ranks); "
+                           f"a process group of {_world()} ranks is active")
+    _check_not_replicated(model)
+    net = model.module if isinstance(model, nn.DataParallel) else model
+    logits, _ = model(_model_input(net, x), y)
+    n = float(x.size(0))
+    if _plain_ce(criterion):
+        ce_sum, hits = losses.ce_sum_top1(logits, y)
+        loss = ce_sum / n
+    else:      # exotic criterion: keep its semantics, top-1 from the HIP kernel
+        loss = criterion(logits, y)
+        hits = losses.ce_sum_top1(logits.detach(), y)[1]
+    optimizer.zero_grad()
+    loss.backward()
+    bucket = net.runner().bucket if hasattr(net, "runner") else None
+    if bucket is not None and any(p.requires_grad for p in bucket.params):
+        _arm_overflow_guard(net, optimizer)      # LoRA trains too: its fp16 backward ran on loss-scaled gradients
+    elif hasattr(optimizer, "overflow_guard"):
+        optimizer.overflow_guard = None          # head alone: f32 arithmetic, no loss scale, nothing to guard
+    optimizer.step()
+    return torch.stack((loss.detach(), hits * (100.0 / n)))
+
+
 def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha, BND, use_structure=True,
                  group_type="block", use_prototype=False, proto_table=None, w_f=0.0, w_r=0.0, BND_pro=0.0,
                  backend=HipBackend, fuse_batches=True, _comm=_EagerComm, proto_distance="kl"):
@@ -243,6 +280,9 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
     _check_not_replicated(model)
     net = model.module if isinstance(model, nn.DataParallel) else model
     world = _world()
+    if _dp_active() and _head_trains(net):      # (before any launch)
+        raise RuntimeError("gs-lora_amd: the data-parallel gs_lora_step all-reduces the flat LoRA gradient bucket only; a trainable classifier "
+                           "head (loss.weight / loss.bias) is served by one process (gs_lora_step eager, or head_probe_step)")
     dev = x_r.device
     split = None
     if getattr(net, "input_norm", None) is not None and (x_r.dtype == torch.uint8) != (x_f.dtype == torch.uint8):
@@ -432,6 +472,9 @@ class GraphedStep:
         return gs_lora_step(self.model, self.optimizer, self.criterion, x_r, y_r, x_f, y_f, **kw)
 
     def __call__(self, x_r, y_r, x_f, y_f, **kw):
+        if _head_trains(self.net):      # (any other trainable frozen tensor is refused, with its own reason, by the model's forward)
+            raise RuntimeError("gs-lora_amd: GraphedStep captures the LoRA-only step; a trainable classifier head (loss.weight / loss.bias) runs "
+                               "through the eager gs_lora_step (cfg HIP_GRAPH=False) or head_probe_step")
         if not self._usable():
             return self._eager(x_r, y_r, x_f, y_f, kw)
         key = self._key(x_r, y_r, x_f, y_f, kw)

@@ -462,6 +462,8 @@ class ViTRunner:
     def forward(self, img, label, save):
         """img: [B, C, H, W], or a tuple of such batches that are processed as ONE batch (gs_lora_step hands over the remain and the
         forget batch this way: each is patchified into its row range of the token matrix, no concatenated image copy is made)."""
+        head_only = save == "head"      # only the head's parameters train: nothing of the blocks is kept (see head_param_grads)
+        save = save is True
         c, parts, u8tab, label = self._fwd_prepare(img, label, save)
         sp = c.sp
         x = self._fwd_patch(c, parts, u8tab)
@@ -479,6 +481,8 @@ class ViTRunner:
                 stash.append(st)
             x = x2
         logits, emb, head = self._fwd_head(c, x, label)
+        if head_only:
+            return logits, emb, dict(ctx=c, emb=emb, label=label, cos_y=head["cos_y"])
         return logits, emb, (dict(ctx=c, layers=stash, x_last=x, emb=emb, label=label, **head) if save else None)
 
     def _fwd_prepare(self, img, label, save):
@@ -679,6 +683,22 @@ class ViTRunner:
         return logits, emb, dict(Th=Th, meanh=meanh, rstdh=rstdh, Wn=Wn, cos_y=cos_y)
 
     # ------------------------------------------------------------------ backward
+    def head_param_grads(self, saved, dlogits, want):
+        """d loss / d (head weight[, head bias]) from the upstream dlogits: ONE gsl_head_wgrad launch into fresh buffers, for the head
+        parameters that train (`want`: one flag per parameter handed to the autograd node — the weight, then the Softmax head's bias).
+        Reads the forward's emb (and, ArcFace, its labels and label cosines) and the raw weight: no activation of the blocks, no
+        gsl_head_bwd, no loss-scale state — the head's arithmetic is f32 in every compute mode."""
+        sp = saved["ctx"].sp
+        if dlogits is None or not any(want):
+            return (None,) * len(want)
+        params = [p for p in (sp.head_w, sp.head_b) if p is not None and p.requires_grad]
+        linear = sp.head_kind in LINEAR_HEADS
+        dW, db = ops.head_wgrad(dlogits.contiguous().float(), saved["emb"], sp.head_w.detach().contiguous(),
+                                "linear" if linear else sp.head_kind, cos_s=sp.cos_s, m=sp.cos_m, easy_margin=sp.easy_margin,
+                                label=saved["label"], cos_y=saved["cos_y"], bias=linear and sp.head_b is not None and sp.head_b.requires_grad)
+        by_param = {id(sp.head_w): dW, id(sp.head_b): db}
+        return tuple(by_param[id(p)] if w else None for p, w in zip(params, want))
+
     def backward(self, saved, dlogits, demb):
         """Accumulates d(loss)/d(LoRA) into the flat gradient bucket (views are the params' .grad). One chain for both LoRA sites: with
         the adapters on the FFN it stops after the LoRA gradients of block 0's FFN; with the adapters on the QKV projection

@@ -102,6 +102,9 @@ def vit_b_16(weights=None, **kwargs):
 
 
 class ModifiedViT(HipModelMixin, nn.Module):
+    # heads.head stays frozen: the reference's imagenet100 drivers never train it, so the head-gradient path serves the face models only
+    _frozen_note = " (the ModifiedViT head, heads.head, is not trainable here: the reference freezes it for imagenet100)"
+
     def __init__(self, vit_model):
         super().__init__()
         self.conv_proj = vit_model.conv_proj

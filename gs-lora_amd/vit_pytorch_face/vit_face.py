@@ -180,14 +180,17 @@ class Transformer(_Holder):
 
 
 class _ViTFaceFn(torch.autograd.Function):
-    """One autograd node for the whole network. LoRA parameters are passed so that autograd sees the
-    dependency; their gradients are accumulated straight into the flat bucket whose views are the
-    parameters' .grad (same observable result as autograd accumulation, no per-tensor copies)."""
+    """One autograd node for the whole network. The trainable parameters are passed so that autograd sees the dependency: first the head's
+    (loss.weight, loss.bias — those that require a gradient), then the LoRA ones. LoRA gradients are accumulated straight into the flat
+    bucket whose views are the parameters' .grad (same observable result as autograd accumulation, no per-tensor copies); the head's are
+    freshly written buffers (gsl_head_wgrad) that autograd accumulates into .grad.
+    mode True: the whole backward chain runs (LoRA, plus the head's one launch when it trains). mode "head" (no trainable LoRA parameter):
+    the forward keeps nothing of the blocks and the backward is that one launch."""
 
     @staticmethod
-    def forward(ctx, runner, img, label, *lora_params):
-        logits, emb, saved = runner.forward(img, label, save=True)
-        ctx.runner, ctx.saved, ctx.n = runner, saved, len(lora_params)
+    def forward(ctx, runner, img, label, mode, n_head, *params):
+        logits, emb, saved = runner.forward(img, label, save=mode)
+        ctx.runner, ctx.saved, ctx.mode, ctx.n_head, ctx.n = runner, saved, mode, n_head, len(params)
         if logits is None:
             return emb
         return logits, emb
@@ -200,9 +203,13 @@ class _ViTFaceFn(torch.autograd.Function):
             dlogits, demb = grads
         else:
             dlogits, demb = None, grads[0]
-        ctx.runner.backward(ctx.saved, dlogits, demb)
+        head_grads = (None,) * ctx.n_head
+        if ctx.n_head:      # d loss / d (loss.weight, loss.bias): demb (the prototype term) reaches the head's parameters through nothing
+            head_grads = ctx.runner.head_param_grads(ctx.saved, dlogits, ctx.needs_input_grad[5:5 + ctx.n_head])
+        if ctx.mode is True:
+            ctx.runner.backward(ctx.saved, dlogits, demb)
         ctx.saved = None
-        return (None, None, None) + (None,) * ctx.n
+        return (None,) * 5 + tuple(head_grads) + (None,) * (ctx.n - ctx.n_head)
 
 
 # the speed mode a model starts in (GSLORA_DTYPE overrides): IEEE fp16 operands since round 5 — same kernels, bytes and MFMA rate as bf16,
@@ -271,22 +278,39 @@ class HipModelMixin:
         self.invalidate_operand_caches()      # (copy_ bumps the versions anyway; explicit so that a custom loader writing through .data is covered too)
         return out
 
+    # names of the non-LoRA parameters that may train on the HIP path: the classifier head of ViT_face / ViTs_face (the linear probe of
+    # train/backbone_forget_main.py:596-600, the baselines' --ffn_open), whose gradient is gsl_head_wgrad
+    trainable_head = ()
+    _frozen_note = ""
+
     def _hip_call(self, img, label):
         runner = self.runner()
         spec = self.hip_spec()
         lora_params = [p for blk in spec.blocks for p in blk.lora_params()] if spec.lora_rank > 0 else []
         grad_on = torch.is_grad_enabled()
-        if grad_on and any(p.requires_grad for n, p in self.named_parameters() if "lora_" not in n):
-            raise RuntimeError(f"gs-lora_amd {type(self).__name__} trains LoRA parameters only: call "
-                               "loralib.mark_only_lora_as_trainable(model) first (or run under torch.no_grad())")
-        if grad_on and any(p.requires_grad for p in lora_params):
-            out = _ViTFaceFn.apply(runner, img, label, *lora_params)
+        head_params = []
+        if grad_on:
+            for n, p in self.named_parameters():
+                if not p.requires_grad or "lora_" in n:
+                    continue
+                if n not in self.trainable_head:
+                    raise RuntimeError(f"gs-lora_amd {type(self).__name__}: parameter {n!r} requires a gradient, but the HIP path trains the LoRA "
+                                       f"parameters{' and the classifier head (loss.weight, loss.bias)' if self.trainable_head else ''} only"
+                                       f"{self._frozen_note}: call loralib.mark_only_lora_as_trainable(model) first, set requires_grad by name "
+                                       "as train/backbone_forget_main.py:596-600 does, or run under torch.no_grad()")
+                head_params.append(p)
+        lora_live = grad_on and any(p.requires_grad for p in lora_params)
+        if lora_live or (head_params and label is not None):
+            # (without a label there are no logits: the head's parameters take no part in the forward)
+            out = _ViTFaceFn.apply(runner, img, label, True if lora_live else "head", len(head_params), *head_params, *lora_params)
             return out if isinstance(out, tuple) else (None, out)
         logits, emb, _ = runner.forward(img, label, save=False)
         return logits, emb
 
 
 class ViT_face(HipModelMixin, nn.Module):
+    trainable_head = ("loss.weight", "loss.bias")
+
     def __init__(self, *, loss_type, GPU_ID, num_class, image_size, patch_size, dim, depth, heads, mlp_dim, pool="cls",
                  channels=3, dim_head=64, dropout=0.0, emb_dropout=0.0, lora_rank=8, lora_pos: str = "FFN"):
         super().__init__()

@@ -291,6 +291,25 @@ GSL_API int gsl_head_bwd_margin(const float* dlogits, const float* demb, const v
                  float* gscale, float* amax_ws, int target_exp, int head_kind, double m, int easy_margin,
                  const float* cos_y, const int64_t* label, gsl_stream_t s);
 
+/* ---- K10w head weight gradient: d loss / d W of the classifier head from dlogits — the one trainable tensor of the linear-probe driver
+ * (train/backbone_forget_main.py:596-600 freezes everything but the parameters named "loss", :657-670 retrains them with plain CE; the
+ * baseline drivers' --ffn_open, train_own_forget_cl.py:426). What autograd gives the reference for vit_face.py:181-207 (CosFace),
+ * :117-141 (ArcFace) and :47-50 (Softmax). All arithmetic f32.
+ *   head_kind 0 = CosFace, 1 = ArcFace, 2 = linear (the Softmax head; cos_s, m, easy_margin, W, label and cos_y are not read).
+ *   dlogits [B,C], emb [B,D] (the LayerNorm output gsl_head_fwd* writes, not normalised), W [C,D] the RAW weight, label [B] / cos_y [B]
+ *   (ArcFace only: cos_y as written by gsl_head_fwd_margin).
+ *   G[b,c] = cos_s * dlogits[b,c]; ArcFace multiplies the label column by d phi / d cos at cos_y[b] — the expression gsl_head_bwd_margin
+ *   uses, a label outside [0, C) included (no column is scaled), so both take the same branch.
+ *   d What_c = sum_b G[b,c] emb_b / max(||emb_b||, 1e-12);  dW_c = (d What_c - What_c (What_c . d What_c)) / ||W_c||, What_c = W_c / ||W_c||;
+ *   ||W_c|| < 1e-12: dW_c = d What_c / 1e-12 (the derivative of F.normalize's clamp, as torch).
+ *   linear: dW_c = sum_b dlogits[b,c] emb_b and, with dbias != NULL, dbias_c = sum_b dlogits[b,c]. dbias must be NULL for the cosine heads.
+ * dW [C,D] and dbias [C] are plain stores of every element (no pre-zeroing, no accumulation). No allocation, no sync, no atomics: the sum
+ * over b runs in an order fixed by (B, C, D) — per wave ascending, the 16 waves of a workgroup added in wave order — so two calls agree
+ * bit for bit; capturable in a HIP graph. Any B >= 1, any C >= 1 (no buffer is sized by C), D <= 1024. */
+GSL_API int gsl_head_wgrad(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y,
+                 float* dW, float* dbias, int B, int C, int D, int head_kind, float cos_s, double m, int easy_margin,
+                 gsl_stream_t s);
+
 /* ---- K11 cross entropy (mean) + top-1 (engine_cl.py:65-78, util/utils.py:354-368).
  * out2 f32 [2] = { sum_i CE_i , #correct }; row_ws f32 [2*B] scratch (per-row loss / hit, summed in a fixed order). */
 GSL_API int gsl_ce_fwd(const float* logits, const int64_t* labels, float* out2, float* row_ws, int B, int C, gsl_stream_t s);
