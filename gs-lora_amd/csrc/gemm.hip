@@ -2149,6 +2149,44 @@ __global__ __launch_bounds__(256) void gemm_f32x3_mfma_kernel(const float* __res
 }
 #endif
 
+// ---- The tile rule: shape -> kernel, written once. launch_gemm, gemm_nt_lora_rows and the exported gsl_gemm_tile_choice call it; the development
+// knobs apply after it. Measured on MI355X at M = 201 728 (profiles/r01_gemm_ab.md): N >= 512 wants the 256x256 8-phase tile (also for the VALU-heavy
+// BIAS_GELU epilogue), skinny N the 256x128 ring. Fewer than 128 tiles of 256x256 cannot fill the 256 CUs: the 128x128 kernel (4x the workgroups)
+// wins there (measured at M = 1576: 15-44 us vs 19-58 us per GEMM); from ~150 tiles on the 8-phase kernel is ahead. Up to ~256 tiles of 128x128 (one
+// per CU) leave CUs idle and serialise the K loop: 64x64 tiles on the ring kernel (tools/probes/small_m_gemm.py, profiles/r03_c_small_m.md).
+// which form of the 64-row ring kernel: 64x128 tiles when the 64x64 grid exceeds the resident workgroups (3 per CU: one round), two K groups for a
+// serial K chain on at most one workgroup per CU
+static inline int small_ring_tile(int M, int N, int K) {
+  const long t64 = (long)((M + BMS - 1) / BMS) * ((N + BNS - 1) / BNS);
+  if (t64 > SMALL_SLOTS) return GSL_TILE_RING64_WIDE;
+  if (GSL_SMALL_KSPLIT && K >= GSL_SMALL_KSPLIT_MINK && t64 <= 256) return GSL_TILE_RING64_KSPLIT;
+  return GSL_TILE_RING64;
+}
+// dtype: GSL_OP16, GSL_F32 or GSL_F32X3. has_out2: STORE with the compact second output, which lives on the 256x128 ring kernel. lora: the in-kernel-LoRA
+// form exists on the ring kernel and the 8-phase kernel only.
+static inline int gemm_tile_choice(int M, int N, int K, int dtype, bool has_out2, bool lora) {
+  if (dtype != GSL_OP16) {
+    // parity mode: the matrix-core kernel wherever its 128x128 tiles are not mostly padding (skinny N = 64 LoRA projections, a handful of
+    // rows: the 64x64 VALU kernel); the two are bit-identical, the choice is speed only
+    if (N >= 128 && M >= 64) return dtype == GSL_F32X3 ? GSL_TILE_F32X3_MFMA : GSL_TILE_F32_MFMA;
+    return GSL_TILE_F32_VALU;
+  }
+  if (has_out2 && !lora) return GSL_TILE_RING256X128;
+  const long tiles256 = (long)((M + BM4 - 1) / BM4) * ((N + BN4 - 1) / BN4), nblk128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  const bool few = M < 1024 || tiles256 < 128;
+  if (few && nblk128 <= 256) return small_ring_tile(M, N, K);
+  if (lora) return GSL_TILE_P8;
+  if (few) return GSL_TILE_128;
+  return N >= 512 ? GSL_TILE_P8 : GSL_TILE_RING256X128;
+}
+#if GSL_HAS_F32      // not an f32 feature guard: this file is compiled once per 16-bit operand format, and only the plain compile defines the exported symbol
+extern "C" int gsl_gemm_tile_choice(int M, int N, int K, int dtype, int has_out2, int in_kernel_lora) {
+  const bool h16 = dtype == GSL_BF16 || dtype == GSL_F16;
+  if (M <= 0 || N <= 0 || K <= 0 || !(h16 || ((dtype == GSL_F32 || dtype == GSL_F32X3) && !in_kernel_lora))) return -1;
+  return gemm_tile_choice(M, N, K, h16 ? GSL_OP16 : dtype, has_out2 != 0, in_kernel_lora != 0);      // (GSL_OP16: the rule does not tell the two 16-bit formats apart)
+}
+#endif
+
 // Launch knobs. The product library has none: block-id remap on, K rotation off, non-temporal output stores, no stamps, and the
 // tile is chosen from the shape alone. The development build (-DGSL_DEV -> libgslora_hip_dev.so, selected with GSLORA_HIP_LIB) reads
 // the ablation / variant knobs of tools/bench_gemm*.py and tools/probes/ from the environment.
@@ -2200,16 +2238,10 @@ static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int 
   const EpiArgs& e = e_in;
   if (dtype == GSL_OP16) {
     const int nblk = ((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
-    // Tile choice, measured on MI355X at M = 201 728 (profiles/r01_gemm_ab.md): N >= 512 wants the 256x256 8-phase tile (also for the
-    // VALU-heavy BIAS_GELU epilogue), skinny N the 256x128 ring. Fewer than 128 tiles of 256x256 cannot fill the 256 CUs: the 128x128
-    // kernel (4x the workgroups) wins there (measured at M = 1576: 15-44 us vs 19-58 us per GEMM); from ~150 tiles on the 8-phase
-    // kernel is ahead.   1 = 128x128 single stage, 3 = 256x128 three-stage ring, 8 = 256x256 8-phase ping-pong.
-    const long tiles256 = (long)((e.M + 255) / 256) * ((e.N + 255) / 256);
-    int variant = (e.M < 1024 || tiles256 < 128) ? 1 : (e.N >= 512 ? 8 : 3);
-    // up to ~256 tiles of 128x128 (one per CU) leave CUs idle and serialise the K loop: 64x64 tiles with a 4-stage ring (12). Measured at
-    // M = 1 576 (tools/probes/small_m_gemm.py, profiles/r03_c_small_m.md).
-    if (variant == 1 && (long)nblk <= 256) variant = 12;
-    if (EPI == GSL_EPI_STORE && e.out2) variant = 3;      // the compact second output lives on the ring kernel (checked by the caller: N <= 128, no bias)
+    // the tile rule (gemm_tile_choice) as the variant numbers the development knobs speak: 1 = 128x128 single stage, 3 = 256x128 three-stage
+    // ring, 8 = 256x256 8-phase ping-pong, 12 = the 64-row ring kernel
+    const int tile = gemm_tile_choice(e.M, e.N, K1 + K2, GSL_OP16, EPI == GSL_EPI_STORE && e.out2, false);
+    int variant = tile == GSL_TILE_P8 ? 8 : tile == GSL_TILE_RING256X128 ? 3 : tile == GSL_TILE_128 ? 1 : 12;
 #define GSL_LAUNCH(KERNEL, NB, NT) hipLaunchKernelGGL(KERNEL, dim3(NB), dim3(NT), 0, st, (const bf16_t*)A1, lda1, (const bf16_t*)W1, \
                                                       ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, e)
 #ifdef GSL_DEV
@@ -2332,11 +2364,11 @@ static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int 
     } else if (variant == 3) {
       GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 0>), ((e.M + BM3 - 1) / BM3) * ((e.N + BN3 - 1) / BN3), 512);
     } else if (variant == 12) {
-      // more 64x64 tiles than resident workgroups (3 per CU): 64x128 tiles, one round
-      if ((long)((e.M + BMS - 1) / BMS) * ((e.N + BNS - 1) / BNS) > SMALL_SLOTS)
+      const int ring = small_ring_tile(e.M, e.N, K1 + K2);
+      if (ring == GSL_TILE_RING64_WIDE)
         hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, false, 4>), dim3(((e.M + BMS - 1) / BMS) * ((e.N + 2 * BNS - 1) / (2 * BNS))), dim3(256), 0, st,
                            (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, LoraInk{}, e);
-      else if (GSL_SMALL_KSPLIT && (K1 + K2) >= GSL_SMALL_KSPLIT_MINK && (long)((e.M + BMS - 1) / BMS) * ((e.N + BNS - 1) / BNS) <= 256)      // a serial K chain on <= one workgroup per CU
+      else if (ring == GSL_TILE_RING64_KSPLIT)
         hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, false, 2, 2>), dim3(((e.M + BMS - 1) / BMS) * ((e.N + BNS - 1) / BNS)), dim3(512), 0, st,
                            (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, LoraInk{}, e);
       else
@@ -2349,8 +2381,7 @@ static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int 
   }
 #if GSL_HAS_F32
   else {
-    // parity mode: the matrix-core kernel wherever its 128x128 tiles are not mostly padding (skinny N = 64 LoRA projections, a handful of
-    // rows: the 64x64 VALU kernel); the two are bit-identical, the choice is speed only
+    // the matrix-core kernel or the 64x64 VALU kernel, by the tile rule (gemm_tile_choice)
     // (development build: GSL_F32_VALU=1 forces the VALU kernel at every shape — the switch for parity debugging should the MFMA's 4-term
     //  accumulation ever stop being a k-ordered fmaf chain on another part or compiler; tests/test_hip_ops.py compares the two directly)
 #ifdef GSL_DEV
@@ -2359,7 +2390,7 @@ static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int 
 #else
     constexpr bool force_valu = false;
 #endif
-    if (e.N >= 128 && e.M >= 64 && !force_valu) {
+    if (gemm_tile_choice(e.M, e.N, K1 + K2, dtype, false, false) != GSL_TILE_F32_VALU && !force_valu) {
       EpiArgs ef = e;
       ef.remap = 1;
       const int nblk = ((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
@@ -2452,6 +2483,7 @@ static int gemm_nt_rows(const void* A1, int lda1, const void* W1, int ldw1, int 
   GSL_CHECK_ARG(A1 && W1 && out && (K2 == 0 || (A2 && W2)), "null operand");
   GSL_CHECK_ARG((lda1 % 8) == 0 && (ldw1 % 8) == 0 && (K2 == 0 || ((lda2 % 8) == 0 && (ldw2 % 8) == 0)) && (ldo % 4) == 0,
                 "leading dimensions must keep 16-byte alignment");
+  GSL_CHECK_ARG(lda1 >= K1 && ldw1 >= K1 && (K2 == 0 || (lda2 >= K2 && ldw2 >= K2)) && ldo >= N, "leading dimensions: lda >= K, ldw >= K, ldo >= N");
   GSL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "p_drop");
   EpiArgs e;
   e.alpha = alpha; e.bias = bias; e.res = res; e.aux = aux; e.out = out; e.out2 = out2; e.ldo = ldo;
@@ -2548,6 +2580,7 @@ static int gemm_nt_lora_rows(const void* A, int lda, const void* W, int ldw, int
   GSL_CHECK_ARG(A && W && P && Q && out, "null operand");
   GSL_CHECK_ARG((lda % 8) == 0 && (ldw % 8) == 0 && (ldp % 8) == 0 && (ldq % 8) == 0 && ldq >= 32 && (ldo % 4) == 0 &&
                 (!tout || ((ldt % 8) == 0 && ldt >= 64)), "leading dimensions (P [16,K], Q [N,>=32], tout [M,>=64])");
+  GSL_CHECK_ARG(lda >= K && ldw >= K && ldp >= K && ldo >= N, "leading dimensions: lda >= K, ldw >= K, ldp >= K, ldo >= N");
   GSL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "p_drop");
   EpiArgs e;
   e.alpha = 1.0f; e.bias = bias; e.res = res; e.aux = aux; e.out = out; e.out2 = out2; e.ldo = ldo;
@@ -2570,17 +2603,17 @@ static int gemm_nt_lora_rows(const void* A, int lda, const void* W, int ldw, int
 #else
 #define GSL_LL_DEV(EPIV)
 #endif
-  // few rows (the launch-bound regime): the 64x64 ring kernel, same rule as gsl_gemm_nt's tile choice
-  const long tiles256 = (long)nb, nblk128 = (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  const bool small = (M < 1024 || tiles256 < 128) && nblk128 <= 256;
+  // few rows (the launch-bound regime): the 64-row ring kernel, by the tile rule (gemm_tile_choice)
+  const int ring = gemm_tile_choice(M, N, K, GSL_OP16, false, true);
+  const bool small = ring != GSL_TILE_P8;
 #define GSL_LL(EPIV)                                                                                                              \
   do {                                                                                                                            \
     GSL_LL_DEV(EPIV)                                                                                                              \
     if (small) {                                                                                                                  \
-      if ((long)((M + BMS - 1) / BMS) * ((N + BNS - 1) / BNS) > SMALL_SLOTS)                                                      \
+      if (ring == GSL_TILE_RING64_WIDE)                                                                                           \
         hipLaunchKernelGGL((gemm_bf16_small_kernel<EPIV, true, 4>), dim3(((M + BMS - 1) / BMS) * ((N + 2 * BNS - 1) / (2 * BNS))), dim3(256), 0, st, \
                            (const bf16_t*)A, lda, (const bf16_t*)W, ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e); \
-      else if (GSL_SMALL_KSPLIT && K >= GSL_SMALL_KSPLIT_MINK && (long)((M + BMS - 1) / BMS) * ((N + BNS - 1) / BNS) <= 256)                         \
+      else if (ring == GSL_TILE_RING64_KSPLIT)                                                                                    \
         hipLaunchKernelGGL((gemm_bf16_small_kernel<EPIV, true, 2, 2>), dim3(((M + BMS - 1) / BMS) * ((N + BNS - 1) / BNS)), dim3(512), 0, st, \
                            (const bf16_t*)A, lda, (const bf16_t*)W, ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e); \
       else                                                                                                                        \

@@ -22,6 +22,9 @@ EPI_STORE, EPI_BIAS_RES_F32, EPI_BIAS_GELU, EPI_MUL, EPI_PATCH, EPI_STORE_F32, E
 EPI_MUL_G8, EPI_BIAS_GELU_G8, EPI_BIAS_RES_F16, EPI_PATCH_F16, EPI_STORE_LN, EPI_STORE_QKV_HM_LN = 9, 10, 11, 12, 13, 14
 VERIF_FLIP_SUM, VERIF_PLAIN = 0, 1      # modes of gsl_verif_pair_dist
 U8_NCHW, U8_NHWC = 0, 1        # source layout of the uint8 gathers (gsl_patchify_u8 / gsl_unfold_patches_u8)
+# gsl_gemm_tile: what gsl_gemm_tile_choice returns
+(TILE_RING64, TILE_RING64_WIDE, TILE_RING64_KSPLIT, TILE_128, TILE_RING256X128, TILE_P8, TILE_F32_VALU, TILE_F32_MFMA,
+ TILE_F32X3_MFMA) = range(9)
 NORM_SPLIT = 8
 SEED_ON_DEVICE = 0x80000000   # flag bit of a `site` argument: `seed` is a device pointer to a uint64 (HIP-graph replays)
 
@@ -39,6 +42,7 @@ SIGNATURES = {
                     _vp, _vp, _i, _f, _u64, _u32, _vp],
     "gsl_gemm_nt_lora": [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i,
                          _f, _u64, _u32, _vp],
+    "gsl_gemm_tile_choice": [_i, _i, _i, _i, _i, _i],
     "gsl_gemm_mulgrad_ws_elems": [_i, _i, _i],
     "gsl_gemm_nt_lora_mulgrad": [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _vp, _vp, _i,
                                  _vp, _i, _vp, _l, _l, _vp, _vp, _l, _l, _i, _i, _vp, _i, _f, _i, _vp, _vp],

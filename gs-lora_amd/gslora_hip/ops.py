@@ -248,15 +248,33 @@ def _gemm_shape(A, W, *a, A2=None, **kw):
     return A.shape[0], W.shape[0], A.shape[1], 0 if A2 is None else A2.shape[1]      # M, N, K1, K2
 
 
+def gemm_tile_choice(M, N, K, dtype, has_out2=False, in_kernel_lora=False, f32_mode=None):
+    """The kernel gemm_nt (or gemm_nt_lora) launches for this shape: one of _lib.TILE_* (gsl_gemm_tile_choice; K = K1 + K2)."""
+    return int(L.load().gsl_gemm_tile_choice(int(M), int(N), int(K), gemm_code(dtype, f32_mode), 1 if has_out2 else 0, 1 if in_kernel_lora else 0))
+
+
+def _share_ldo(what, epilogue, out, res, aux, out2):
+    """The kernels index res, the aux of EPI_MUL and the out2 of EPI_BIAS_GELU with the row stride of `out` (ldo): row slices and column
+    blocks are accepted for them, a row stride that differs from out's is refused. Every other aux / out2 (the LayerNorm column vector,
+    the 8-bit GELU' code tensor, the compact [M, 16] copy of STORE) has a layout of its own and must be contiguous."""
+    with_ldo = {"res": res, "aux": aux if epilogue == L.EPI_MUL else None, "out2": out2 if epilogue == L.EPI_BIAS_GELU else None}
+    _need(*(t for t in (res, aux, out2) if not any(t is v for v in with_ldo.values())))
+    for name, t in with_ldo.items():
+        if t is None:
+            continue
+        _need(t, rows_ok=True)
+        if t.dim() < 2 or (t.numel() > t.shape[-1] and t.stride(-2) != out.stride(0)):
+            raise RuntimeError(f"{what}: {name} and out must share one row stride (the kernel indexes {name} with out's leading dimension)")
+
+
 @_profiled(None, _gemm_shape)
 def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, bias=None, res=None, aux=None, out2=None,
             pos=None, cls=None, T=0, p_drop=0.0, seed=0, site=0, tag=None, f32_mode=None):
     """f32_mode: None, or "x3" — float32 tensors only: the products as three bf16 pieces per operand on the bf16 matrix cores (GSL_F32X3;
     f32x3_split_reference states the split). Same tensors, epilogues and dropout masks as the exact-f32 call."""
-    _need(A2, W2, bias, aux, out2, pos, cls)
-    _need(A1, W1, out, res, rows_ok=True)      # lda1 / ldw1 / ldo travel with the call (res shares ldo with out)
-    if res is not None and res.shape[0] > 1 and res.stride(0) != out.stride(0):
-        raise RuntimeError("gemm_nt: res and out must share one row stride")
+    _need(bias, pos, cls)
+    _need(A1, W1, A2, W2, out, rows_ok=True)      # lda / ldw of both K segments and ldo travel with the call
+    _share_ldo("gemm_nt", epilogue, out, res, aux, out2)
     M, K1 = A1.shape
     N = W1.shape[0]
     K2 = 0 if A2 is None else A2.shape[1]
@@ -271,7 +289,9 @@ def gemm_nt(A1, W1, out, *, epilogue=L.EPI_STORE, A2=None, W2=None, alpha=1.0, b
 def gemm_nt_lora(A, W, P, Q, lora_scale, tout, out, *, epilogue=L.EPI_STORE, bias=None, res=None, aux=None, out2=None, p_drop=0.0,
                  seed=0, site=0, tag=None):
     """out = epilogue(A W^T + t Q^T), t = lora_scale * A P^T computed inside the kernel and stored to tout [M,64] (bf16)."""
-    _need(A, W, P, Q, tout, out, bias, res, aux, out2)
+    _need(P, Q, tout, bias)
+    _need(A, W, out, rows_ok=True)
+    _share_ldo("gemm_nt_lora", epilogue, out, res, aux, out2)
     M, K = A.shape
     N = W.shape[0]
     L.check(L.load().gsl_gemm_nt_lora(_p(A), A.stride(0), _p(W), W.stride(0), K, _p(P), P.stride(0), _p(Q), Q.stride(0),
@@ -287,10 +307,15 @@ def gemm_nt_lora_mulgrad(A, W, P, Q, lora_scale, tout, out, aux, U1, G1, g1s, Y2
     G1[n*g1s[0] + j*g1s[1]] (+)= sum_m out[m,n] U1[m,j] and G2[n*g2s[0] + j*g2s[1]] (+)= sum_m Y2[m,n] t[m,j].
     A uint8 aux is the 8-bit GELU' code of EPI_BIAS_GELU_G8; p_drop is then the dropout rate of the forward that wrote it.
     gscale: device {S, 1/S} of a loss-scaled (fp16) backward — G1 / G2 receive the sums multiplied by 1/S."""
-    _need(A, W, P, Q, tout, out, aux, U1, Y2, gscale)
+    aux_u8 = aux.dtype == torch.uint8
+    _need(P, Q, tout, gscale)
+    _need(A, W, out, U1, Y2, rows_ok=True)      # row slices / column blocks: lda, ldw, ldo (out, aux and Y2 share it) and ldu1 travel with the call
+    _need(aux, rows_ok=not aux_u8)               # the 8-bit code tensor is slab-major [N/64][M][64] whatever ldo is: contiguous, no row stride to share
     M, K = A.shape
     N = W.shape[0]
-    if not (out.stride(0) == aux.stride(0) == Y2.stride(0) and U1.stride(1) == 1):
+    if aux_u8 and aux.numel() != M * N:
+        raise RuntimeError("gemm_nt_lora_mulgrad: the 8-bit aux is the code tensor of EPI_BIAS_GELU_G8, M * N bytes")
+    if not (out.stride(0) == Y2.stride(0) and (aux_u8 or aux.stride(0) == out.stride(0)) and U1.stride(1) == 1):
         raise RuntimeError("gemm_nt_lora_mulgrad: out / aux / Y2 must share one row stride")
     lib = L.load()
     need = lib.gsl_gemm_mulgrad_ws_elems(M, N, r)

@@ -137,6 +137,25 @@ GSL_API int gsl_gemm_nt(const void* A1, int lda1, const void* W1, int ldw1, int 
                 const float* pos, const float* cls, int T,
                 float p_drop, uint64_t seed, uint32_t site, gsl_stream_t s);
 
+/* Leading dimensions (elements) of both entry points: lda >= K and ldw >= K of every segment, ldo >= N (STORE_QKV_HM: ldo == N);
+ * a smaller one fails with GSL_ERR_ARG. aux and out2 of the MUL / BIAS_GELU epilogues are indexed with ldo, like res. */
+
+/* The tile rule: the kernel gsl_gemm_nt (in_kernel_lora = 0) or gsl_gemm_nt_lora (in_kernel_lora = 1) launches for a shape — a function
+ * of the shape alone, the same one the launches call. K = K1 + K2; has_out2: GSL_EPI_STORE with the compact second output. The
+ * development build's variant knobs apply after it. Returns a gsl_gemm_tile, or -1 for a dtype the entry point does not take. */
+enum gsl_gemm_tile {
+  GSL_TILE_RING64 = 0,         /* 16-bit: 64x64 tiles, LDS-DMA ring (few rows: up to 256 tiles of 128x128)                 */
+  GSL_TILE_RING64_WIDE = 1,    /* 16-bit: the ring kernel on 64x128 tiles (more 64x64 tiles than resident workgroups)      */
+  GSL_TILE_RING64_KSPLIT = 2,  /* 16-bit: the ring kernel, two wave groups split K (K >= 1024, at most 256 tiles of 64x64)  */
+  GSL_TILE_128 = 3,            /* 16-bit: 128x128 single stage                                                             */
+  GSL_TILE_RING256X128 = 4,    /* 16-bit: 256x128 three-stage ring (N < 512; STORE with out2)                              */
+  GSL_TILE_P8 = 5,             /* 16-bit: 256x256 8-phase                                                                  */
+  GSL_TILE_F32_VALU = 6,       /* f32 / f32x3: 64x64 VALU kernel (N < 128 or M < 64)                                       */
+  GSL_TILE_F32_MFMA = 7,       /* f32: 128x128 matrix-core kernel                                                          */
+  GSL_TILE_F32X3_MFMA = 8      /* f32x3: 128x128 tiles, three bf16 pieces per operand                                      */
+};
+GSL_API int gsl_gemm_tile_choice(int M, int N, int K, int dtype, int has_out2, int in_kernel_lora);
+
 /* Same GEMM with the LoRA rank-r term produced INSIDE the kernel (bf16 only; replaces the two-launch form
  * t = s*(A P^T) [gsl_gemm_nt, N=64] ; out = A W^T + t Q^T [gsl_gemm_nt with a K segment], and saves one full read of A):
  *   out = epilogue(A*W^T + t*Q^T),  t = lora_scale * (A*P^T)

@@ -13,11 +13,11 @@ differs), never below 2e-5: 2.1e-5 to 4.7e-5 here. The kernels' worst lse error 
 The reference is float64 torch on the dtype-rounded inputs: on the CPU for a few items, on the device (plain torch, every item
 compared) for the many-item rows. `uniform` (q = 0) is checked against its closed forms instead."""
 import functools
-import math
 
 import pytest
 import torch
 
+from guard_bands import Banded, ptr
 from oracle import attn_probes as P
 
 pytestmark = pytest.mark.gpu
@@ -256,40 +256,6 @@ def test_development_build_variants_on_the_probes(ops, monkeypatch, variant, T, 
 
 
 # ---------------------------------------------------------------------------------------------------------------- guard bands
-BAND = 16384            # elements in front of and behind every view: a multiple of 64, so a view keeps its 16-byte alignment
-SENTINEL = {2: (torch.int16, 0x5A5A), 4: (torch.int32, 0x5A5A5A5A)}
-
-
-class Banded:
-    """A view of `shape` in the middle of a larger buffer. Inputs: the bands are NaN. Outputs: the whole buffer holds a sentinel bit
-    pattern (a finite, huge number in every dtype, so an element the kernel leaves unwritten misses the reference)."""
-
-    def __init__(self, shape, dtype, src=None):
-        n = math.prod(shape)
-        self.buf = torch.empty(2 * BAND + n, device="cuda", dtype=dtype)
-        self.itype, self.sent = SENTINEL[self.buf.element_size()]
-        self.n, self.is_input = n, src is not None
-        self.view = self.buf[BAND:BAND + n].view(shape)
-        if self.is_input:
-            self.buf.fill_(float("nan"))
-            self.view.copy_(src)
-            self.before = self.buf.view(self.itype).clone()
-        else:
-            self.buf.view(self.itype).fill_(self.sent)
-        assert self.view.data_ptr() % 16 == 0
-
-    def bands_intact(self):
-        bits = self.buf.view(self.itype)
-        lo, hi = bits[:BAND], bits[BAND + self.n:]
-        if self.is_input:
-            return torch.equal(bits, self.before)
-        return bool((lo == self.sent).all() and (hi == self.sent).all())
-
-
-def ptr(b):
-    return None if b is None else b.view.data_ptr()
-
-
 GUARD = ([("dense", 2, 2, T, dt, lay) for T in T_NKT14 for dt in H16 for lay in (0, 1)]
          + [("dense", 2, 2, T, F32, 0) for T in T_F32]
          + [("dense", 2, 1, T, dt, lay) for T in T_LONG for dt, lay in ((F32, 0), (BF16, 0), (BF16, 1), (F16, 0), (F16, 1))]

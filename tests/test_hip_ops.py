@@ -58,9 +58,11 @@ def test_gemm_store_asymmetric(ops, dt):
 @pytest.mark.parametrize("dt", DTS)
 # the last two shapes (170 images x 197 tokens: 131 M-tiles of 256 with a ragged last tile) run the 8-phase 256x256 kernel and its
 # staged full-row epilogues in bf16 mode
-# tile choice by shape (bf16): the first four run the 64x64 ring kernel (<= 256 tiles of 128x128), (2600, 2048) the 128x128 kernel,
-# (9000, 64) the 256x128 ring, the 33 490-row shapes the 256x256 8-phase kernel
-# ((1576, 2048, ..): 800 tiles of 64x64 exceed the resident workgroups -> the 64x128 form of the ring kernel)
+# tile choice by shape (16-bit; gsl_gemm_tile_choice): up to 256 tiles of 128x128 run the 64-row ring kernel — (591, 192), (130, 64), (257, 2048)
+# and (9000, 64) (36 tiles of 256x256, 71 of 128x128) its 64x64 form, (788, 512), (1576, 512) and (900, 512) the K-split form (K >= 1024, at most
+# 256 tiles of 64x64), (1576, 2048) the 64x128 form (800 tiles of 64x64 exceed the resident workgroups) —, (2600, 2048) the 128x128 kernel, the
+# 33 490-row shapes the 256x256 8-phase kernel. No shape here reaches the 256x128 three-stage ring (M >= 1024, at least 128 tiles of 256x256,
+# N < 512): tests/test_hip_gemm_edges.py runs it, and asserts the tile of every shape it names.
 @pytest.mark.parametrize("M,N,K1,K2", [(591, 192, 128, 64), (130, 64, 64, 0), (257, 2048, 512, 64), (788, 512, 2048, 64), (1576, 2048, 512, 64), (1576, 512, 1536, 0), (900, 512, 1088, 64),
                                        (2600, 2048, 512, 64), (9000, 64, 512, 0), (33490, 512, 192, 0), (33490, 2048, 512, 64)])
 def test_gemm_epilogues(ops, dt, M, N, K1, K2):
