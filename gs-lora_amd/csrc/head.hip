@@ -121,10 +121,153 @@ __global__ __launch_bounds__(1024) void head_fwd_kernel(const X* __restrict__ x,
   }
 }
 
+// ------------------------------------------------------------------ K10t class-tiled head, C > HEAD_TILED_C
+// The per-image kernels above and below read all of Wn once per image and (the backward) keep an image's dlogits row in LDS: fine at
+// C = 100, refused or ruinous at the 10 572 / 85 742 / 93 431 identities face transformers train on. Above HEAD_TILED_C classes the four
+// entry points run the head's two products as tiled f32 GEMMs on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain per output —
+// the instruction of gemm_f32_mfma_kernel), so Wn is read once per image TILE:
+//   forward   head_fwd_kernel(logits = NULL) writes emb / mean / rstd, then head_logits_tiled_kernel: logits tile = emb tile . Wn tile^T
+//   backward  head_de_tiled_kernel: d e-hat [B, D] = (s dlogits, the ArcFace label column times d phi) . Wn into the workspace, ONCE, then
+//             head_bwd_kernel<.., WS = true>, which takes d e-hat from there (twice in the loss-scaled form, as ever: it is cheap)
+// Every output element is one chain over ascending k that starts at 0 and runs over zero-filled padding to the K tile's end: the value of
+// row b depends on neither B nor the tile b falls in. Rows / columns past B, C, D are never read (clamped row, or a zero in its place)
+// and never written. No LDS array is sized by C. Index arithmetic on [B, C] / [C, D] is size_t; the entry points hold B C and C D below 2^31.
+constexpr int HEAD_TILED_C = 1024;      // C <= this: the per-image kernels, bit for bit what they always computed
+typedef __attribute__((ext_vector_type(4))) float head_f32x4_t;
+constexpr int HT_BK = 32;               // K tile of the logits kernel: 32 columns of D
+constexpr int HT_LDA = HT_BK + 4;       // row stride of a [row][k] panel: 36 r + fc covers the 64 banks once over a fragment read
+constexpr int HL_BM = 64, HL_BN = 128;  // logits tile: images x classes; 4 waves of 32 x 64 (2 x 4 fragments)
+
+__device__ __forceinline__ float4 keep4(bool keep, float4 v) {      // v, or zeros for a chunk outside the tensor
+  return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void head_logits_tiled_kernel(const float* __restrict__ emb, const float* __restrict__ Wn,
+                                                                const int64_t* __restrict__ label, float* __restrict__ logits, int B,
+                                                                int D, int C, float cs, float cm, const float* __restrict__ hbias,
+                                                                int linear, ArcMargin arc, float* __restrict__ cos_y) {
+  fp16_sat_on();
+  __shared__ __attribute__((aligned(16))) float As[HL_BM * HT_LDA];
+  __shared__ __attribute__((aligned(16))) float Ws[HL_BN * HT_LDA];
+  __shared__ float invs[HL_BM];
+  __shared__ int labs[HL_BM];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // image tiles fastest: the workgroups in flight together share a few class tiles of Wn (21.6 MB at C = 10 572, D = 512) in L2
+  const int nbm = (B + HL_BM - 1) / HL_BM;
+  const int m0 = (blockIdx.x % nbm) * HL_BM, n0 = (blockIdx.x / nbm) * HL_BN;
+  // 1 / max(||emb_b||, 1e-12) of the tile's images: a wave per row, lanes over d, one wave reduction — the order is fixed by D alone
+  for (int r = wave; r < HL_BM; r += 4) {
+    const int b = m0 + r;
+    float inv = 1.0f;
+    int lab = -1;
+    if (b < B) {
+      if (!linear) {
+        float ss = 0.f;
+        for (int d = lane; d < D; d += 64) { const float v = emb[(size_t)b * D + d]; ss += v * v; }
+        inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+      }
+      if (label) { const int64_t y = label[b]; lab = (y >= 0 && y < C) ? (int)y : -1; }
+    }
+    if (lane == 0) { invs[r] = inv; labs[r] = lab; }
+  }
+  const int lrow = tid >> 3, lch = (tid & 7) * 4;      // staging: 32 rows x 8 float4 per pass
+  float4 ra[HL_BM / 32], rw[HL_BN / 32];
+  // Every load is unconditional on a clamped (in-bounds) address and what lies outside the tensor is replaced by zero afterwards: a
+  // load under a condition compiles to a branch with its own s_waitcnt vmcnt(0), i.e. one memory round trip per load instead of per tile.
+  auto fetch = [&](int k0) {
+    const bool kin = k0 + lch < D;      // (D % 4 == 0: a float4 lies inside the row or outside it)
+    const int kc = min(k0 + lch, D - 4);
+#pragma unroll
+    for (int i = 0; i < HL_BM / 32; ++i) {
+      const int gm = min(m0 + lrow + 32 * i, B - 1);
+      ra[i] = *reinterpret_cast<const float4*>(emb + (size_t)gm * D + kc);
+    }
+#pragma unroll
+    for (int i = 0; i < HL_BN / 32; ++i) {
+      const int gn = min(n0 + lrow + 32 * i, C - 1);
+      rw[i] = *reinterpret_cast<const float4*>(Wn + (size_t)gn * D + kc);
+    }
+#pragma unroll
+    for (int i = 0; i < HL_BM / 32; ++i) ra[i] = keep4(kin, ra[i]);
+#pragma unroll
+    for (int i = 0; i < HL_BN / 32; ++i) rw[i] = keep4(kin, rw[i]);
+  };
+  head_f32x4_t acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = head_f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const int fr = lane & 15, fc = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int nk = (D + HT_BK - 1) / HT_BK;
+  fetch(0);
+  for (int kt = 0; kt < nk; ++kt) {
+#pragma unroll
+    for (int i = 0; i < HL_BM / 32; ++i) *reinterpret_cast<float4*>(&As[(lrow + 32 * i) * HT_LDA + lch]) = ra[i];
+#pragma unroll
+    for (int i = 0; i < HL_BN / 32; ++i) *reinterpret_cast<float4*>(&Ws[(lrow + 32 * i) * HT_LDA + lch]) = rw[i];
+    wg_barrier_lds();
+    if (kt + 1 < nk) fetch((kt + 1) * HT_BK);      // the next tile's loads fly under this tile's MFMAs
+#pragma unroll
+    for (int ks = 0; ks < HT_BK / 4; ++ks) {
+      float af[2], wf[4];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) af[i] = As[(wm * 32 + i * 16 + fr) * HT_LDA + ks * 4 + fc];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) wf[j] = Ws[(wn * 64 + j * 16 + fr) * HT_LDA + ks * 4 + fc];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], wf[j], acc[i][j], 0, 0, 0);
+    }
+    wg_barrier_lds();      // every wave has read the panels before the next tile overwrites them
+  }
+  // a lane holds images 4 fc + r, class fr of every fragment: a store instruction writes 16 consecutive classes of 4 images
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = wm * 32 + i * 16 + 4 * fc + r, b = m0 + row;
+      if (b >= B) continue;
+      const float inv = invs[row];
+      const int lab = labs[row];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = n0 + wn * 64 + j * 16 + fr;
+        if (c >= C) continue;
+        float dk = acc[i][j][r];
+        float* out = logits + (size_t)b * C + c;
+        if (linear) *out = dk + (hbias ? hbias[c] : 0.f);
+        else if constexpr (KIND == HEAD_ARCFACE) {
+          dk *= inv;
+          if (c == lab) { cos_y[b] = dk; dk = arc_phi(dk, arc); }
+          *out = cs * dk;
+        } else { dk *= inv; *out = cs * ((c == lab) ? (dk - cm) : dk); }
+      }
+    }
+}
+
+// the argument checks of the class-tiled path, for all four entry points (a macro: GSL_CHECK_ARG reports the caller's name)
+// `used`: the call touches the [B, C] / [C, D] tensors at all (logits / dlogits given)
+#define GSL_HEAD_TILED_CHECKS(used)                                                                                                  \
+  GSL_CHECK_ARG(!(used) || C <= HEAD_TILED_C || ((long long)B * C < (1ll << 31) && (long long)C * D < (1ll << 31)),                  \
+                "C out of range: above 1024 classes B*C and C*D must stay below 2^31 elements");                                    \
+  GSL_CHECK_ARG(!(used) || C <= HEAD_TILED_C || ((((uintptr_t)Wn) | ((uintptr_t)emb)) & 15) == 0,                                    \
+                "above 1024 classes Wn and emb must be 16-byte aligned (the tiled kernels load float4)")
+
 template <int KIND>
 static void head_fwd_launch(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
                             const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C, float cos_s,
                             float cos_m, const float* head_bias, int linear_head, int pool_mean, ArcMargin arc, float* cos_y, gsl_stream_t s) {
+  if (logits && C > HEAD_TILED_C) {      // class-tiled: the per-image kernel stops behind emb / mean / rstd, the logits are a GEMM of their own
+    head_fwd_launch<KIND>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, nullptr, B, D, C, cos_s, cos_m, head_bias, linear_head,
+                          pool_mean, arc, cos_y, s);
+    const int nblk = ((B + HL_BM - 1) / HL_BM) * ((C + HL_BN - 1) / HL_BN);
+    hipLaunchKernelGGL((head_logits_tiled_kernel<KIND>), dim3(nblk), dim3(256), 0, as_stream(s), (const float*)emb, Wn, label, logits, B, D, C,
+                       cos_s, cos_m, head_bias, linear_head, arc, cos_y);
+    return;
+  }
   const int nthr = B <= 128 ? 1024 : 256;      // one workgroup per image: with few images give each one 16 waves (100 class rows in two rounds)
   if (x_dtype == GSL_F16)
     hipLaunchKernelGGL((head_fwd_kernel<f16_t, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const f16_t*)x, T, gamma, beta, eps, Wn, label,
@@ -144,6 +287,7 @@ extern "C" int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamm
   GSL_CHECK_ARG(x && gamma && beta && emb && mean && rstd && B > 0 && T > 0, "null/size");
   GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");
   GSL_CHECK_ARG(!logits || (Wn && C > 0), "Wn required for logits");
+  GSL_HEAD_TILED_CHECKS(logits != nullptr);
   head_fwd_launch<HEAD_COSFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
                                 linear_head, pool_mean, ArcMargin{}, nullptr, s);
   return check_launch("gsl_head_fwd");
@@ -164,6 +308,7 @@ extern "C" int gsl_head_fwd_margin(const void* x, int x_dtype, int T, const floa
   GSL_CHECK_ARG(x && gamma && beta && emb && mean && rstd && B > 0 && T > 0, "null/size");
   GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");
   GSL_CHECK_ARG(!logits || (Wn && C > 0), "Wn required for logits");
+  GSL_HEAD_TILED_CHECKS(logits != nullptr);
   GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !linear_head, "ArcFace is a cosine head (linear_head = 0)");
   GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !logits || (label && cos_y), "ArcFace logits need label and cos_y [B]");
   if (head_kind == HEAD_ARCFACE)
@@ -175,12 +320,106 @@ extern "C" int gsl_head_fwd_margin(const void* x, int x_dtype, int T, const floa
   return check_launch("gsl_head_fwd_margin");
 }
 
+// Stage 1 of the class-tiled backward: ws [B, D] = G . Wn with G[b, c] = cs * dlogits[b, c], the ArcFace label column times
+// d phi / d cos at cos_y[b] — head_bwd_kernel's expressions, in its order. One workgroup per (32 images x 64 columns) tile runs the whole
+// class loop, classes ascending in K tiles of 128: a fixed partition, no atomics. Type-independent (f32 in, f32 out).
+// The workgroup is alone on its CU at the flagship shape (B = 1024, D = 512: 256 tiles), so a K tile is a round trip to memory that only
+// its own MFMAs can hide: 128 classes per tile put 48 KB of loads in flight per CU, with a quarter of the barriers of a 32-class tile.
+constexpr int HD_BM = 32, HD_BN = 64;   // d e-hat tile: images x columns; 4 waves of 16 x 32 (1 x 2 fragments)
+constexpr int HD_BK = 128;              // classes per K tile
+constexpr int HD_LDA = HD_BK + 4;       // row stride of the [image][class] panel: 132 fr + fc covers the 64 banks once
+constexpr int HD_LDW = HD_BN + 16;      // row stride of the [class][column] panel of Wn: 80 fc + fr covers the 64 banks once
+
+template <int KIND>
+__global__ __launch_bounds__(256) void head_de_tiled_kernel(const float* __restrict__ dlogits, const float* __restrict__ Wn,
+                                                            const int64_t* __restrict__ label, const float* __restrict__ cos_y,
+                                                            float* __restrict__ ws, int B, int D, int C, float cs, ArcMargin arc) {
+  fp16_sat_on();
+  __shared__ __attribute__((aligned(16))) float As[HD_BM * HD_LDA];      // G tile [image][class]
+  __shared__ __attribute__((aligned(16))) float Ws[HD_BK * HD_LDW];      // Wn tile [class][column]
+  __shared__ float dph[HD_BM];
+  __shared__ int labs[HD_BM];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // image tiles fastest: workgroup i runs on XCD i % 8, so an XCD holds every column tile of its image tiles — together they read whole
+  // rows of Wn (all L2 channels; one 256-byte slice per 2 KB row from every workgroup of an XCD camps on two of them) and share dlogits
+  const int nbm = (B + HD_BM - 1) / HD_BM;
+  const int m0 = (blockIdx.x % nbm) * HD_BM, d0 = (blockIdx.x / nbm) * HD_BN;
+  if (tid < HD_BM) {
+    int lab = -1;
+    float dp = 1.0f;
+    if constexpr (KIND == HEAD_ARCFACE) {
+      if (m0 + tid < B) {
+        const int64_t y = label[m0 + tid];
+        if (y >= 0 && y < C) { lab = (int)y; dp = arc_dphi(cos_y[m0 + tid], arc); }
+      }
+    }
+    labs[tid] = lab; dph[tid] = dp;
+  }
+  wg_barrier_lds();
+  const int ak = tid & (HD_BK - 1), ar = tid / HD_BK;   // G staging: 2 rows x 128 classes per pass (rows of dlogits start at any dword)
+  const int wr = tid >> 4, wch = (tid & 15) * 4;        // Wn staging: 16 classes x 16 float4 per pass
+  float ra[HD_BM / 2];
+  float4 rw[HD_BK / 16];
+  // unconditional loads on clamped (in-bounds) addresses, zero selected afterwards for what lies outside (see head_logits_tiled_kernel)
+  const int dc = min(d0 + wch, D - 4);
+  const bool din = d0 + wch < D;
+  auto fetch = [&](int k0) {
+    const int c = k0 + ak, cc = min(c, C - 1);
+#pragma unroll
+    for (int i = 0; i < HD_BM / 2; ++i) ra[i] = dlogits[(size_t)min(m0 + ar + 2 * i, B - 1) * C + cc];
+#pragma unroll
+    for (int i = 0; i < HD_BK / 16; ++i) rw[i] = *reinterpret_cast<const float4*>(Wn + (size_t)min(k0 + wr + 16 * i, C - 1) * D + dc);
+#pragma unroll
+    for (int i = 0; i < HD_BM / 2; ++i) {
+      const int r = ar + 2 * i;
+      float v = (m0 + r < B && c < C) ? cs * ra[i] : 0.f;
+      if constexpr (KIND == HEAD_ARCFACE) { if (c == labs[r]) v *= dph[r]; }
+      ra[i] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < HD_BK / 16; ++i) rw[i] = keep4(din && k0 + wr + 16 * i < C, rw[i]);
+  };
+  head_f32x4_t acc[2];
+  acc[0] = acc[1] = head_f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const int fr = lane & 15, fc = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int nk = (C + HD_BK - 1) / HD_BK;
+  fetch(0);
+  for (int kt = 0; kt < nk; ++kt) {
+#pragma unroll
+    for (int i = 0; i < HD_BM / 2; ++i) As[(ar + 2 * i) * HD_LDA + ak] = ra[i];
+#pragma unroll
+    for (int i = 0; i < HD_BK / 16; ++i) *reinterpret_cast<float4*>(&Ws[(wr + 16 * i) * HD_LDW + wch]) = rw[i];
+    wg_barrier_lds();
+    if (kt + 1 < nk) fetch((kt + 1) * HD_BK);
+#pragma unroll
+    for (int ks = 0; ks < HD_BK / 4; ++ks) {
+      const float af = As[(wm * 16 + fr) * HD_LDA + ks * 4 + fc];
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af, Ws[(ks * 4 + fc) * HD_LDW + wn * 32 + j * 16 + fr], acc[j], 0, 0, 0);
+    }
+    wg_barrier_lds();
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = m0 + wm * 16 + 4 * fc + r;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int d = d0 + wn * 32 + j * 16 + fr;
+      if (b < B && d < D) ws[(size_t)b * D + d] = acc[j][r];
+    }
+  }
+}
+
 // compact != 0 (pool = 'cls' only): dx / dxb are [B, D] — the gradient of the cls rows alone; the stream gradient of every other token is
 // exactly zero and is neither written here nor read by the consumers (the cls-row-only backward of the last block, gsl_layernorm_bwd's
 // dres_cls_T). The dropout counter of element (b, d) stays that of the dense tensor, (b*Tn)*D + d: same masks in both forms.
 // KIND = HEAD_ARCFACE: the label column of dlogits is multiplied by d phi / d cos at cos_y [B] (written by the forward) before
 // the sum over the classes; everything after that is the CosFace code.
-template <typename T, typename S, typename X, int KIND>
+// WS = true (stage 2 of the class-tiled backward, C > HEAD_TILED_C): d e-hat [B, D] was left in the workspace by head_de_tiled_kernel and
+// arrives through the Wn argument; the class loop and dl[] do not exist in these instantiations, everything else is the code below.
+template <typename T, typename S, typename X, int KIND, bool WS = false>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ demb_in,
                                                        const X* __restrict__ x, int Tn, const float* __restrict__ gamma,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -247,18 +486,22 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   float nn = 0.f;
   for (int d = tid; d < D; d += 256) nn += er[d] * er[d];
   const float nrm = fmaxf(sqrtf(block_sum(nn, sm)), 1e-12f);
-  if (dlogits) {
-    for (int c = tid; c < C; c += 256) dl[c] = cs * dlogits[(size_t)b * C + c];
-    if constexpr (KIND == HEAD_ARCFACE) {      // the thread that stored dl[y] rescales it: no barrier needed in between
-      const long y = (long)label[b];
-      if (y >= 0 && y < C && tid == (int)(y & 255)) dl[y] *= arc_dphi(cos_y[b], arc);
+  if constexpr (!WS) {
+    if (dlogits) {
+      for (int c = tid; c < C; c += 256) dl[c] = cs * dlogits[(size_t)b * C + c];
+      if constexpr (KIND == HEAD_ARCFACE) {      // the thread that stored dl[y] rescales it: no barrier needed in between
+        const long y = (long)label[b];
+        if (y >= 0 && y < C && tid == (int)(y & 255)) dl[y] *= arc_dphi(cos_y[b], arc);
+      }
     }
   }
   __syncthreads();
   float dotp = 0.f;
   for (int d = tid; d < D; d += 256) {
     float g = 0.f;
-    if (dlogits) {
+    if constexpr (WS) {
+      if (dlogits) g = Wn[(size_t)b * D + d];
+    } else if (dlogits) {
       for (int c = 0; c < C; ++c) g += dl[c] * Wn[(size_t)c * D + d];
     }
     de[d] = g;                       // d e-hat
@@ -319,18 +562,30 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // tools/emu_operand_precision.py): the largest gradient operand anywhere in the backward is 1.2x the head's, so the chain peaks near 2.5e3
 // (26x below fp16's 65504; stores saturate, they never produce Inf), and the LoRA-gradient error is flat for S between 2^6 and 2^20.
 constexpr int GSL_GRAD_TARGET_EXP = 11;
-template <int KIND>
+template <int KIND, bool WS = false>
 static void head_bwd_launch(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma, const float* mean,
                             const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb, int B, int D, int C, float cos_s, int dtype,
                             int stream_dtype, DropCfg drop, int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int texp,
                             ArcMargin arc, const float* cos_y, const int64_t* label, gsl_stream_t s) {
-#define GSL_HB(T_, S_, X_)                                                                                                          \
+  if constexpr (!WS) {
+    if (C > HEAD_TILED_C) {      // class-tiled: d e-hat once into amax_ws [B, B + B D), then the per-image kernel without its class loop
+      float* de = amax_ws + B;
+      if (dlogits) {
+        const int nblk = ((B + HD_BM - 1) / HD_BM) * ((D + HD_BN - 1) / HD_BN);
+        hipLaunchKernelGGL((head_de_tiled_kernel<KIND>), dim3(nblk), dim3(256), 0, as_stream(s), dlogits, Wn, label, cos_y, de, B, D, C, cos_s, arc);
+      }
+      head_bwd_launch<KIND, true>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, de, dx, dxb, B, D, C, cos_s, dtype, stream_dtype, drop,
+                                  linear_head, pool_mean, compact, gscale, amax_ws, texp, arc, cos_y, label, s);
+      return;
+    }
+  }
+#define GSL_HB(T_, S_, X_)                                                                                                         \
   do {                                                                                                                              \
     if (gscale)                                                                                                                     \
-      hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma, \
+      hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND, WS>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma, \
                          mean, rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, amax_ws,        \
                          (const float*)nullptr, 0, gscale, texp, arc, cos_y, label);                                                 \
-    hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma,   \
+    hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND, WS>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma,   \
                        mean, rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, (float*)nullptr,   \
                        (const float*)(gscale ? amax_ws : nullptr), B, gscale, texp, arc, cos_y, label);                              \
   } while (0)
@@ -351,7 +606,9 @@ static void head_bwd_launch(const float* dlogits, const float* demb, const void*
 // the argument checks of both backward entry points (a macro: GSL_CHECK_ARG reports the caller's name)
 #define GSL_HEAD_BWD_CHECKS()                                                                                                        \
   GSL_CHECK_ARG(x && gamma && mean && rstd && emb && dx && B > 0 && T >= 1, "null/size");                                          \
-  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0 && C <= 1024, "D <= 1024, D%4==0, C <= 1024");                               \
+  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");                                                       \
+  GSL_CHECK_ARG(C <= HEAD_TILED_C || amax_ws, "C > 1024 needs the workspace amax_ws [B*(D+1)] (d e-hat of the class-tiled backward), also without gscale"); \
+  GSL_HEAD_TILED_CHECKS(dlogits != nullptr);                                                                                         \
   GSL_CHECK_ARG(!dlogits || Wn, "Wn required with dlogits");                                                                         \
   GSL_CHECK_ARG(!(compact && pool_mean), "compact cls-row gradients need pool = 'cls'");                                            \
   GSL_CHECK_ARG(!gscale || amax_ws, "gscale (loss-scaled gradients) needs amax_ws [B]");                                            \

@@ -554,6 +554,7 @@ def cosface_prep(W):
 
 
 HEAD_KINDS = {"cosface": 0, "arcface": 1}      # head_kind of gsl_head_fwd_margin / gsl_head_bwd_margin
+HEAD_TILED_C = 1024      # more classes than this: the class-tiled head kernels (csrc/head.hip), whose backward needs B * (D + 1) workspace floats
 
 
 def _head_fwd(entry, margin, x, B, T, D, gamma, beta, eps, Wn, label, cos_s, cos_m, head_bias, linear, pool_mean):
@@ -592,11 +593,13 @@ def _head_bwd(entry, margin, dlogits, demb, x, B, T, D, gamma, mean, rstd, emb, 
     _need(dlogits, demb, x, gamma, mean, rstd, emb, Wn, gscale, *(margin[3:] if margin else ()))
     if gscale is not None and (gscale.numel() < 4 or gscale.dtype != torch.float32):
         raise RuntimeError(f"{entry[4:]}: gscale must be a float32 tensor of 4 elements {{S, 1/S, seen maximum, exponent}}")
-    amax_ws = torch.empty(B, device=x.device, dtype=torch.float32) if gscale is not None else None
+    C = Wn.shape[0] if Wn is not None else 0
+    # above HEAD_TILED_C classes the workspace is required in every mode and also carries d e-hat [B, D] behind the B maxima (gsl_head_bwd)
+    ws_elems = B * (D + 1) if C > HEAD_TILED_C else (B if gscale is not None else 0)
+    amax_ws = torch.empty(ws_elems, device=x.device, dtype=torch.float32) if ws_elems else None
     rows = B if compact else B * T
     dx = torch.empty(rows, D, device=x.device, dtype=stream_dtype)
     dxb = torch.empty(rows, D, device=x.device, dtype=dtype)
-    C = Wn.shape[0] if Wn is not None else 0
     tail = (margin[0], float(margin[1]), 1 if margin[2] else 0, _p(margin[3]), _p(margin[4])) if margin else ()
     L.check(getattr(L.load(), entry)(_p(dlogits), _p(demb), _p(x), code(x.dtype), T, _p(gamma), _p(mean), _p(rstd), _p(emb), _p(Wn), _p(dx),
                                      _p(dxb), B, D, C, float(cos_s), code(dtype), code(stream_dtype), float(p_drop), int(seed), int(site),

@@ -281,7 +281,13 @@ GSL_API int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamma, 
  *   [3] = the exponent E in use: S * max lands in [2^(E-1), 2^E).
  * Pass 1 reads the PREVIOUS backward's [2]: >= 65504 (a 16-bit store saturated) or non-finite -> E drops by 2 (floor 4); below 2^9 with E
  * under target_exp -> E grows by 1; an E outside [4, 15] (the zeroed buffer) -> target_exp. target_exp: 0 = the default 11 (32x headroom at the head;
- * the largest gradient operand of a depth-6 chain measured 1.2x the head's). gsl_adamw_flat / _dev skip the update of a step whose [2] saturated. */
+ * the largest gradient operand of a depth-6 chain measured 1.2x the head's). gsl_adamw_flat / _dev skip the update of a step whose [2] saturated.
+ * Number of classes. Any C >= 1. C <= 1024: the per-image kernels; amax_ws is [B] floats and may be NULL without gscale, as above.
+ * C > 1024: the class-tiled kernels (gsl_head_fwd*: the logits are a tiled f32 GEMM behind the per-image pool + LayerNorm; gsl_head_bwd*:
+ * d e-hat = (s dlogits) . Wn is a tiled f32 GEMM that runs ONCE, also in the loss-scaled form). WORKSPACE CONTRACT for C > 1024: amax_ws is
+ * REQUIRED in every mode, also with gscale == NULL, and holds B*(D+1) floats — [0, B) the per-image maxima as above, [B, B + B*D) d e-hat.
+ * Supported range for C > 1024: B*C and C*D below 2^31 elements, Wn and emb 16-byte aligned; anything else is an argument error by name
+ * before any launch (so is amax_ws == NULL). Results are bit-repeatable, and row b's do not depend on B. */
 GSL_API int gsl_head_bwd(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
                  const float* mean, const float* rstd, const float* emb, const float* Wn,
                  void* dx, void* dxb, int B, int D, int C, float cos_s, int dtype, int stream_dtype,
