@@ -2254,15 +2254,6 @@ static inline constexpr int attn_env(const char*, int dflt) { return dflt; }
 static inline constexpr unsigned long long* attn_stamps() { return nullptr; }
 #endif
 static inline int attn_persistent() { return attn_env("GSL_ATTN_PERSISTENT", 1); }
-static inline int attn_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0; hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) n = pr.multiProcessorCount;
-    else n = 256;
-  }
-  return n;
-}
 static inline int attn_abl() { return attn_env("GSL_ATTN_ABL", 0); }
 // Launch shape of the long-sequence kernels (T > 224): tiles (query tiles of the forward / dQ, key tiles of dK / dV) per workgroup = waves.
 // Blocks of <= 16 tiles; while items * blocks < CUs (few images) an item is split further, down to 4 tiles per workgroup. Returns the
@@ -2270,7 +2261,7 @@ static inline int attn_abl() { return attn_env("GSL_ATTN_ABL", 0); }
 static inline int attn_long_shape(int T, int items, int& nb, dim3& grid) {
   const int nt = (T + 15) / 16;
   nb = (nt + 15) / 16;
-  if ((long)items * nb < attn_num_cus()) nb = std::max(nb, std::min((attn_num_cus() + items - 1) / items, (nt + 3) / 4));
+  if ((long)items * nb < num_cus()) nb = std::max(nb, std::min((num_cus() + items - 1) / items, (nt + 3) / 4));
   const int w = std::max(4, (nt + nb - 1) / nb);      // >= 256 threads: panel_load() covers a panel in two rounds
   nb = (nt + w - 1) / w;
   grid = dim3((unsigned)(((items + 7) / 8) * 8 * nb));
@@ -2302,15 +2293,15 @@ extern "C" int GSL_ENTRY(gsl_attention_fwd)(const void* qkv, void* o, float* lse
   }
   const dim3 grid(B * H), blk(256);
   // (item_remap for the forward: measured +1 % — 212 -> 215 us at B = 1024 —, so the plain order stays; the backward gains 2.3 %: profiles/r04_notes.md)
-  const int imap = (B % 8 == 0 && attn_num_cus() % 8 == 0) ? attn_env("GSL_ATTN_ITEM_REMAP_FWD", 0) : 0;
+  const int imap = (B % 8 == 0 && num_cus() % 8 == 0) ? attn_env("GSL_ATTN_ITEM_REMAP_FWD", 0) : 0;
   if (dtype == GSL_OP16) {
     if (T <= 64) hipLaunchKernelGGL(attn_fwd_bf16_kernel<4>, grid, blk, 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
-    else if (attn_persistent() && T <= 208 && B * H >= 2 * attn_num_cus())
+    else if (attn_persistent() && T <= 208 && B * H >= 2 * num_cus())
     {
-      if (T > 192) hipLaunchKernelGGL((attn_fwd_bf16_pers_kernel<14, true>), dim3(attn_num_cus()), dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, B * H, hm, imap);
-      else hipLaunchKernelGGL((attn_fwd_bf16_pers_kernel<14, false>), dim3(attn_num_cus()), dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, B * H, hm, imap);
+      if (T > 192) hipLaunchKernelGGL((attn_fwd_bf16_pers_kernel<14, true>), dim3(num_cus()), dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, B * H, hm, imap);
+      else hipLaunchKernelGGL((attn_fwd_bf16_pers_kernel<14, false>), dim3(num_cus()), dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, B * H, hm, imap);
     }
-    else if (B * H < attn_num_cus()) hipLaunchKernelGGL((attn_fwd_bf16_kernel<14, 1024>), grid, dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
+    else if (B * H < num_cus()) hipLaunchKernelGGL((attn_fwd_bf16_kernel<14, 1024>), grid, dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
     else hipLaunchKernelGGL(attn_fwd_bf16_kernel<14>, grid, dim3(512), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
   }
 #if GSL_HAS_F32
@@ -2366,10 +2357,10 @@ extern "C" int GSL_ENTRY(gsl_attention_bwd)(const void* qkv, const void* o, cons
       // round 5: every score tile computed once (attn_bwd_merged_kernel; bit-identical to the fused kernel, GSL_ATTN_BWD_MERGED=0 in the dev build)
       // (from 8 items per CU: a persistent workgroup pays its prologue and a ragged last round — at 4.5 items per CU, ViT-B/16 48 + 48 x 12
       //  heads, the fused kernel is 4 % faster per launch: profiles/r05_notes.md)
-      if (T > 192 && T <= 208 && B * H >= attn_env("GSL_ATTN_BWD_MERGED_MIN", 8) * attn_num_cus() && attn_env("GSL_ATTN_BWD_MERGED", 1))
-        hipLaunchKernelGGL((attn_bwd_merged_kernel<14>), dim3(attn_num_cus()), dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, B * H, hm, (attn_num_cus() % 8 == 0) ? imap : 0, stp);
+      if (T > 192 && T <= 208 && B * H >= attn_env("GSL_ATTN_BWD_MERGED_MIN", 8) * num_cus() && attn_env("GSL_ATTN_BWD_MERGED", 1))
+        hipLaunchKernelGGL((attn_bwd_merged_kernel<14>), dim3(num_cus()), dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, B * H, hm, (num_cus() % 8 == 0) ? imap : 0, stp);
       else
-      if (B * H < attn_num_cus()) {      // fewer items than CUs: sixteen waves per item
+      if (B * H < num_cus()) {      // fewer items than CUs: sixteen waves per item
         if (T > 192 && T <= 208) hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<14, true, 1024>), grid, dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, stp, hm, imap);
         else hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<14, false, 1024>), grid, dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, stp, hm, imap);
       }

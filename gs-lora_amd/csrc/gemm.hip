@@ -129,8 +129,10 @@ __device__ __forceinline__ uint32_t gelu_tab_entry(float a, float tab_c4) {
 // N % 4 == 0 is enforced by the host wrapper. v = primary output, g = second output (GELU' of BIAS_GELU).
 // bp: the 4 bias values of columns n..n+3 already in registers (the staged epilogues load them once per wave: a per-fragment
 // global load + s_waitcnt vmcnt(0) serialises the VALU-bound epilogue), or nullptr to load them here.
-// alpha is honoured by the STORE / STORE_F32 / MUL epilogues only (the only callers that pass alpha != 1 are the LoRA
-// down-projections); the host wrapper rejects alpha != 1 for the others.
+// alpha is applied here for the STORE / STORE_F32 / MUL / MUL_G8 epilogues only (the only callers that pass alpha != 1 are the LoRA
+// down-projections), and the staged epilogues of the others differ: epilogue_staged_res_f32 multiplies by it, the 16-bit residual, patch and
+// table-GELU ones do not. So gsl_gemm_nt refuses alpha != 1 for every epilogue that runs as another EPI than these four, and for the STORE_LN
+// forms (EPI_ALPHA1 in check_epilogue).
 // HASW: w0 is the first-stage dropout hash value of the fragment's first element pair (drop_w0), advanced by the caller with one
 // add per fragment instead of a 64-bit index and a quarter-rate multiply here.
 template <int EPI, typename T, bool HASW = false>
@@ -963,7 +965,7 @@ __device__ __forceinline__ void epilogue_staged_res_bf16_impl(const EpiArgs& e, 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         f32x4_t v = acc[q * 4 + ii][j];
-        *reinterpret_cast<f32x4_t*>(cst + (ii * 16 + fr) * CLF + j * 16 + fc * 4) = v;      // (alpha is 1 for this epilogue: the host rejects anything else)
+        *reinterpret_cast<f32x4_t*>(cst + (ii * 16 + fr) * CLF + j * 16 + fc * 4) = v;      // (no alpha multiply: check_epilogue refuses alpha != 1 for this epilogue, EPI_ALPHA1)
       }
     __builtin_amdgcn_sched_barrier(0);      // the next round's rows are requested AFTER this round's 64 accumulator registers are staged (free)
     if (q + 1 < NQ) fetch(q + 1, (q & 1) ? rsa : rsb);
@@ -2149,7 +2151,7 @@ __global__ __launch_bounds__(256) void gemm_f32x3_mfma_kernel(const float* __res
 }
 #endif
 
-// ---- The tile rule: shape -> kernel, written once. launch_gemm, gemm_nt_lora_rows and the exported gsl_gemm_tile_choice call it; the development
+// ---- The tile rule: shape -> kernel, written once. launch_op16, launch_f32 and the exported gsl_gemm_tile_choice call it; the development
 // knobs apply after it. Measured on MI355X at M = 201 728 (profiles/r01_gemm_ab.md): N >= 512 wants the 256x256 8-phase tile (also for the VALU-heavy
 // BIAS_GELU epilogue), skinny N the 256x128 ring. Fewer than 128 tiles of 256x256 cannot fill the 256 CUs: the 128x128 kernel (4x the workgroups)
 // wins there (measured at M = 1576: 15-44 us vs 19-58 us per GEMM); from ~150 tiles on the 8-phase kernel is ahead. Up to ~256 tiles of 128x128 (one
@@ -2218,197 +2220,98 @@ static inline int mrev_for(int key) {
 #endif
 }
 
-// workgroups of the persistent kernels: one per CU
-#if GSL_P8_PERSISTENT
-static inline int p8p_grid() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0; hipDeviceProp_t pr;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    n -= n % 8;      // xcd_remap of the sequence numbers assumes seq % 8 = blockIdx % 8
-    if (n < 8) n = 8;
-  }
-  return n;
+// ---- One GEMM call as the host side passes it around: each extern "C" entry fills one from its arguments (new_call + assignments by name), checks
+// it, and everything below takes const GemmCall&. The plain form has lora = false and a zero LoraInk; the in-kernel-LoRA form has one K segment.
+struct GemmCall {
+  const void* A1; int lda1; const void* W1; int ldw1; int K1;
+  const void* A2; int lda2; const void* W2; int ldw2; int K2;
+  int dtype;         // GSL_OP16, GSL_F32 or GSL_F32X3
+  int epilogue;      // as the caller named it (gsl_epilogue)
+  int epi;           // the kernels' EPI template value that runs it (check_epilogue)
+  hipStream_t st;
+  EpiArgs e;
+  LoraInk lk; bool lora;
+};
+// a call with nothing but the launch knobs set: alpha 1, no operands, no dropout
+static inline GemmCall new_call(int dtype, int epilogue, gsl_stream_t s, bool allow_krot) {
+  GemmCall c{};
+  c.dtype = dtype; c.epilogue = epilogue; c.st = as_stream(s);
+  c.e.alpha = 1.0f; c.e.drop = make_drop(0.f, 0, 0);
+  set_launch_knobs(c.e, allow_krot);
+  return c;
 }
-#endif
 
-template <int EPI>
-static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int ldw1, int K1, const void* A2,
-                       int lda2, const void* W2, int ldw2, int K2, const EpiArgs& e_in, hipStream_t st) {
-  const EpiArgs& e = e_in;
-  if (dtype == GSL_OP16) {
-    const int nblk = ((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
-    // the tile rule (gemm_tile_choice) as the variant numbers the development knobs speak: 1 = 128x128 single stage, 3 = 256x128 three-stage
-    // ring, 8 = 256x256 8-phase ping-pong, 12 = the 64-row ring kernel
-    const int tile = gemm_tile_choice(e.M, e.N, K1 + K2, GSL_OP16, EPI == GSL_EPI_STORE && e.out2, false);
-    int variant = tile == GSL_TILE_P8 ? 8 : tile == GSL_TILE_RING256X128 ? 3 : tile == GSL_TILE_128 ? 1 : 12;
-#define GSL_LAUNCH(KERNEL, NB, NT) hipLaunchKernelGGL(KERNEL, dim3(NB), dim3(NT), 0, st, (const bf16_t*)A1, lda1, (const bf16_t*)W1, \
-                                                      ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, e)
-#ifdef GSL_DEV
-    // development knobs: GSL_GEMM_VARIANT = 1 / 3 / 8 or the lab kernels 4 (256x256 two-stage), 9 (256x128x32, two workgroups per CU),
-    // 10 (persistent ping-pong), 11 (in-wave pipelined); GSL_GEMM_ABL = main-loop ablation of the ring kernel (tools/bench_gemm_abl.py)
-    const char* ev = getenv("GSL_GEMM_VARIANT");
-    if (ev) variant = atoi(ev);
-    if (EPI == GSL_EPI_BIAS_GELU && !ev && variant == 8) { const char* gv = getenv("GSL_GELU_VARIANT"); if (gv) variant = atoi(gv); }
-    if (variant == 10 && (K1 + K2) >= 192 && (e.N % 8) == 0 && (e.ldo % 8) == 0 && e.N >= 8) {
-      if constexpr (EPI == GSL_EPI_STORE || EPI == GSL_EPI_BIAS_GELU) {
-        EpiArgs e = e_in;
-        { const char* ab = getenv("GSL_PP_ABL"); e.T = ab ? atoi(ab) : 0; }
-        const int ntm = (e.M + PP_TM - 1) / PP_TM, ntn = (e.N + PP_TN - 1) / PP_TN;
-        const int nunits = ntm * ((ntn % 2 == 0) ? 2 : 1);
-        int grid = nunits < 256 ? nunits : 256;
-        hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI>), dim3(grid), dim3(512), 0, st, (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1,
-                           (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, e);
-        return check_launch("gsl_gemm_nt(pp)");
-      }
-    }
-    if (variant == 11 && (e.M % IW_TM) == 0 && (e.N % IW_TN) == 0 && (e.ldo % 8) == 0 && (K1 % 64) == 0 && (K2 % 64) == 0 &&
-        ((K1 + K2) == 512 || (K1 + K2) == 576) && (EPI != GSL_EPI_BIAS_GELU || e.out2)) {
-      if constexpr (EPI == GSL_EPI_STORE || EPI == GSL_EPI_BIAS_GELU) {
-        EpiArgs e = e_in;
-        { const char* ab = getenv("GSL_PP_ABL"); e.T = ab ? atoi(ab) : 0; }
-        const int ntm = e.M / IW_TM, ntn = e.N / IW_TN;
-        const int nunits = ntm * ((ntn % 2 == 0) ? 2 : 1);
-        const int grid = nunits < 256 ? nunits : 256;
-        if ((K1 + K2) == 576)
-          hipLaunchKernelGGL((gemm_bf16_iw_kernel<EPI, 9>), dim3(grid), dim3(512), 0, st, (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1,
-                             (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, e);
-        else
-          hipLaunchKernelGGL((gemm_bf16_iw_kernel<EPI, 8>), dim3(grid), dim3(512), 0, st, (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1,
-                             (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, e);
-        return check_launch("gsl_gemm_nt(iw)");
-      }
-    }
-    if constexpr (EPI != GSL_EPI_BIAS_RES_BF16 && EPI != GSL_EPI_PATCH_BF16 && EPI != GSL_EPI_MUL_G8 && EPI != GSL_EPI_BIAS_GELU_G8) {
-      if (variant == 9) {
-        EpiArgs e9 = e;
-        if (EPI != GSL_EPI_PATCH) { const char* sg = getenv("GSL_STAGGER"); e9.T = sg ? atoi(sg) : 0; }
-        hipLaunchKernelGGL(gemm_bf16_k32x2_kernel<EPI>, dim3(((e.M + 255) / 256) * ((e.N + 127) / 128)), dim3(512), 0, st, (const bf16_t*)A1, lda1,
-                           (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, e9);
-        return check_launch("gsl_gemm_nt(k32x2)");
-      }
-      if (variant == 4) {
-        GSL_LAUNCH(gemm_bf16_t256_kernel<EPI>, ((e.M + BM4 - 1) / BM4) * ((e.N + BN4 - 1) / BN4), 512);
-        return check_launch("gsl_gemm_nt(t256)");
-      }
-    }
-    if constexpr (EPI == GSL_EPI_STORE) {      // probe: W fragments straight from L2 into registers (13 full, 14 A-DMA stream alone, 15 A-DMA + W loads alone)
-      if (variant >= 13 && variant <= 15) {
-        const int nb3 = ((e.M + BM3 - 1) / BM3) * ((e.N + BN3 - 1) / BN3);
-        if (variant == 13) GSL_LAUNCH((gemm_bf16_ring3w_kernel<EPI, 0>), nb3, 512);
-        else if (variant == 14) GSL_LAUNCH((gemm_bf16_ring3w_kernel<EPI, 1>), nb3, 512);
-        else GSL_LAUNCH((gemm_bf16_ring3w_kernel<EPI, 2>), nb3, 512);
-        return check_launch("gsl_gemm_nt(ring3w probe)");
-      }
-    }
-    if constexpr (EPI == GSL_EPI_STORE) {
-      const char* ab = getenv("GSL_GEMM_ABL");
-      const int abl = ab ? atoi(ab) : 0;
-      if (variant == 3 && abl) {
-        const int nb3 = ((e.M + BM3 - 1) / BM3) * ((e.N + BN3 - 1) / BN3);
-        switch (abl) {
-          case 1: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 1>), nb3, 512); break;
-          case 2: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 2>), nb3, 512); break;
-          case 3: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 3>), nb3, 512); break;
-          case 4: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 4>), nb3, 512); break;
-          case 5: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 5>), nb3, 512); break;
-          case 6: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 6>), nb3, 512); break;
-          case 9: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 9>), nb3, 512); break;
-          default: GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 11>), nb3, 512);
-        }
-        return check_launch("gsl_gemm_nt(ring3 ablation)");
-      }
-    }
-#endif
-#if GSL_P8_PERSISTENT
-    if constexpr (EPI == GSL_EPI_STORE) {
-      // plain-store GEMMs (QKV, out-proj dX, QKV dX, LoRA-free dX) with at least two rounds of tiles: the persistent form (see the kernel)
-      const int nt8 = ((e.M + BM4 - 1) / BM4) * ((e.N + BN4 - 1) / BN4);
-      if (variant == 8 && (e.N % 8) == 0 && (e.ldo % 8) == 0 && nt8 >= 2 * p8p_grid()) {
-        hipLaunchKernelGGL((gemm_bf16_p8p_kernel<EPI>), dim3(p8p_grid()), dim3(512), 0, st, (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1,
-                           (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, nt8, e);
-        return check_launch("gsl_gemm_nt(p8p)");
-      }
-    }
-#endif
-#ifdef GSL_DEV
-    if constexpr (EPI == GSL_EPI_STORE) {
-      // development (GSL_W4=1): plain-store GEMMs on the 4-wave 32x32x16 kernel where its shape rules hold (gemm_w4.inc; measured alternative)
-      const char* w = getenv("GSL_W4");
-      if (w && atoi(w) == 1 && variant == 8 && w4_usable(e.M, e.N, K1, K2, lda1, ldw1, e.ldo)) {
-        hipLaunchKernelGGL((gemm_op16_w4_kernel<EPI>), dim3(((e.M + 255) / 256) * (e.N / 256)), dim3(256), 0, st, (const op16_t*)A1, lda1,
-                           (const op16_t*)W1, ldw1, K1, e);
-        return check_launch("gsl_gemm_nt(w4)");
-      }
-    }
-#endif
-#ifdef GSL_DEV
-    if constexpr (EPI == GSL_EPI_STORE || EPI == GSL_EPI_BIAS_GELU_G8) {
-      // development (GSL_O4=1): the plain-store and fused-FFN1 GEMMs of the 8-phase class on the overlap kernel where its shape rules hold
-      // (gemm_o4.inc; a measured alternative). GSL_O4_ONE_PER_CU=1: 16 KB of dynamic LDS on top = one workgroup per CU.
-      const char* o = getenv("GSL_O4");
-      if (o && atoi(o) != 0 && variant == 8 && !(EPI == GSL_EPI_STORE && e.out2) && o4_usable(e.M, e.N, K1, K2, lda1, ldw1, lda2, ldw2, e.ldo)) {
-        const char* o1 = getenv("GSL_O4_ONE_PER_CU");
-        const int o4_dyn = (o1 && atoi(o1)) ? 16384 : 0;
-        hipLaunchKernelGGL((gemm_op16_o4_kernel<EPI>), dim3(((e.M + O4_BM - 1) / O4_BM) * (e.N / O4_BN)), dim3(256), o4_dyn, st, (const op16_t*)A1, lda1,
-                           (const op16_t*)W1, ldw1, K1, (const op16_t*)A2, lda2, (const op16_t*)W2, ldw2, K2, e);
-        return check_launch("gsl_gemm_nt(o4)");
-      }
-    }
-#endif
-    if (variant == 8) {
-      EpiArgs e8 = e;
-      e8.mrev = mrev_for(EPI == GSL_EPI_STORE ? (e.N > K1 ? 0 : (e.N < K1 ? 11 : 12)) : EPI);
-      hipLaunchKernelGGL((gemm_bf16_p8_kernel<EPI, false>), dim3(((e.M + BM4 - 1) / BM4) * ((e.N + BN4 - 1) / BN4)), dim3(512), 0, st,
-                         (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, LoraInk{}, e8);
-    } else if (variant == 3) {
-      GSL_LAUNCH((gemm_bf16_ring3_kernel<EPI, 0>), ((e.M + BM3 - 1) / BM3) * ((e.N + BN3 - 1) / BN3), 512);
-    } else if (variant == 12) {
-      const int ring = small_ring_tile(e.M, e.N, K1 + K2);
-      if (ring == GSL_TILE_RING64_WIDE)
-        hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, false, 4>), dim3(((e.M + BMS - 1) / BMS) * ((e.N + 2 * BNS - 1) / (2 * BNS))), dim3(256), 0, st,
-                           (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, LoraInk{}, e);
-      else if (ring == GSL_TILE_RING64_KSPLIT)
-        hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, false, 2, 2>), dim3(((e.M + BMS - 1) / BMS) * ((e.N + BNS - 1) / BNS)), dim3(512), 0, st,
-                           (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, LoraInk{}, e);
-      else
-        hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, false, 2>), dim3(((e.M + BMS - 1) / BMS) * ((e.N + BNS - 1) / BNS)), dim3(256), 0, st,
-                           (const bf16_t*)A1, lda1, (const bf16_t*)W1, ldw1, K1, (const bf16_t*)A2, lda2, (const bf16_t*)W2, ldw2, K2, LoraInk{}, e);
-    } else {
-      GSL_LAUNCH((gemm_bf16_glds_kernel<EPI, 1>), nblk, 256);
-    }
-#undef GSL_LAUNCH
-  }
-#if GSL_HAS_F32
-  else {
-    // the matrix-core kernel or the 64x64 VALU kernel, by the tile rule (gemm_tile_choice)
-    // (development build: GSL_F32_VALU=1 forces the VALU kernel at every shape — the switch for parity debugging should the MFMA's 4-term
-    //  accumulation ever stop being a k-ordered fmaf chain on another part or compiler; tests/test_hip_ops.py compares the two directly)
-#ifdef GSL_DEV
-    const char* fv = getenv("GSL_F32_VALU");
-    const bool force_valu = fv && atoi(fv) != 0;
-#else
-    constexpr bool force_valu = false;
-#endif
-    if (gemm_tile_choice(e.M, e.N, K1 + K2, dtype, false, false) != GSL_TILE_F32_VALU && !force_valu) {
-      EpiArgs ef = e;
-      ef.remap = 1;
-      const int nblk = ((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
-      if (dtype == GSL_F32X3)      // the same tiles with the products on the bf16 matrix cores (three-piece split, six products: the kernel's comment)
-        hipLaunchKernelGGL(gemm_f32x3_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
-                           ldw1, K1, (const float*)A2, lda2, (const float*)W2, ldw2, K2, ef);
-      else
-        hipLaunchKernelGGL(gemm_f32_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
-                           ldw1, K1, (const float*)A2, lda2, (const float*)W2, ldw2, K2, ef);
-    } else {
-      const int nblk = ((e.M + 63) / 64) * ((e.N + 63) / 64);
-      hipLaunchKernelGGL(gemm_f32_kernel<EPI>, dim3(nblk), dim3(256), 0, st, (const float*)A1, lda1, (const float*)W1,
-                         ldw1, K1, (const float*)A2, lda2, (const float*)W2, ldw2, K2, e);
-    }
-  }
-#endif
-  return check_launch("gsl_gemm_nt");
+// ---- What each epilogue of the ABI needs, and the EPI template value that runs it: one table for gsl_gemm_nt and gsl_gemm_nt_lora.
+// EPI_ALPHA1: not every kernel applies alpha in this epilogue (the staged residual, patch and table-GELU epilogues drop it), so alpha != 1 is refused.
+enum : unsigned {
+  EPI_BIAS = 1u, EPI_RES = 2u, EPI_AUX = 4u, EPI_POS_CLS = 8u, EPI_TOKENS = 16u /* T > 0 */, EPI_OP16_ONLY = 32u, EPI_LDO8 = 64u, EPI_N64 = 128u,
+  EPI_ALPHA1 = 256u, EPI_F16_STREAM = 512u /* EpiArgs::f16 */, EPI_LN = 1024u /* ln_* setup */, EPI_HM = 2048u /* hmT / hmH setup */,
+  EPI_HAS_LORA = 4096u /* an in-kernel-LoRA form exists */
+};
+struct EpiRule { int abi, kernel; unsigned needs; };
+constexpr unsigned EPI_RES16 = EPI_BIAS | EPI_RES | EPI_OP16_ONLY | EPI_LDO8 | EPI_ALPHA1 | EPI_HAS_LORA;
+constexpr unsigned EPI_PATCH = EPI_BIAS | EPI_POS_CLS | EPI_TOKENS | EPI_ALPHA1, EPI_PATCH16 = EPI_PATCH | EPI_OP16_ONLY | EPI_LDO8;
+constexpr unsigned EPI_STORE_LN = EPI_BIAS | EPI_AUX | EPI_POS_CLS | EPI_ALPHA1 | EPI_LN;
+constexpr EpiRule EPI_RULES[] = {
+    {GSL_EPI_STORE, GSL_EPI_STORE, EPI_HAS_LORA},
+    {GSL_EPI_STORE_F32, GSL_EPI_STORE_F32, 0u},
+    {GSL_EPI_STORE_QKV_HM, GSL_EPI_STORE, EPI_OP16_ONLY | EPI_HM},
+    {GSL_EPI_STORE_LN, GSL_EPI_STORE, EPI_STORE_LN},
+    {GSL_EPI_STORE_QKV_HM_LN, GSL_EPI_STORE, EPI_STORE_LN | EPI_OP16_ONLY | EPI_HM},
+    {GSL_EPI_BIAS_RES_F32, GSL_EPI_BIAS_RES_F32, EPI_BIAS | EPI_RES | EPI_ALPHA1 | EPI_HAS_LORA},
+    {GSL_EPI_BIAS_RES_BF16, GSL_EPI_BIAS_RES_BF16, EPI_RES16},
+    {GSL_EPI_BIAS_RES_F16, GSL_EPI_BIAS_RES_BF16, EPI_RES16 | EPI_F16_STREAM},      // the same kernels with the stream element type switched at run time
+    {GSL_EPI_PATCH, GSL_EPI_PATCH, EPI_PATCH},
+    {GSL_EPI_PATCH_BF16, GSL_EPI_PATCH_BF16, EPI_PATCH16},
+    {GSL_EPI_PATCH_F16, GSL_EPI_PATCH_BF16, EPI_PATCH16 | EPI_F16_STREAM},
+    {GSL_EPI_BIAS_GELU, GSL_EPI_BIAS_GELU, EPI_BIAS | EPI_ALPHA1 | EPI_HAS_LORA},
+    {GSL_EPI_BIAS_GELU_G8, GSL_EPI_BIAS_GELU_G8, EPI_BIAS | EPI_OP16_ONLY | EPI_N64 | EPI_ALPHA1 | EPI_HAS_LORA},
+    {GSL_EPI_MUL, GSL_EPI_MUL, EPI_AUX | EPI_HAS_LORA},
+    // aux = 8-bit GELU' codes (slab-major); p_drop = the dropout rate of the forward that wrote them (no mask is applied here)
+    {GSL_EPI_MUL_G8, GSL_EPI_MUL_G8, EPI_AUX | EPI_OP16_ONLY | EPI_N64 | EPI_HAS_LORA},
+};
+constexpr const EpiRule* epi_rule(int abi) {
+  for (const EpiRule& r : EPI_RULES)
+    if (r.abi == abi) return &r;
+  return nullptr;
 }
+// checks c against its epilogue's row and finishes c.e for the kernel (epi, f16, the ln_* and hm* fields)
+static int check_epilogue(GemmCall& c) {
+  EpiArgs& e = c.e;
+  const EpiRule* r = epi_rule(c.epilogue);
+  if (!r || (c.lora && !(r->needs & EPI_HAS_LORA)))
+    return fail(GSL_ERR_ARG, "%s: unknown epilogue, or one without this form: %ld", c.lora ? "gsl_gemm_nt_lora" : "gsl_gemm_nt", c.epilogue);
+  const unsigned needs = r->needs;
+  GSL_CHECK_ARG(!(needs & EPI_BIAS) || e.bias, "this epilogue requires bias");
+  GSL_CHECK_ARG(!(needs & EPI_RES) || e.res, "this epilogue requires res");
+  GSL_CHECK_ARG(!(needs & EPI_AUX) || e.aux, "this epilogue requires aux");
+  GSL_CHECK_ARG(!(needs & EPI_POS_CLS) || (e.pos && e.cls), "this epilogue requires pos and cls (STORE_LN: mean[M] and rstd[M])");
+  GSL_CHECK_ARG(!(needs & EPI_TOKENS) || e.T > 0, "this epilogue requires T > 0");
+  GSL_CHECK_ARG(!(needs & EPI_OP16_ONLY) || c.dtype == GSL_OP16, "this epilogue takes bf16 / fp16 operands only");
+  GSL_CHECK_ARG(!(needs & EPI_LDO8) || (e.ldo % 8) == 0, "this epilogue requires ldo % 8 == 0");
+  GSL_CHECK_ARG(!(needs & EPI_N64) || (e.N % 64) == 0, "this epilogue requires N % 64 == 0 (slab-major code tensor)");
+  GSL_CHECK_ARG(!(needs & EPI_ALPHA1) || e.alpha == 1.0f,
+                "alpha must be 1 for this epilogue (every kernel applies alpha in STORE, STORE_F32, STORE_QKV_HM, MUL and MUL_G8 only)");
+  if (c.epilogue == GSL_EPI_STORE && e.out2 && !c.lora)
+    GSL_CHECK_ARG(c.dtype == GSL_OP16 && e.N >= 16 && e.N <= 128 && !e.bias, "STORE with out2 (compact [M,16] copy of columns 0..15): 16-bit operands, 16 <= N <= 128, no bias");
+  c.epi = r->kernel;
+  e.f16 = (needs & EPI_F16_STREAM) ? 1 : 0;
+  if (needs & EPI_LN) {      // consumer-side LayerNorm: pos = mean [M], cls = rstd [M], aux = c [N] (f32), bias = d [N]
+    GSL_CHECK_ARG(!e.out2, "STORE_LN: no out2");
+    e.ln_mean = e.pos; e.ln_rstd = e.cls; e.ln_c = reinterpret_cast<const float*>(e.aux); e.ln_d = e.bias;
+    e.bias = nullptr; e.aux = nullptr; e.pos = nullptr; e.cls = nullptr;
+    if (!(needs & EPI_HM)) {
+      GSL_CHECK_ARG(e.T >= 0, "STORE_LN: T = 0, or the row stride of mean / rstd (row m reads element m * T: the cls rows of a [B * T] tensor)");
+      e.ln_rs = e.T > 0 ? e.T : 1;
+    }
+  }
+  if (needs & EPI_HM) {      // the STORE kernels with a permuting copy-out: out is [B][H][3][T][64], M = B * T rows, N = 3 * H * 64
+    GSL_CHECK_ARG(e.T >= 8 && (e.M % e.T) == 0 && (e.N % 192) == 0 && e.ldo == e.N, "STORE_QKV_HM: M = B*T (T >= 8), N = 3*H*64, ldo = N");
+    e.hmT = e.T; e.hmH = e.N / 192;
+  }
+  return GSL_OK;
+}
+constexpr bool epi_has_lora(int epi) { return (epi_rule(epi)->needs & EPI_HAS_LORA) != 0; }
 
 // ---- tail split (round 6). The 8-phase kernel runs one 256 x 256 tile per CU at a time, so a launch takes ceil(tiles / CUs) tile times: the
 // N = 512 GEMMs of the step (out-proj forward and dX, QKV dX, FFN1-dX, FFN2 forward: 1 576 tiles on 256 CUs = 6.16 rounds) pay SEVEN — 12 % of
@@ -2416,14 +2319,6 @@ static int launch_gemm(int dtype, const void* A1, int lda1, const void* W1, int 
 // remaining row panels as a second launch, which the tile rule puts on the 64 x 64 ring kernel (640 small workgroups, three per CU: ~0.25 tile
 // times instead of one). Same MFMA instruction, same k order, same epilogue arithmetic: the rows of the tail are bit-identical to what the
 // 8-phase kernel writes (tests/test_hip_ops.py::test_gemm_tail_split_*); their dropout counters continue at row `mbase` (EpiArgs::mbase).
-static inline int gemm_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0; hipDeviceProp_t pr;
-    n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-  }
-  return n;
-}
 #ifndef GSL_TAIL_SPLIT
 #define GSL_TAIL_SPLIT 1
 #endif
@@ -2434,20 +2329,146 @@ static inline int tail_split_rows(int M, int N, int dtype) {
   { const char* t = getenv("GSL_TAIL_SPLIT"); if (t) on = atoi(t) != 0; }
 #endif
   if (!on || dtype != GSL_OP16 || (M % 256) || (N % 256) || N < 512) return 0;
-  const long nt = N / 256, tiles = (long)(M / 256) * nt, ncu = gemm_num_cus();
+  const long nt = N / 256, tiles = (long)(M / 256) * nt, ncu = num_cus();
   if (tiles <= ncu) return 0;
   const long r = tiles % ncu;
   if (r == 0 || r * 10 > ncu * 3 || (r % nt)) return 0;
   return (int)(r / nt) * 256;
 }
-static inline const void* rows_after(const void* p, long rows, long ld, int esize) { return p ? static_cast<const char*>(p) + rows * ld * esize : nullptr; }
-static inline void* rows_after(void* p, long rows, long ld, int esize) { return p ? static_cast<char*>(p) + rows * ld * esize : nullptr; }
+template <typename P> static inline P* rows_after(P* p, long rows, long ld) { return p ? p + rows * ld : nullptr; }
+// the two launches of a split call: the first M - tail rows, and the last `tail` rows (operands, residual and outputs are 2-byte row-major tensors:
+// the tail is a pointer offset; in the in-kernel-LoRA form t = s A P^T of the tail rows goes to tout's tail rows)
+struct GemmSplit { GemmCall head, tail; };
+static GemmSplit split_rows(const GemmCall& c, int tail) {
+  GemmSplit s{c, c};
+  const int head = c.e.M - tail;
+  GemmCall& t = s.tail;
+  s.head.e.M = head;
+  t.e.M = tail; t.e.mbase = head;
+  t.A1 = rows_after((const uint16_t*)c.A1, head, c.lda1);
+  if (c.K2) t.A2 = rows_after((const uint16_t*)c.A2, head, c.lda2);
+  t.e.res = rows_after((const uint16_t*)c.e.res, head, c.e.ldo);
+  t.e.out = rows_after((uint16_t*)c.e.out, head, c.e.ldo);
+  t.lk.tout = rows_after(c.lk.tout, head, c.lk.ldt);
+  return s;
+}
 
-static int gemm_nt_rows(const void* A1, int lda1, const void* W1, int ldw1, int K1, const void* A2, int lda2,
-                        const void* W2, int ldw2, int K2, int M, int N, int dtype, int epilogue, float alpha,
-                        const float* bias, const void* res, const void* aux, void* out, void* out2, int ldo,
-                        const float* pos, const float* cls, int T, float p_drop, uint64_t seed, uint32_t site,
-                        gsl_stream_t s, int mbase);
+#ifdef GSL_DEV
+#include "gemm_dev_launch.inc"
+#endif
+
+// ---- The launch rule of the 16-bit GEMMs: the tile rule names the kernel, and each kernel is launched from exactly one place. LORA: the
+// in-kernel-LoRA form (c.lk, one K segment), which exists on the 8-phase kernel and the 64-row ring kernel — the only tiles the rule gives it.
+template <int EPI, bool LORA>
+static int launch_op16(const GemmCall& c) {
+  const EpiArgs& e = c.e;
+  const bf16_t *A1 = (const bf16_t*)c.A1, *W1 = (const bf16_t*)c.W1, *A2 = (const bf16_t*)c.A2, *W2 = (const bf16_t*)c.W2;
+  int tile = gemm_tile_choice(e.M, e.N, c.K1 + c.K2, GSL_OP16, EPI == GSL_EPI_STORE && e.out2, LORA);
+#ifdef GSL_DEV
+  { int rc; if (dev_launch<EPI, LORA>(c, tile, rc)) return rc; }      // the lab's kernels and knobs (gemm_dev_launch.inc)
+#endif
+  auto tiles = [&](int bm, int bn) { return dim3(((e.M + bm - 1) / bm) * ((e.N + bn - 1) / bn)); };
+  switch (tile) {
+    case GSL_TILE_P8: {
+      EpiArgs e8 = e;
+      e8.mrev = mrev_for(LORA ? 16 + EPI : EPI != GSL_EPI_STORE ? EPI : e.N > c.K1 ? 0 : e.N < c.K1 ? 11 : 12);
+      hipLaunchKernelGGL((gemm_bf16_p8_kernel<EPI, LORA>), tiles(BM4, BN4), dim3(512), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2, c.ldw2,
+                         c.K2, c.lk, e8);
+      break;
+    }
+    case GSL_TILE_RING64_WIDE:
+      hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, LORA, 4>), tiles(BMS, 2 * BNS), dim3(256), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2,
+                         c.ldw2, c.K2, c.lk, e);
+      break;
+    case GSL_TILE_RING64_KSPLIT:
+      hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, LORA, 2, 2>), tiles(BMS, BNS), dim3(512), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2,
+                         c.ldw2, c.K2, c.lk, e);
+      break;
+    case GSL_TILE_RING64:
+      hipLaunchKernelGGL((gemm_bf16_small_kernel<EPI, LORA, 2>), tiles(BMS, BNS), dim3(256), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2,
+                         c.ldw2, c.K2, c.lk, e);
+      break;
+    default:
+      if constexpr (LORA) {
+        return fail(GSL_ERR_UNSUPPORTED, "gsl_gemm_nt_lora: tile %s%ld has no in-kernel-LoRA form", "", tile);
+      } else if (tile == GSL_TILE_RING256X128) {
+        hipLaunchKernelGGL((gemm_bf16_ring3_kernel<EPI, 0>), tiles(BM3, BN3), dim3(512), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2, c.ldw2,
+                           c.K2, e);
+      } else {      // GSL_TILE_128
+        hipLaunchKernelGGL((gemm_bf16_glds_kernel<EPI, 1>), tiles(BM, BN), dim3(256), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2, c.ldw2,
+                           c.K2, e);
+      }
+  }
+  return check_launch(LORA ? "gsl_gemm_nt_lora" : "gsl_gemm_nt");
+}
+
+#if GSL_HAS_F32
+// f32 / f32x3 tensors: the matrix-core kernel or the 64x64 VALU kernel, by the tile rule (gemm_tile_choice)
+// (development build: GSL_F32_VALU=1 forces the VALU kernel at every shape — the switch for parity debugging should the MFMA's 4-term
+//  accumulation ever stop being a k-ordered fmaf chain on another part or compiler; tests/test_hip_ops.py compares the two directly)
+template <int EPI>
+static int launch_f32(const GemmCall& c) {
+  const EpiArgs& e = c.e;
+  const float *A1 = (const float*)c.A1, *W1 = (const float*)c.W1, *A2 = (const float*)c.A2, *W2 = (const float*)c.W2;
+#ifdef GSL_DEV
+  const char* fv = getenv("GSL_F32_VALU");
+  const bool force_valu = fv && atoi(fv) != 0;
+#else
+  constexpr bool force_valu = false;
+#endif
+  if (gemm_tile_choice(e.M, e.N, c.K1 + c.K2, c.dtype, false, false) != GSL_TILE_F32_VALU && !force_valu) {
+    EpiArgs ef = e;
+    ef.remap = 1;
+    const int nblk = ((e.M + BM - 1) / BM) * ((e.N + BN - 1) / BN);
+    if (c.dtype == GSL_F32X3)      // the same tiles with the products on the bf16 matrix cores (three-piece split, six products: the kernel's comment)
+      hipLaunchKernelGGL(gemm_f32x3_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2, c.ldw2, c.K2, ef);
+    else
+      hipLaunchKernelGGL(gemm_f32_mfma_kernel<EPI>, dim3(nblk), dim3(256), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2, c.ldw2, c.K2, ef);
+  } else {
+    const int nblk = ((e.M + 63) / 64) * ((e.N + 63) / 64);
+    hipLaunchKernelGGL(gemm_f32_kernel<EPI>, dim3(nblk), dim3(256), 0, c.st, A1, c.lda1, W1, c.ldw1, c.K1, A2, c.lda2, W2, c.ldw2, c.K2, e);
+  }
+  return check_launch("gsl_gemm_nt");
+}
+#endif
+
+template <int EPI>
+static int launch_epi(const GemmCall& c) {
+  if constexpr (epi_has_lora(EPI)) {
+    if (c.lora) return launch_op16<EPI, true>(c);
+  }
+  if (c.dtype == GSL_OP16) return launch_op16<EPI, false>(c);
+#if GSL_HAS_F32
+  return launch_f32<EPI>(c);
+#else
+  return fail(GSL_ERR_ARG, "gsl_gemm_nt: dtype%s %ld", "", c.dtype);
+#endif
+}
+// one checked call (check_epilogue) -> the kernels of its EPI
+static int launch_rows(const GemmCall& c) {
+  switch (c.epi) {
+    case GSL_EPI_STORE: return launch_epi<GSL_EPI_STORE>(c);
+    case GSL_EPI_STORE_F32: return launch_epi<GSL_EPI_STORE_F32>(c);
+    case GSL_EPI_BIAS_RES_F32: return launch_epi<GSL_EPI_BIAS_RES_F32>(c);
+    case GSL_EPI_BIAS_RES_BF16: return launch_epi<GSL_EPI_BIAS_RES_BF16>(c);
+    case GSL_EPI_PATCH: return launch_epi<GSL_EPI_PATCH>(c);
+    case GSL_EPI_PATCH_BF16: return launch_epi<GSL_EPI_PATCH_BF16>(c);
+    case GSL_EPI_BIAS_GELU: return launch_epi<GSL_EPI_BIAS_GELU>(c);
+    case GSL_EPI_BIAS_GELU_G8: return launch_epi<GSL_EPI_BIAS_GELU_G8>(c);
+    case GSL_EPI_MUL: return launch_epi<GSL_EPI_MUL>(c);
+    case GSL_EPI_MUL_G8: return launch_epi<GSL_EPI_MUL_G8>(c);
+    default: return fail(GSL_ERR_ARG, "gsl_gemm_nt: no kernel for epilogue%s %ld", "", c.epi);
+  }
+}
+// ... as one launch, or as two when the tail split applies: plain STORE and the 16-bit residual epilogues split
+static int launch_tail_split(const GemmCall& c) {
+  const bool splittable = (c.epilogue == GSL_EPI_STORE && !c.e.out2) || c.epilogue == GSL_EPI_BIAS_RES_BF16 || c.epilogue == GSL_EPI_BIAS_RES_F16;
+  const int tail = (splittable && c.e.M >= 1024) ? tail_split_rows(c.e.M, c.e.N, c.dtype) : 0;
+  if (tail <= 0) return launch_rows(c);
+  const GemmSplit s = split_rows(c, tail);
+  const int rc = launch_rows(s.head);
+  return rc ? rc : launch_rows(s.tail);
+}
 
 extern "C" int GSL_ENTRY(gsl_gemm_nt)(const void* A1, int lda1, const void* W1, int ldw1, int K1, const void* A2, int lda2,
                            const void* W2, int ldw2, int K2, int M, int N, int dtype, int epilogue, float alpha,
@@ -2456,27 +2477,6 @@ extern "C" int GSL_ENTRY(gsl_gemm_nt)(const void* A1, int lda1, const void* W1, 
                            gsl_stream_t s) {
   GSL_FORWARD_H16(dtype, h16_gsl_gemm_nt(A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, M, N, dtype, epilogue, alpha, bias, res, aux, out, out2,
                                          ldo, pos, cls, T, p_drop, seed, site, s));
-  // plain STORE and the 16-bit residual epilogues split (operands, residual and output are 2-byte row-major tensors: the tail is a pointer offset)
-  const bool splittable = (epilogue == GSL_EPI_STORE && !out2) || epilogue == GSL_EPI_BIAS_RES_BF16 || epilogue == GSL_EPI_BIAS_RES_F16;
-  const int tail = (splittable && A1 && W1 && out && M >= 1024) ? tail_split_rows(M, N, dtype) : 0;
-  if (tail > 0) {
-    const int head = M - tail;
-    const int rc = gemm_nt_rows(A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, head, N, dtype, epilogue, alpha, bias, res, aux, out, out2, ldo, pos, cls,
-                                T, p_drop, seed, site, s, 0);
-    if (rc) return rc;
-    return gemm_nt_rows(rows_after(A1, head, lda1, 2), lda1, W1, ldw1, K1, K2 ? rows_after(A2, head, lda2, 2) : A2, lda2, W2, ldw2, K2, tail, N, dtype,
-                        epilogue, alpha, bias, rows_after(res, head, ldo, 2), aux, rows_after(out, head, ldo, 2), out2, ldo, pos, cls, T, p_drop, seed, site, s,
-                        head);
-  }
-  return gemm_nt_rows(A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, M, N, dtype, epilogue, alpha, bias, res, aux, out, out2, ldo, pos, cls, T, p_drop, seed,
-                      site, s, 0);
-}
-
-static int gemm_nt_rows(const void* A1, int lda1, const void* W1, int ldw1, int K1, const void* A2, int lda2,
-                        const void* W2, int ldw2, int K2, int M, int N, int dtype, int epilogue, float alpha,
-                        const float* bias, const void* res, const void* aux, void* out, void* out2, int ldo,
-                        const float* pos, const float* cls, int T, float p_drop, uint64_t seed, uint32_t site,
-                        gsl_stream_t s, int mbase) {
   GSL_CHECK_ARG((GSL_HAS_F32 && (dtype == GSL_F32 || dtype == GSL_F32X3)) || dtype == GSL_OP16, "dtype");
   GSL_CHECK_ARG(M > 0 && N > 0 && (N % 4) == 0, "M>0, N>0, N%4==0");
   GSL_CHECK_ARG(K1 > 0 && (K1 % 64) == 0 && K2 >= 0 && (K2 % 64) == 0, "K1,K2 multiples of 64");
@@ -2485,70 +2485,14 @@ static int gemm_nt_rows(const void* A1, int lda1, const void* W1, int ldw1, int 
                 "leading dimensions must keep 16-byte alignment");
   GSL_CHECK_ARG(lda1 >= K1 && ldw1 >= K1 && (K2 == 0 || (lda2 >= K2 && ldw2 >= K2)) && ldo >= N, "leading dimensions: lda >= K, ldw >= K, ldo >= N");
   GSL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "p_drop");
-  EpiArgs e;
-  e.alpha = alpha; e.bias = bias; e.res = res; e.aux = aux; e.out = out; e.out2 = out2; e.ldo = ldo;
-  e.pos = pos; e.cls = cls; e.T = T; e.drop = make_drop(p_drop, seed, site); e.M = M; e.N = N;
-  set_launch_knobs(e, true);
-  e.mbase = mbase;
-  e.hmT = 0; e.hmH = 0;
-  hipStream_t st = as_stream(s);
-  switch (epilogue) {
-    case GSL_EPI_STORE:
-      if (out2) GSL_CHECK_ARG(dtype == GSL_OP16 && N >= 16 && N <= 128 && !bias, "STORE with out2 (compact [M,16] copy of columns 0..15): 16-bit operands, 16 <= N <= 128, no bias");
-      return launch_gemm<GSL_EPI_STORE>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_STORE_F32: return launch_gemm<GSL_EPI_STORE_F32>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_STORE_QKV_HM_LN:
-    case GSL_EPI_STORE_LN:          // consumer-side LayerNorm: pos = mean [M], cls = rstd [M], aux = c [N] (f32), bias = d [N] (required)
-      GSL_CHECK_ARG(pos && cls && aux && bias && !out2 && alpha == 1.0f, "STORE_LN: pos = mean[M], cls = rstd[M], aux = c[N], bias = d[N] (all f32), alpha 1, no out2");
-      e.ln_mean = pos; e.ln_rstd = cls; e.ln_c = reinterpret_cast<const float*>(aux); e.ln_d = bias; e.bias = nullptr; e.aux = nullptr; e.pos = nullptr; e.cls = nullptr;
-      if (epilogue == GSL_EPI_STORE_LN) {
-        GSL_CHECK_ARG(T >= 0, "STORE_LN: T = 0, or the row stride of mean / rstd (row m reads element m * T: the cls rows of a [B * T] tensor)");
-        e.ln_rs = T > 0 ? T : 1;
-        return launch_gemm<GSL_EPI_STORE>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-      }
-      [[fallthrough]];
-    case GSL_EPI_STORE_QKV_HM:      // the STORE kernels with a permuting copy-out: out is [B][H][3][T][64], M = B * T rows, N = 3 * H * 64
-      GSL_CHECK_ARG(dtype == GSL_OP16 && T >= 8 && (M % T) == 0 && (N % 192) == 0 && ldo == N, "STORE_QKV_HM: bf16, M = B*T (T >= 8), N = 3*H*64, ldo = N");
-      e.hmT = T; e.hmH = N / 192;
-      return launch_gemm<GSL_EPI_STORE>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_BIAS_RES_F32:
-      GSL_CHECK_ARG(bias && res, "bias/res required");
-      return launch_gemm<GSL_EPI_BIAS_RES_F32>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_BIAS_RES_F16:      // the same kernels with the stream element type switched at run time (EpiArgs::f16)
-      e.f16 = 1;
-      [[fallthrough]];
-    case GSL_EPI_BIAS_RES_BF16:
-      GSL_CHECK_ARG(bias && res && dtype == GSL_OP16 && (ldo % 8) == 0, "bias/res required, bf16 only");
-      return launch_gemm<GSL_EPI_BIAS_RES_BF16>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_PATCH_F16:
-      e.f16 = 1;
-      [[fallthrough]];
-    case GSL_EPI_PATCH_BF16:
-      GSL_CHECK_ARG(bias && pos && cls && T > 0 && dtype == GSL_OP16 && (ldo % 8) == 0, "bias/pos/cls/T required, bf16 only");
-      return launch_gemm<GSL_EPI_PATCH_BF16>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_BIAS_GELU:
-      GSL_CHECK_ARG(bias, "bias required");
-      return launch_gemm<GSL_EPI_BIAS_GELU>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_MUL:
-      GSL_CHECK_ARG(aux, "aux required");
-      return launch_gemm<GSL_EPI_MUL>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_BIAS_GELU_G8:
-      GSL_CHECK_ARG(bias && dtype == GSL_OP16 && (N % 64) == 0, "bias required, bf16 only, N % 64 == 0 (slab-major code tensor)");
-      return launch_gemm<GSL_EPI_BIAS_GELU_G8>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_MUL_G8:      // aux = 8-bit GELU' codes [M, ldo bytes]; p_drop = the dropout rate of the forward that wrote them (no mask is applied here)
-      GSL_CHECK_ARG(aux && dtype == GSL_OP16 && (N % 64) == 0, "aux required, bf16 only, N % 64 == 0 (slab-major code tensor)");
-      return launch_gemm<GSL_EPI_MUL_G8>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    case GSL_EPI_PATCH:
-      GSL_CHECK_ARG(bias && pos && cls && T > 0, "bias/pos/cls/T required");
-      return launch_gemm<GSL_EPI_PATCH>(dtype, A1, lda1, W1, ldw1, K1, A2, lda2, W2, ldw2, K2, e, st);
-    default: return fail(GSL_ERR_ARG, "gsl_gemm_nt: unknown epilogue%s %ld", "", epilogue);
-  }
+  GemmCall c = new_call(dtype, epilogue, s, true);
+  c.A1 = A1; c.lda1 = lda1; c.W1 = W1; c.ldw1 = ldw1; c.K1 = K1; c.A2 = A2; c.lda2 = lda2; c.W2 = W2; c.ldw2 = ldw2; c.K2 = K2;
+  EpiArgs& e = c.e;
+  e.M = M; e.N = N; e.alpha = alpha; e.bias = bias; e.res = res; e.aux = aux; e.out = out; e.out2 = out2; e.ldo = ldo;
+  e.pos = pos; e.cls = cls; e.T = T; e.drop = make_drop(p_drop, seed, site);
+  if (const int rc = check_epilogue(c)) return rc;
+  return launch_tail_split(c);
 }
-
-static int gemm_nt_lora_rows(const void* A, int lda, const void* W, int ldw, int K, const void* P, int ldp, const void* Q,
-                             int ldq, float lora_scale, void* tout, int ldt, int M, int N, int dtype, int epilogue,
-                             const float* bias, const void* res, const void* aux, void* out, void* out2, int ldo,
-                             float p_drop, uint64_t seed, uint32_t site, gsl_stream_t s, int mbase);
 
 extern "C" int GSL_ENTRY(gsl_gemm_nt_lora)(const void* A, int lda, const void* W, int ldw, int K, const void* P, int ldp, const void* Q,
                                 int ldq, float lora_scale, void* tout, int ldt, int M, int N, int dtype, int epilogue,
@@ -2556,25 +2500,6 @@ extern "C" int GSL_ENTRY(gsl_gemm_nt_lora)(const void* A, int lda, const void* W
                                 float p_drop, uint64_t seed, uint32_t site, gsl_stream_t s) {
   GSL_FORWARD_H16(dtype, h16_gsl_gemm_nt_lora(A, lda, W, ldw, K, P, ldp, Q, ldq, lora_scale, tout, ldt, M, N, dtype, epilogue, bias, res, aux, out,
                                               out2, ldo, p_drop, seed, site, s));
-  // tail split (see gsl_gemm_nt): the in-kernel-LoRA form exists on the 64 x 64 ring kernel too; t = s A P^T of the tail rows goes to tout's tail rows
-  const bool splittable = (epilogue == GSL_EPI_STORE && !out2) || epilogue == GSL_EPI_BIAS_RES_BF16 || epilogue == GSL_EPI_BIAS_RES_F16;
-  const int tail = (splittable && A && W && out && M >= 1024) ? tail_split_rows(M, N, dtype) : 0;
-  if (tail > 0) {
-    const int head = M - tail;
-    const int rc = gemm_nt_lora_rows(A, lda, W, ldw, K, P, ldp, Q, ldq, lora_scale, tout, ldt, head, N, dtype, epilogue, bias, res, aux, out, out2, ldo,
-                                     p_drop, seed, site, s, 0);
-    if (rc) return rc;
-    return gemm_nt_lora_rows(rows_after(A, head, lda, 2), lda, W, ldw, K, P, ldp, Q, ldq, lora_scale, rows_after(tout, head, ldt, 2), ldt, tail, N, dtype,
-                             epilogue, bias, rows_after(res, head, ldo, 2), aux, rows_after(out, head, ldo, 2), out2, ldo, p_drop, seed, site, s, head);
-  }
-  return gemm_nt_lora_rows(A, lda, W, ldw, K, P, ldp, Q, ldq, lora_scale, tout, ldt, M, N, dtype, epilogue, bias, res, aux, out, out2, ldo, p_drop, seed,
-                           site, s, 0);
-}
-
-static int gemm_nt_lora_rows(const void* A, int lda, const void* W, int ldw, int K, const void* P, int ldp, const void* Q,
-                             int ldq, float lora_scale, void* tout, int ldt, int M, int N, int dtype, int epilogue,
-                             const float* bias, const void* res, const void* aux, void* out, void* out2, int ldo,
-                             float p_drop, uint64_t seed, uint32_t site, gsl_stream_t s, int mbase) {
   if (dtype != GSL_OP16) return fail(GSL_ERR_UNSUPPORTED, "gsl_gemm_nt_lora: bf16 / fp16 operands only (f32 parity mode uses gsl_gemm_nt with a K segment)%s %ld", "", dtype);
   GSL_CHECK_ARG(M > 0 && N > 0 && (N % 4) == 0 && K > 0 && (K % 64) == 0, "M,N>0, N%4==0, K%64==0");
   GSL_CHECK_ARG(A && W && P && Q && out, "null operand");
@@ -2582,62 +2507,14 @@ static int gemm_nt_lora_rows(const void* A, int lda, const void* W, int ldw, int
                 (!tout || ((ldt % 8) == 0 && ldt >= 64)), "leading dimensions (P [16,K], Q [N,>=32], tout [M,>=64])");
   GSL_CHECK_ARG(lda >= K && ldw >= K && ldp >= K && ldo >= N, "leading dimensions: lda >= K, ldw >= K, ldp >= K, ldo >= N");
   GSL_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "p_drop");
-  EpiArgs e;
-  e.alpha = 1.0f; e.bias = bias; e.res = res; e.aux = aux; e.out = out; e.out2 = out2; e.ldo = ldo;
-  e.pos = nullptr; e.cls = nullptr; e.T = 0; e.drop = make_drop(p_drop, seed, site); e.M = M; e.N = N;
-  set_launch_knobs(e, true);
-  e.mbase = mbase;
-  e.hmT = 0; e.hmH = 0;
-  LoraInk lk;
-  lk.P = (const bf16_t*)P; lk.ldp = ldp; lk.Q = (const bf16_t*)Q; lk.ldq = ldq; lk.s = lora_scale; lk.tout = (bf16_t*)tout; lk.ldt = ldt;
-  const int nb = ((M + BM4 - 1) / BM4) * ((N + BN4 - 1) / BN4);
-  hipStream_t st = as_stream(s);
-#ifdef GSL_DEV
-  const char* ev = getenv("GSL_GEMM_VARIANT");      // development knob: 4 = single-phase 256x256 kernel, default = 8-phase schedule
-  const bool old_sched = ev && atoi(ev) == 4;
-#endif
-#ifdef GSL_DEV
-#define GSL_LL_DEV(EPIV)                                                                                                          \
-    if (old_sched) { hipLaunchKernelGGL(gemm_bf16_t256_lora_kernel<EPIV>, dim3(nb), dim3(512), 0, st, (const bf16_t*)A, lda,       \
-                                        (const bf16_t*)W, ldw, K, lk, e); break; }
-#else
-#define GSL_LL_DEV(EPIV)
-#endif
-  // few rows (the launch-bound regime): the 64-row ring kernel, by the tile rule (gemm_tile_choice)
-  const int ring = gemm_tile_choice(M, N, K, GSL_OP16, false, true);
-  const bool small = ring != GSL_TILE_P8;
-#define GSL_LL(EPIV)                                                                                                              \
-  do {                                                                                                                            \
-    GSL_LL_DEV(EPIV)                                                                                                              \
-    if (small) {                                                                                                                  \
-      if (ring == GSL_TILE_RING64_WIDE)                                                                                           \
-        hipLaunchKernelGGL((gemm_bf16_small_kernel<EPIV, true, 4>), dim3(((M + BMS - 1) / BMS) * ((N + 2 * BNS - 1) / (2 * BNS))), dim3(256), 0, st, \
-                           (const bf16_t*)A, lda, (const bf16_t*)W, ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e); \
-      else if (ring == GSL_TILE_RING64_KSPLIT)                                                                                    \
-        hipLaunchKernelGGL((gemm_bf16_small_kernel<EPIV, true, 2, 2>), dim3(((M + BMS - 1) / BMS) * ((N + BNS - 1) / BNS)), dim3(512), 0, st, \
-                           (const bf16_t*)A, lda, (const bf16_t*)W, ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e); \
-      else                                                                                                                        \
-        hipLaunchKernelGGL((gemm_bf16_small_kernel<EPIV, true, 2>), dim3(((M + BMS - 1) / BMS) * ((N + BNS - 1) / BNS)), dim3(256), 0, st, \
-                           (const bf16_t*)A, lda, (const bf16_t*)W, ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e); \
-      break;                                                                                                                      \
-    }                                                                                                                             \
-    e.mrev = mrev_for(16 + EPIV);                                                                                                 \
-    hipLaunchKernelGGL((gemm_bf16_p8_kernel<EPIV, true>), dim3(nb), dim3(512), 0, st, (const bf16_t*)A, lda, (const bf16_t*)W,     \
-                       ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e);                                    \
-  } while (0)
-  switch (epilogue) {
-    case GSL_EPI_STORE: GSL_LL(GSL_EPI_STORE); break;
-    case GSL_EPI_BIAS_RES_F32: GSL_CHECK_ARG(bias && res, "bias/res required"); GSL_LL(GSL_EPI_BIAS_RES_F32); break;
-    case GSL_EPI_BIAS_RES_F16: e.f16 = 1; [[fallthrough]];
-    case GSL_EPI_BIAS_RES_BF16: GSL_CHECK_ARG(bias && res && (ldo % 8) == 0, "bias/res required"); GSL_LL(GSL_EPI_BIAS_RES_BF16); break;
-    case GSL_EPI_BIAS_GELU: GSL_CHECK_ARG(bias, "bias required"); GSL_LL(GSL_EPI_BIAS_GELU); break;
-    case GSL_EPI_MUL: GSL_CHECK_ARG(aux, "aux required"); GSL_LL(GSL_EPI_MUL); break;
-    case GSL_EPI_BIAS_GELU_G8: GSL_CHECK_ARG(bias && (N % 64) == 0, "bias required, N % 64 == 0"); GSL_LL(GSL_EPI_BIAS_GELU_G8); break;
-    case GSL_EPI_MUL_G8: GSL_CHECK_ARG(aux && (N % 64) == 0, "aux required, N % 64 == 0"); GSL_LL(GSL_EPI_MUL_G8); break;
-    default: return fail(GSL_ERR_ARG, "gsl_gemm_nt_lora: unsupported epilogue%s %ld", "", epilogue);
-  }
-#undef GSL_LL
-  return check_launch("gsl_gemm_nt_lora");
+  GemmCall c = new_call(dtype, epilogue, s, true);
+  c.A1 = A; c.lda1 = lda; c.W1 = W; c.ldw1 = ldw; c.K1 = K;
+  c.lora = true;
+  c.lk.P = (const bf16_t*)P; c.lk.ldp = ldp; c.lk.Q = (const bf16_t*)Q; c.lk.ldq = ldq; c.lk.s = lora_scale; c.lk.tout = (bf16_t*)tout; c.lk.ldt = ldt;
+  EpiArgs& e = c.e;
+  e.M = M; e.N = N; e.bias = bias; e.res = res; e.aux = aux; e.out = out; e.out2 = out2; e.ldo = ldo; e.drop = make_drop(p_drop, seed, site);
+  if (const int rc = check_epilogue(c)) return rc;
+  return launch_tail_split(c);
 }
 
 // =====================================================================================
@@ -2698,29 +2575,28 @@ extern "C" int GSL_ENTRY(gsl_gemm_nt_lora_mulgrad)(const void* A, int lda, const
                 (!tout || ((ldt % 8) == 0 && ldt >= 64)) && (ldu1 % 8) == 0 && ldu1 >= 16,
                 "leading dimensions (P [16,K], Q [N,>=32], tout [M,>=64], U1 [M,>=16], out/aux/Y2 [M,ldo])");
   GSL_CHECK_ARG(r >= 1 && r <= 16, "r in [1,16]");
-  EpiArgs e;
-  e.alpha = 1.0f; e.bias = nullptr; e.res = nullptr; e.aux = aux; e.out = out; e.out2 = nullptr; e.ldo = ldo;
-  e.pos = nullptr; e.cls = nullptr; e.T = 0; e.drop = make_drop(0.f, 0, 0); e.M = M; e.N = N;
+  GemmCall c = new_call(dtype, GSL_EPI_MUL, s, false);   // K rotation stays off: every N tile must accumulate t = s A P^T in the same K order (G2 contracts the tile-local t, which has to equal tout bit for bit)
+  c.A1 = A; c.lda1 = lda; c.W1 = W; c.ldw1 = ldw; c.K1 = K;
+  c.lora = true;
+  c.lk.P = (const bf16_t*)P; c.lk.ldp = ldp; c.lk.Q = (const bf16_t*)Q; c.lk.ldq = ldq; c.lk.s = lora_scale; c.lk.tout = (bf16_t*)tout; c.lk.ldt = ldt;
+  EpiArgs& e = c.e;
+  e.M = M; e.N = N; e.aux = aux; e.out = out; e.ldo = ldo;
   e.drop.scale = 1.0f / (1.0f - p_drop);      // only the decode of the 8-bit GELU' codes reads it: no mask is applied in this kernel
-  set_launch_knobs(e, false);   // K rotation stays off: every N tile must accumulate t = s A P^T in the same K order (G2 contracts the tile-local t, which has to equal tout bit for bit)
-  e.hmT = 0; e.hmH = 0;
   const int R = (r <= 8) ? 8 : 16;
   const int ntile = (M + BM4 - 1) / BM4, nslab = (ntile + GF_FAN - 1) / GF_FAN;
   const size_t NR = (size_t)N * R;
   e.gu1 = (const bf16_t*)U1; e.ldgu1 = ldu1; e.gy2 = (const bf16_t*)Y2; e.gR = R;
   e.gpart1 = ws; e.gpart2 = ws + (size_t)ntile * NR;
   float* part2 = ws + 2 * (size_t)ntile * NR;
-  LoraInk lk;
-  lk.P = (const bf16_t*)P; lk.ldp = ldp; lk.Q = (const bf16_t*)Q; lk.ldq = ldq; lk.s = lora_scale; lk.tout = (bf16_t*)tout; lk.ldt = ldt;
   const int nb = ntile * ((N + BN4 - 1) / BN4);
-  hipStream_t st = as_stream(s);
+  hipStream_t st = c.st;
   e.mrev = mrev_for(30);
   if (aux_u8)
     hipLaunchKernelGGL((gemm_bf16_p8_kernel<GSL_EPI_MUL_G8, true, true>), dim3(nb), dim3(512), 0, st, (const bf16_t*)A, lda, (const bf16_t*)W,
-                       ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e);
+                       ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, c.lk, e);
   else
     hipLaunchKernelGGL((gemm_bf16_p8_kernel<GSL_EPI_MUL, true, true>), dim3(nb), dim3(512), 0, st, (const bf16_t*)A, lda, (const bf16_t*)W,
-                       ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, lk, e);
+                       ldw, K, (const bf16_t*)nullptr, 0, (const bf16_t*)nullptr, 0, 0, c.lk, e);
   int rc = check_launch("gsl_gemm_nt_lora_mulgrad");
   if (rc) return rc;
   const int NR4 = (int)(NR / 4);

@@ -28,6 +28,14 @@ inline int check_launch(const char* what) {
   return GSL_OK;
 }
 #define GSL_LAUNCH_CHECK() return gsl::check_launch(__func__)
+// compute units of the current device: queried once, 256 if the query fails
+inline int num_cus() {
+  static const int n = [] {
+    int dev = 0; hipDeviceProp_t pr;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+  }();
+  return n;
+}
 
 // ------------------------------------------------------------------ bf16
 typedef uint16_t bf16_t;

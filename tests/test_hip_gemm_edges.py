@@ -544,3 +544,42 @@ def test_leading_dimensions_below_the_row_length_are_refused(ops, dt):
             assert lora(**dict(dict(lda=K, ldw=K, ldp=K, ldo=N), **bad)) != 0, bad
             assert b"argument check failed" in lib.gsl_last_error(), bad
     torch.cuda.synchronize()
+
+
+def test_alpha_is_refused_where_not_every_kernel_applies_it(ops):
+    """gsl_gemm_nt applies alpha in the STORE, STORE_F32 and MUL epilogues on every kernel; the staged residual, patch and table-GELU epilogues of
+    the 8-phase kernel drop it while their fragment forms differ among themselves. So alpha != 1 is an argument error for BIAS_RES_*, PATCH* and
+    BIAS_GELU*: the call names alpha and returns before anything is launched (out keeps its sentinel), the same call with alpha = 1 runs.
+    Where alpha is applied, alpha = 2 doubles the alpha = 1 result: within one rounding of the output type (a factor 2 is exact, so the bound
+    is the unit roundoff of the output format times the value)."""
+    from gslora_hip import _lib as L
+    M = N = K = 64
+    T = 8
+    g = torch.Generator(device="cuda").manual_seed(SEED)
+    rnd = lambda *s, dt=BF16: torch.randn(*s, device="cuda", generator=g).to(dt)
+    A, W, bias, pos, cls = rnd(M, K), rnd(N, K), rnd(N, dt=F32), rnd(T, N, dt=F32), rnd(N, dt=F32)
+    stream = lambda dt: dict(bias=bias, res=rnd(M, N, dt=dt))
+    patch = dict(bias=bias, pos=pos, cls=cls, T=T)
+    refused = (("BIAS_RES_F32", F32, stream(F32)), ("BIAS_RES_BF16", BF16, stream(BF16)), ("BIAS_RES_F16", F16, stream(F16)),
+               ("PATCH", F32, patch), ("PATCH_BF16", BF16, patch), ("PATCH_F16", F16, patch),
+               ("BIAS_GELU", BF16, dict(bias=bias)), ("BIAS_GELU_G8", BF16, dict(bias=bias)))
+    for name, odt, kw in refused:
+        out = torch.full((M, N), 7.0, device="cuda", dtype=odt)
+        with pytest.raises(RuntimeError, match="alpha"):
+            ops.gemm_nt(A, W, out, epilogue=getattr(L, "EPI_" + name), alpha=2.0, **kw)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), (name, "a refused call wrote to out")
+        ops.gemm_nt(A, W, out, epilogue=getattr(L, "EPI_" + name), alpha=1.0, **kw)      # the operands were valid: alpha alone was refused
+        torch.cuda.synchronize()
+        assert not bool((out == 7.0).all()), name
+    for name, odt, kw in (("STORE", BF16, {}), ("STORE_F32", F32, {}), ("MUL", BF16, dict(aux=rnd(M, N)))):
+        one, two = torch.zeros(M, N, device="cuda", dtype=odt), torch.zeros(M, N, device="cuda", dtype=odt)
+        ops.gemm_nt(A, W, one, epilogue=getattr(L, "EPI_" + name), alpha=1.0, **kw)
+        ops.gemm_nt(A, W, two, epilogue=getattr(L, "EPI_" + name), alpha=2.0, **kw)
+        torch.cuda.synchronize()
+        want = 2.0 * one.double()
+        assert bool((want != 0).any()), name
+        err = (two.double() - want).abs()
+        bound = want.abs() * (torch.finfo(odt).eps / 2)
+        print(f"alpha=2 {name}: max |err| {err.max().item():.3e}, max err / bound {(err / bound.clamp_min(1e-300)).max().item():.3f}")
+        assert bool((err <= bound).all()), (name, err.max().item())
