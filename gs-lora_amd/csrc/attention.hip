@@ -18,12 +18,15 @@
 //     and dK/dV (waves own key tiles; Q and dO panels in LDS); probabilities are recomputed
 //     from the saved log-sum-exp (flash-style), delta = rowsum(dO∘O) is produced by the dQ phase.
 //     T > 64 runs both phases in ONE launch (attn_bwd_fused_bf16_kernel); the two-kernel form stays for
-//     T <= 64 and as the bit-exact reference of the tests.
+//     T <= 64 and, in the development build only, as the bit-exact reference of the tests.
 //   * forward, T in (64, 208] and enough (image, head) items: a persistent wave-specialised kernel
 //     (attn_fwd_bf16_pers_kernel: 13 compute waves + 3 loader waves per CU) streams the next item's
 //     panels under the current item's softmax; bit-identical to the one-item-per-workgroup kernel.
 // f32 path (parity mode): v_mfma_f32_16x16x4_f32 kernels (exact f32: a k-ordered fmaf chain per output), K / V or Q / dO panels in LDS;
 //   the cls-query kernels of the last block are templated on the element type.
+// Host side (end of the file): each entry fills one AttnCall, attn_kernel_choice — the one rule (shape, dtype, direction) -> kernel, exported as
+// gsl_attention_kernel_choice — names the kernel, and attn_launch_as holds each product launch once. The product reads nothing from the environment;
+// the development knobs and the kernels only they reach live in attention_dev_launch.inc (-DGSL_DEV), behind one hook.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -627,6 +630,13 @@ __global__ __launch_bounds__(512, (NT == 1 ? 4 : 2)) void attn_bwd_dkv_bf16_kern
 // for key tile NKT - 2 only, and tile NKT - 1 — no valid key / query, probabilities exactly zero — is left out of both phases at
 // compile time (a run-time uniform branch inside the unrolled tile loop makes the compiler sink all exponentials below it and spill
 // the score tiles). Same values in the same order as the generic form: bit-identical.
+// The development parameters stay in the product kernels (stamps, the nostore bit of hm; the product passes nullptr / 0): the stamp sites act as
+// scheduling fences in kernels that sit at the 128-register cap. With GSL_ATTN_STAMP / GSL_MSTAMP as no-ops and nostore a constexpr false the
+// compiler reports (gfx950, -O3, product flags; not run on a GPU; profiles/attn_host_side.md):
+//   attn_bwd_fused_bf16_kernel<14, true, 512>    120 VGPR, no spill        -> 128 VGPR, 7 VGPRs spilled, 16 B/lane scratch
+//   attn_bwd_fused_bf16_kernel<14, true, 1024>   120 VGPR, no spill        -> 128 VGPR, 6 VGPRs spilled, 12 B/lane scratch
+//   attn_bwd_fused_bf16_kernel<14, false, 512>   113 VGPR, 66 SGPR spills  -> 127 VGPR, 58 SGPR spills
+//   attn_bwd_merged_kernel<14>                   94 SGPR, 124 VGPR         -> 81 SGPR, 122 VGPR
 template <int NKT, bool FAST, int NT = 512>      // NT = 1024: sixteen waves, one tile each (fewer items than CUs; see attn_fwd_bf16_kernel)
 __global__ __launch_bounds__(NT, 4) void attn_bwd_fused_bf16_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
                                                                      const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
@@ -2196,65 +2206,26 @@ __global__ __launch_bounds__(256) void attn_fwd_cls_long_kernel(const T* __restr
   if (tid == 0) lse_cls[(size_t)b * H + h] = m + logf(e);
 }
 
-extern "C" int GSL_ENTRY(gsl_attention_fwd_cls)(const void* qkv, const void* q_cls, void* o_cls, float* lse_cls, int B, int T, int H, float scale,
-                                     int dtype, int qkv_layout, gsl_stream_t s) {
-  GSL_FORWARD_H16(dtype, h16_gsl_attention_fwd_cls(qkv, q_cls, o_cls, lse_cls, B, T, H, scale, dtype, qkv_layout, s));
-  GSL_CHECK_ARG(qkv && o_cls && lse_cls && B > 0 && T > 1 && H > 0, "null/size");
-  GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
-  GSL_CHECK_ARG(qkv_layout >= 0 && qkv_layout <= 2 && (qkv_layout != 2 || q_cls), "qkv_layout: 0 token-major, 1 head-major, 2 kv + q_cls");
-  const dim3 grid(B * H), blk(256);
-  if (T > 256) {      // key chunks with the online max / sum
-    if (dtype == GSL_OP16)
-      hipLaunchKernelGGL(attn_fwd_cls_long_kernel<bf16_t>, grid, blk, 0, as_stream(s), (const bf16_t*)qkv, (const bf16_t*)q_cls, (bf16_t*)o_cls, lse_cls, T, H, scale, qkv_layout);
-#if GSL_HAS_F32
-    else if (dtype == GSL_F32)
-      hipLaunchKernelGGL(attn_fwd_cls_long_kernel<float>, grid, blk, 0, as_stream(s), (const float*)qkv, (const float*)q_cls, (float*)o_cls, lse_cls, T, H, scale, qkv_layout);
-#endif
-    else return fail(GSL_ERR_ARG, "gsl_attention_fwd_cls: bad dtype%s %ld", "", dtype);
-    return check_launch("gsl_attention_fwd_cls");
-  }
-  if (dtype == GSL_OP16)
-    hipLaunchKernelGGL(attn_fwd_cls_kernel<bf16_t>, grid, blk, 0, as_stream(s), (const bf16_t*)qkv, (const bf16_t*)q_cls, (bf16_t*)o_cls, lse_cls, T, H, scale, qkv_layout);
-#if GSL_HAS_F32
-  else if (dtype == GSL_F32)
-    hipLaunchKernelGGL(attn_fwd_cls_kernel<float>, grid, blk, 0, as_stream(s), (const float*)qkv, (const float*)q_cls, (float*)o_cls, lse_cls, T, H, scale, qkv_layout);
-#endif
-  else return fail(GSL_ERR_ARG, "gsl_attention_fwd_cls: bad dtype%s %ld", "", dtype);
-  return check_launch("gsl_attention_fwd_cls");
+// ===================================================================================== host side: one call record, one kernel rule, one launch per kernel, the C ABI
+enum { ATTN_FWD = 0, ATTN_BWD = 1, ATTN_FWD_CLS = 2, ATTN_BWD_CLS = 3 };      // `direction` of gsl_attention_kernel_choice
+// What the product passes for the kernels' development parameters (they stay: see attn_bwd_fused_bf16_kernel); the development build overwrites them.
+constexpr int ATTN_ABL_NONE = 0;                                // abl: nothing ablated
+constexpr unsigned long long* ATTN_NO_STAMPS = nullptr;         // stamps: no cycle-stamp buffer
+constexpr int ATTN_FWD_IMAP = 0;      // the forward keeps the plain item order: the remap measured +1 % there (212 -> 215 us at B = 1024)
+// One attention call as the host side passes it around: each entry fills one after its argument checks (attn_call + assignments by name).
+struct AttnCall {
+  const void *qkv, *q_cls, *o, *d_o; const float* lse;      // inputs (o: the forward's output as a backward reads it; d_o: d_o_cls of the cls backward)
+  void *out, *dq_cls; float *lse_out, *delta_ws;            // o / o_cls or dqkv, the cls backward's query gradients (layout 2), the forwards' lse, scratch
+  int B, T, H; float scale; int dtype, qkv_layout, cls_compact; hipStream_t st;      // dtype: GSL_OP16 or GSL_F32; qkv_layout: the kernels' hm
+  int items, imap;                        // B * H; heads of an image on one XCD (the kernels' item_remap): attn_item_remap
+  int abl = ATTN_ABL_NONE; unsigned long long* stamps = ATTN_NO_STAMPS;
+};
+static inline AttnCall attn_call(int B, int T, int H, float scale, int dtype, int qkv_layout, gsl_stream_t s) {
+  AttnCall c{};
+  c.B = B; c.T = T; c.H = H; c.scale = scale; c.dtype = dtype; c.qkv_layout = qkv_layout; c.st = as_stream(s); c.items = B * H;
+  return c;
 }
 
-extern "C" int GSL_ENTRY(gsl_attention_bwd_cls)(const void* qkv, const void* q_cls, const void* o, const void* d_o_cls, const float* lse, void* dqkv,
-                                     void* dq_cls, int B, int T, int H, float scale, int dtype, int qkv_layout, int cls_compact,
-                                     gsl_stream_t s) {
-  GSL_FORWARD_H16(dtype, h16_gsl_attention_bwd_cls(qkv, q_cls, o, d_o_cls, lse, dqkv, dq_cls, B, T, H, scale, dtype, qkv_layout, cls_compact, s));
-  GSL_CHECK_ARG(qkv && o && d_o_cls && lse && dqkv && B > 0 && T > 1 && H > 0, "null/size");
-  GSL_CHECK_ARG(qkv_layout >= 0 && qkv_layout <= 2 && (qkv_layout != 2 || (q_cls && dq_cls)), "qkv_layout: 0 token-major, 1 head-major, 2 kv + q_cls / dq_cls");
-  const dim3 grid(B * H), blk(256);
-  if (dtype == GSL_OP16)
-    hipLaunchKernelGGL(attn_bwd_cls_kernel<bf16_t>, grid, blk, 0, as_stream(s), (const bf16_t*)qkv, (const bf16_t*)q_cls, (const bf16_t*)o,
-                       (const bf16_t*)d_o_cls, lse, (bf16_t*)dqkv, (bf16_t*)dq_cls, T, H, scale, qkv_layout, cls_compact);
-#if GSL_HAS_F32
-  else if (dtype == GSL_F32)
-    hipLaunchKernelGGL(attn_bwd_cls_kernel<float>, grid, blk, 0, as_stream(s), (const float*)qkv, (const float*)q_cls, (const float*)o,
-                       (const float*)d_o_cls, lse, (float*)dqkv, (float*)dq_cls, T, H, scale, qkv_layout, cls_compact);
-#endif
-  else return fail(GSL_ERR_ARG, "gsl_attention_bwd_cls: bad dtype%s %ld", "", dtype);
-  return check_launch("gsl_attention_bwd_cls");
-}
-
-// Development knobs (libgslora_hip_dev.so only; the product library reads nothing from the environment):
-//   GSL_ATTN_PERSISTENT=0 one item per workgroup; GSL_ATTN_ABL=1 staging only, 2 no staging; GSL_ATTN_BWD_SPLIT=1 the two-kernel backward;
-//   GSL_ATTN_NT key tiles per wave of the dK/dV kernel; GSL_ATTN_STAMPS device address of a cycle-stamp buffer;
-//   GSL_ATTN_BWD_MERGED=0 the fused two-phase backward instead of the merged one, GSL_ATTN_BWD_MERGED_MIN items per CU from which the merged one runs.
-#ifdef GSL_DEV
-static inline int attn_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static inline unsigned long long* attn_stamps() { const char* sp = getenv("GSL_ATTN_STAMPS"); return sp ? reinterpret_cast<unsigned long long*>(strtoull(sp, nullptr, 0)) : nullptr; }
-#else
-static inline constexpr int attn_env(const char*, int dflt) { return dflt; }
-static inline constexpr unsigned long long* attn_stamps() { return nullptr; }
-#endif
-static inline int attn_persistent() { return attn_env("GSL_ATTN_PERSISTENT", 1); }
-static inline int attn_abl() { return attn_env("GSL_ATTN_ABL", 0); }
 // Launch shape of the long-sequence kernels (T > 224): tiles (query tiles of the forward / dQ, key tiles of dK / dV) per workgroup = waves.
 // Blocks of <= 16 tiles; while items * blocks < CUs (few images) an item is split further, down to 4 tiles per workgroup. Returns the
 // waves per workgroup and sets nb = blocks per item and the grid (items rounded up to a multiple of 8: long_item()).
@@ -2268,50 +2239,123 @@ static inline int attn_long_shape(int T, int items, int& nb, dim3& grid) {
   return w;
 }
 
-// =====================================================================================
-// C ABI
-// =====================================================================================
+// ---- The kernel rule: (shape, dtype, direction) -> gsl_attn_kernel, written once: attn_launch and the exported gsl_attention_kernel_choice
+// call it, the development knobs apply after it. dtype: GSL_OP16; anything else counts as f32.
+// The merged backward runs from 8 items per CU: a persistent workgroup pays its prologue and a ragged last round — at 4.5 items per CU (ViT-B/16:
+// 48 + 48 images x 12 heads) the fused kernel is 4 % faster per launch (profiles/r05_notes.md). (A persistent wave-specialised fused backward like
+// the forward's was measured slower, 795 vs 736 us at B = 1024: four workgroup-wide barriers per item cost more than the hidden staging saves.)
+static inline bool attn_fast(int T) { return T > 192 && T <= 208; }      // FAST of the NKT = 14 kernels: the last key tile holds no valid key
+static inline int attn_kernel_choice(int T, int items, int dtype, int dir) {
+  if (dir == ATTN_FWD_CLS) return T > 256 ? GSL_ATTN_FWD_CLS_LONG : GSL_ATTN_FWD_CLS;
+  if (dir == ATTN_BWD_CLS) return GSL_ATTN_BWD_CLS;
+  const bool fwd = dir == ATTN_FWD;
+  const int cus = num_cus();
+  if (dtype != GSL_OP16) return T > 224 ? (fwd ? GSL_ATTN_FWD_F32_LONG : GSL_ATTN_BWD_F32_LONG) : (fwd ? GSL_ATTN_FWD_F32 : GSL_ATTN_BWD_F32);
+  if (T > 224) return fwd ? GSL_ATTN_FWD_LONG : GSL_ATTN_BWD_LONG;
+  if (T <= 64) return fwd ? GSL_ATTN_FWD_T64 : GSL_ATTN_BWD_T64;
+  if (fwd && T <= 208 && items >= 2 * cus) return GSL_ATTN_FWD_PERSISTENT;
+  if (!fwd && attn_fast(T) && items >= 8 * cus) return GSL_ATTN_BWD_MERGED;
+  if (items < cus) return fwd ? GSL_ATTN_FWD_1024 : GSL_ATTN_BWD_FUSED_1024;
+  return fwd ? GSL_ATTN_FWD_512 : GSL_ATTN_BWD_FUSED_512;
+}
+// The XCD item remap a launch receives: the backward gains 2.3 % from it (profiles/r04_notes.md); the merged kernel's persistent grid also
+// needs a CU count that is a multiple of 8. Kernels without an imap parameter ignore it.
+static inline int attn_item_remap(int B, int cus, int dir, int kernel) { return dir == ATTN_BWD ? B % 8 == 0 && (kernel != GSL_ATTN_BWD_MERGED || cus % 8 == 0) : ATTN_FWD_IMAP; }
+#if GSL_HAS_F32      // not an f32 feature guard: this file is compiled once per 16-bit operand format, and only the plain compile defines the exported symbol
+extern "C" int gsl_attention_kernel_choice(int B, int T, int H, int dtype, int qkv_layout, int direction) {
+  const bool h16 = dtype == GSL_BF16 || dtype == GSL_F16, cls = direction == ATTN_FWD_CLS || direction == ATTN_BWD_CLS;
+  if (!(h16 || dtype == GSL_F32) || direction < ATTN_FWD || direction > ATTN_BWD_CLS || B <= 0 || T <= 1 || H <= 0) return -1;
+  if (direction != ATTN_BWD_CLS && T > GSL_ATTN_MAX_T) return -1;
+  if (cls ? (qkv_layout < 0 || qkv_layout > 2) : !(qkv_layout == 0 || (qkv_layout == 1 && h16))) return -1;
+  return attn_kernel_choice(T, B * H, h16 ? GSL_OP16 : dtype, direction);      // (GSL_OP16: the rule does not tell the two 16-bit formats apart)
+}
+#endif
+
+// ---- One launch per kernel, in the call's element type E (the casts, once). Kernels that differ in a template flag only have one signature: the
+// flag picks the function, one line launches it.
+template <class E>
+static void attn_launch_as(const AttnCall& c, int kernel) {
+  const E *qkv = (const E*)c.qkv, *q_cls = (const E*)c.q_cls, *o = (const E*)c.o, *d_o = (const E*)c.d_o; E *out = (E*)c.out, *dq_cls = (E*)c.dq_cls;
+  const dim3 items(c.items);
+  const int hm = c.qkv_layout;
+  auto fwd_cls = kernel == GSL_ATTN_FWD_CLS_LONG ? attn_fwd_cls_long_kernel<E> : attn_fwd_cls_kernel<E>;
+  switch (kernel) {      // the cls-query kernels are templated on the element type
+    case GSL_ATTN_FWD_CLS: case GSL_ATTN_FWD_CLS_LONG: hipLaunchKernelGGL(fwd_cls, items, dim3(256), 0, c.st, qkv, q_cls, out, c.lse_out, c.T, c.H, c.scale, hm); return;
+    case GSL_ATTN_BWD_CLS: hipLaunchKernelGGL(attn_bwd_cls_kernel<E>, items, dim3(256), 0, c.st, qkv, q_cls, o, d_o, c.lse, out, dq_cls, c.T, c.H, c.scale, hm, c.cls_compact); return;
+  }
+  if constexpr (std::is_same_v<E, float>) {
+    const dim3 one(64), mfma(512), q64(c.items, (c.T + 63) / 64), k32(c.items, (c.T + 31) / 32);
+    const bool small = c.T <= 64;      // the 64-row panel of the matrix-core kernels, else 224 rows
+    auto fwd = small ? attn_fwd_f32_mfma_kernel<64> : attn_fwd_f32_mfma_kernel<224>;
+    auto dq = small ? attn_bwd_dq_f32_mfma_kernel<64> : attn_bwd_dq_f32_mfma_kernel<224>;
+    auto dkv = small ? attn_bwd_dkv_f32_mfma_kernel<64> : attn_bwd_dkv_f32_mfma_kernel<224>;
+    switch (kernel) {
+      case GSL_ATTN_FWD_F32_LONG: hipLaunchKernelGGL(attn_fwd_long_f32_kernel, q64, one, 0, c.st, qkv, out, c.lse_out, c.T, c.H, c.scale); break;
+      case GSL_ATTN_FWD_F32: hipLaunchKernelGGL(fwd, items, mfma, 0, c.st, qkv, out, c.lse_out, c.T, c.H, c.scale); break;
+      case GSL_ATTN_BWD_F32_LONG:
+        hipLaunchKernelGGL(attn_bwd_dq_long_f32_kernel, q64, one, 0, c.st, qkv, o, d_o, c.lse, out, c.delta_ws, c.T, c.H, c.scale);
+        hipLaunchKernelGGL(attn_bwd_dkv_long_f32_kernel, k32, one, 0, c.st, qkv, d_o, c.lse, c.delta_ws, out, c.T, c.H, c.scale);
+        break;
+      case GSL_ATTN_BWD_F32:
+        hipLaunchKernelGGL(dq, items, mfma, 0, c.st, qkv, o, d_o, c.lse, out, c.delta_ws, c.T, c.H, c.scale);
+        hipLaunchKernelGGL(dkv, items, mfma, 0, c.st, qkv, d_o, c.lse, c.delta_ws, out, c.T, c.H, c.scale);
+    }
+  } else {
+    const dim3 cus(num_cus());
+    const int nt = kernel == GSL_ATTN_FWD_T64 ? 256 : (kernel == GSL_ATTN_FWD_1024 || kernel == GSL_ATTN_BWD_FUSED_1024) ? 1024 : 512;
+    const bool fast = attn_fast(c.T);
+    auto fwd_item = nt == 256 ? attn_fwd_bf16_kernel<4> : nt == 1024 ? attn_fwd_bf16_kernel<14, 1024> : attn_fwd_bf16_kernel<14>;
+    auto fwd_pers = c.T > 192 ? attn_fwd_bf16_pers_kernel<14, true> : attn_fwd_bf16_pers_kernel<14, false>;
+    auto bwd_fused = nt == 1024 ? (fast ? attn_bwd_fused_bf16_kernel<14, true, 1024> : attn_bwd_fused_bf16_kernel<14, false, 1024>)
+                                : (fast ? attn_bwd_fused_bf16_kernel<14, true> : attn_bwd_fused_bf16_kernel<14, false>);
+    int nb = 1; dim3 lg;
+    const dim3 lblk(c.T > 224 ? 64 * attn_long_shape(c.T, c.items, nb, lg) : 0);      // the long kernels: K / V (Q / dO) panels streamed through LDS
+    switch (kernel) {
+      case GSL_ATTN_FWD_LONG: hipLaunchKernelGGL(attn_fwd_long_kernel, lg, lblk, 0, c.st, qkv, out, c.lse_out, c.T, c.H, c.scale, hm, c.items, nb); break;
+      case GSL_ATTN_FWD_T64: case GSL_ATTN_FWD_1024: case GSL_ATTN_FWD_512: hipLaunchKernelGGL(fwd_item, items, dim3(nt), 0, c.st, qkv, out, c.lse_out, c.T, c.H, c.scale, c.abl, hm); break;
+      case GSL_ATTN_FWD_PERSISTENT: hipLaunchKernelGGL(fwd_pers, cus, dim3(1024), 0, c.st, qkv, out, c.lse_out, c.T, c.H, c.scale, c.items, hm, c.imap); break;
+      case GSL_ATTN_BWD_LONG:      // dQ (writes delta_ws), then dK / dV (reads it)
+        hipLaunchKernelGGL(attn_bwd_dq_long_kernel, lg, lblk, 0, c.st, qkv, o, d_o, c.lse, out, c.delta_ws, c.T, c.H, c.scale, hm, c.items, nb);
+        hipLaunchKernelGGL(attn_bwd_dkv_long_kernel, lg, lblk, 0, c.st, qkv, d_o, c.lse, c.delta_ws, out, c.T, c.H, c.scale, hm, c.items, nb);
+        break;
+      case GSL_ATTN_BWD_T64:
+        hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<4>, items, dim3(256), 0, c.st, qkv, o, d_o, c.lse, out, c.delta_ws, c.T, c.H, c.scale, c.abl, hm);
+        hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<4, 2>), items, dim3(256), 0, c.st, qkv, d_o, c.lse, c.delta_ws, out, c.T, c.H, c.scale, c.abl, hm);
+        break;
+      case GSL_ATTN_BWD_MERGED: hipLaunchKernelGGL(attn_bwd_merged_kernel<14>, cus, dim3(1024), 0, c.st, qkv, o, d_o, c.lse, out, c.T, c.H, c.scale, c.items, hm, c.imap, c.stamps); break;
+      case GSL_ATTN_BWD_FUSED_1024: case GSL_ATTN_BWD_FUSED_512: hipLaunchKernelGGL(bwd_fused, items, dim3(nt), 0, c.st, qkv, o, d_o, c.lse, out, c.T, c.H, c.scale, c.stamps, hm, c.imap);
+    }
+  }
+}
+
+// The development build's knobs and kernels (-DGSL_DEV -> libgslora_hip_dev.so): attn_dev_launch runs once per call, after the rule.
+#ifdef GSL_DEV
+#include "attention_dev_launch.inc"
+#else
+static inline bool attn_dev_launch(AttnCall&, int, int&, int&) { return false; }
+#endif
+// what every entry does after its argument checks: the rule, the development hook, the dtype ladder, the launch
+static int attn_launch(AttnCall& c, int dir, const char* what) {
+  int kernel = attn_kernel_choice(c.T, c.items, c.dtype, dir), rc = 0;
+  c.imap = attn_item_remap(c.B, num_cus(), dir, kernel);
+  if (attn_dev_launch(c, dir, kernel, rc)) return rc;
+  if (c.dtype == GSL_OP16) attn_launch_as<bf16_t>(c, kernel);
+#if GSL_HAS_F32
+  else if (c.dtype == GSL_F32) attn_launch_as<float>(c, kernel);
+#endif
+  else return fail(GSL_ERR_ARG, "%s: bad dtype %ld", what, c.dtype);
+  return check_launch(what);
+}
+
 extern "C" int GSL_ENTRY(gsl_attention_fwd)(const void* qkv, void* o, float* lse, int B, int T, int H, float scale, int dtype,
                                  int qkv_layout, gsl_stream_t s) {
   GSL_FORWARD_H16(dtype, h16_gsl_attention_fwd(qkv, o, lse, B, T, H, scale, dtype, qkv_layout, s));
   GSL_CHECK_ARG(qkv && o && lse && B > 0 && T > 1 && H > 0, "null/size");
   GSL_CHECK_ARG(qkv_layout == 0 || (qkv_layout == 1 && dtype == GSL_OP16), "qkv_layout: 0 token-major, 1 head-major (bf16 kernels only)");
-  const int hm = qkv_layout;
   GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
-  hipStream_t st = as_stream(s);
-  if (T > 224) {      // K / V panels streamed through LDS
-    int nb = 1; dim3 lg;
-    const int w = attn_long_shape(T, B * H, nb, lg);
-    if (dtype == GSL_OP16)
-      hipLaunchKernelGGL(attn_fwd_long_kernel, lg, dim3(64 * w), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, hm, B * H, nb);
-#if GSL_HAS_F32
-    else if (dtype == GSL_F32)
-      hipLaunchKernelGGL(attn_fwd_long_f32_kernel, dim3(B * H, (T + 63) / 64), dim3(64), 0, st, (const float*)qkv, (float*)o, lse, T, H, scale);
-#endif
-    else return fail(GSL_ERR_ARG, "gsl_attention_fwd: bad dtype%s %ld", "", dtype);
-    return check_launch("gsl_attention_fwd");
-  }
-  const dim3 grid(B * H), blk(256);
-  // (item_remap for the forward: measured +1 % — 212 -> 215 us at B = 1024 —, so the plain order stays; the backward gains 2.3 %: profiles/r04_notes.md)
-  const int imap = (B % 8 == 0 && num_cus() % 8 == 0) ? attn_env("GSL_ATTN_ITEM_REMAP_FWD", 0) : 0;
-  if (dtype == GSL_OP16) {
-    if (T <= 64) hipLaunchKernelGGL(attn_fwd_bf16_kernel<4>, grid, blk, 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
-    else if (attn_persistent() && T <= 208 && B * H >= 2 * num_cus())
-    {
-      if (T > 192) hipLaunchKernelGGL((attn_fwd_bf16_pers_kernel<14, true>), dim3(num_cus()), dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, B * H, hm, imap);
-      else hipLaunchKernelGGL((attn_fwd_bf16_pers_kernel<14, false>), dim3(num_cus()), dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, B * H, hm, imap);
-    }
-    else if (B * H < num_cus()) hipLaunchKernelGGL((attn_fwd_bf16_kernel<14, 1024>), grid, dim3(1024), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
-    else hipLaunchKernelGGL(attn_fwd_bf16_kernel<14>, grid, dim3(512), 0, st, (const bf16_t*)qkv, (bf16_t*)o, lse, T, H, scale, attn_abl(), hm);
-  }
-#if GSL_HAS_F32
-  else if (dtype == GSL_F32) {
-    if (T <= 64) hipLaunchKernelGGL(attn_fwd_f32_mfma_kernel<64>, grid, dim3(512), 0, st, (const float*)qkv, (float*)o, lse, T, H, scale);
-    else hipLaunchKernelGGL(attn_fwd_f32_mfma_kernel<224>, grid, dim3(512), 0, st, (const float*)qkv, (float*)o, lse, T, H, scale);
-  }
-#endif
-  else return fail(GSL_ERR_ARG, "gsl_attention_fwd: bad dtype%s %ld", "", dtype);
-  return check_launch("gsl_attention_fwd");
+  AttnCall c = attn_call(B, T, H, scale, dtype, qkv_layout, s);
+  c.qkv = qkv; c.out = o; c.lse_out = lse;
+  return attn_launch(c, ATTN_FWD, "gsl_attention_fwd");
 }
 
 extern "C" int GSL_ENTRY(gsl_attention_bwd)(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv,
@@ -2319,74 +2363,31 @@ extern "C" int GSL_ENTRY(gsl_attention_bwd)(const void* qkv, const void* o, cons
   GSL_FORWARD_H16(dtype, h16_gsl_attention_bwd(qkv, o, d_o, lse, dqkv, delta_ws, B, T, H, scale, dtype, qkv_layout, s));
   GSL_CHECK_ARG(qkv && o && d_o && lse && dqkv && delta_ws && B > 0 && T > 1 && H > 0, "null/size");
   GSL_CHECK_ARG(qkv_layout == 0 || (qkv_layout == 1 && dtype == GSL_OP16), "qkv_layout: 0 token-major, 1 head-major (bf16 kernels only)");
-  const int hm = qkv_layout;
   GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
-  hipStream_t st = as_stream(s);
-  if (T > 224) {      // dQ over K / V panels (writes delta_ws), then dK / dV over Q / dO panels (reads it)
-    if (dtype == GSL_OP16) {
-      const bf16_t* q = (const bf16_t*)qkv; const bf16_t* oo = (const bf16_t*)o; const bf16_t* g = (const bf16_t*)d_o;
-      bf16_t* dq = (bf16_t*)dqkv;
-      int nb = 1; dim3 lg;
-      const int w = attn_long_shape(T, B * H, nb, lg);
-      hipLaunchKernelGGL(attn_bwd_dq_long_kernel, lg, dim3(64 * w), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale, hm, B * H, nb);
-      hipLaunchKernelGGL(attn_bwd_dkv_long_kernel, lg, dim3(64 * w), 0, st, q, g, lse, delta_ws, dq, T, H, scale, hm, B * H, nb);
-    }
-#if GSL_HAS_F32
-    else if (dtype == GSL_F32) {
-      const float* q = (const float*)qkv; const float* oo = (const float*)o; const float* g = (const float*)d_o;
-      float* dq = (float*)dqkv;
-      hipLaunchKernelGGL(attn_bwd_dq_long_f32_kernel, dim3(B * H, (T + 63) / 64), dim3(64), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale);
-      hipLaunchKernelGGL(attn_bwd_dkv_long_f32_kernel, dim3(B * H, (T + 31) / 32), dim3(64), 0, st, q, g, lse, delta_ws, dq, T, H, scale);
-    }
-#endif
-    else return fail(GSL_ERR_ARG, "gsl_attention_bwd: bad dtype%s %ld", "", dtype);
-    return check_launch("gsl_attention_bwd");
-  }
-  const dim3 grid(B * H), blk(256);
-  if (dtype == GSL_OP16) {
-    const bf16_t* q = (const bf16_t*)qkv; const bf16_t* oo = (const bf16_t*)o; const bf16_t* g = (const bf16_t*)d_o;
-    bf16_t* dq = (bf16_t*)dqkv;
-    const int imap = (B % 8 == 0) ? attn_env("GSL_ATTN_ITEM_REMAP", 1) : 0;      // heads of an image on one XCD (item_remap)
-    if (T <= 64) {
-      hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<4>, grid, blk, 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale, attn_abl(), hm);
-      hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<4, 2>), grid, blk, 0, st, q, g, lse, delta_ws, dq, T, H, scale, attn_abl(), hm);
-    } else if (attn_env("GSL_ATTN_BWD_SPLIT", 0) == 0) {
-      // (a persistent wave-specialised form like the forward's was measured slower here: 795 vs 736 us at B = 1024 — its four
-      //  workgroup-wide barriers per item cost more than the hidden staging saves; profiles/r01_gemm_ab.md)
-      unsigned long long* stp = attn_stamps();
-      // round 5: every score tile computed once (attn_bwd_merged_kernel; bit-identical to the fused kernel, GSL_ATTN_BWD_MERGED=0 in the dev build)
-      // (from 8 items per CU: a persistent workgroup pays its prologue and a ragged last round — at 4.5 items per CU, ViT-B/16 48 + 48 x 12
-      //  heads, the fused kernel is 4 % faster per launch: profiles/r05_notes.md)
-      if (T > 192 && T <= 208 && B * H >= attn_env("GSL_ATTN_BWD_MERGED_MIN", 8) * num_cus() && attn_env("GSL_ATTN_BWD_MERGED", 1))
-        hipLaunchKernelGGL((attn_bwd_merged_kernel<14>), dim3(num_cus()), dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, B * H, hm, (num_cus() % 8 == 0) ? imap : 0, stp);
-      else
-      if (B * H < num_cus()) {      // fewer items than CUs: sixteen waves per item
-        if (T > 192 && T <= 208) hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<14, true, 1024>), grid, dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, stp, hm, imap);
-        else hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<14, false, 1024>), grid, dim3(1024), 0, st, q, oo, g, lse, dq, T, H, scale, stp, hm, imap);
-      }
-      else if (T > 192 && T <= 208) hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<14, true>), grid, dim3(512), 0, st, q, oo, g, lse, dq, T, H, scale, stp, hm | (attn_abl() == 4 ? 2 : 0), imap);
-      else hipLaunchKernelGGL((attn_bwd_fused_bf16_kernel<14, false>), grid, dim3(512), 0, st, q, oo, g, lse, dq, T, H, scale, stp, hm, imap);
-    } else {        // development knob GSL_ATTN_BWD_SPLIT=1: the two-kernel form
-      hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<14>, grid, dim3(512), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale, attn_abl(), hm);
-      {       // measured at B = 1024, T = 197: NT = 1 (two workgroups per CU) 410 us, NT = 2 480 us
-        if (attn_env("GSL_ATTN_NT", 1) == 1) hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<14, 1>), grid, dim3(512), 0, st, q, g, lse, delta_ws, dq, T, H, scale, attn_abl(), hm);
-        else hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<14, 2>), grid, dim3(512), 0, st, q, g, lse, delta_ws, dq, T, H, scale, attn_abl(), hm); }
-    }
-  }
-#if GSL_HAS_F32
-  else if (dtype == GSL_F32) {
-    const float* q = (const float*)qkv; const float* oo = (const float*)o; const float* g = (const float*)d_o;
-    float* dq = (float*)dqkv;
-    if (T <= 64) {
-      hipLaunchKernelGGL(attn_bwd_dq_f32_mfma_kernel<64>, grid, dim3(512), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale);
-      hipLaunchKernelGGL(attn_bwd_dkv_f32_mfma_kernel<64>, grid, dim3(512), 0, st, q, g, lse, delta_ws, dq, T, H, scale);
-    } else {
-      hipLaunchKernelGGL(attn_bwd_dq_f32_mfma_kernel<224>, grid, dim3(512), 0, st, q, oo, g, lse, dq, delta_ws, T, H, scale);
-      hipLaunchKernelGGL(attn_bwd_dkv_f32_mfma_kernel<224>, grid, dim3(512), 0, st, q, g, lse, delta_ws, dq, T, H, scale);
-    }
-  }
-#endif
-  else return fail(GSL_ERR_ARG, "gsl_attention_bwd: bad dtype%s %ld", "", dtype);
-  return check_launch("gsl_attention_bwd");
+  AttnCall c = attn_call(B, T, H, scale, dtype, qkv_layout, s);
+  c.qkv = qkv; c.o = o; c.d_o = d_o; c.lse = lse; c.out = dqkv; c.delta_ws = delta_ws;
+  return attn_launch(c, ATTN_BWD, "gsl_attention_bwd");
+}
+
+extern "C" int GSL_ENTRY(gsl_attention_fwd_cls)(const void* qkv, const void* q_cls, void* o_cls, float* lse_cls, int B, int T, int H, float scale,
+                                     int dtype, int qkv_layout, gsl_stream_t s) {
+  GSL_FORWARD_H16(dtype, h16_gsl_attention_fwd_cls(qkv, q_cls, o_cls, lse_cls, B, T, H, scale, dtype, qkv_layout, s));
+  GSL_CHECK_ARG(qkv && o_cls && lse_cls && B > 0 && T > 1 && H > 0, "null/size");
+  GSL_CHECK_ARG(T <= GSL_ATTN_MAX_T, GSL_ATTN_MAX_T_MSG);
+  GSL_CHECK_ARG(qkv_layout >= 0 && qkv_layout <= 2 && (qkv_layout != 2 || q_cls), "qkv_layout: 0 token-major, 1 head-major, 2 kv + q_cls");
+  AttnCall c = attn_call(B, T, H, scale, dtype, qkv_layout, s);
+  c.qkv = qkv; c.q_cls = q_cls; c.out = o_cls; c.lse_out = lse_cls;
+  return attn_launch(c, ATTN_FWD_CLS, "gsl_attention_fwd_cls");
+}
+
+extern "C" int GSL_ENTRY(gsl_attention_bwd_cls)(const void* qkv, const void* q_cls, const void* o, const void* d_o_cls, const float* lse, void* dqkv,
+                                     void* dq_cls, int B, int T, int H, float scale, int dtype, int qkv_layout, int cls_compact,
+                                     gsl_stream_t s) {
+  GSL_FORWARD_H16(dtype, h16_gsl_attention_bwd_cls(qkv, q_cls, o, d_o_cls, lse, dqkv, dq_cls, B, T, H, scale, dtype, qkv_layout, cls_compact, s));
+  GSL_CHECK_ARG(qkv && o && d_o_cls && lse && dqkv && B > 0 && T > 1 && H > 0, "null/size");      // (any T)
+  GSL_CHECK_ARG(qkv_layout >= 0 && qkv_layout <= 2 && (qkv_layout != 2 || (q_cls && dq_cls)), "qkv_layout: 0 token-major, 1 head-major, 2 kv + q_cls / dq_cls");
+  AttnCall c = attn_call(B, T, H, scale, dtype, qkv_layout, s);
+  c.qkv = qkv; c.q_cls = q_cls; c.o = o; c.d_o = d_o_cls; c.lse = lse; c.out = dqkv; c.dq_cls = dq_cls; c.cls_compact = cls_compact;
+  return attn_launch(c, ATTN_BWD_CLS, "gsl_attention_bwd_cls");
 }
 GSL_OPNS_END

@@ -25,6 +25,11 @@ U8_NCHW, U8_NHWC = 0, 1        # source layout of the uint8 gathers (gsl_patchif
 # gsl_gemm_tile: what gsl_gemm_tile_choice returns
 (TILE_RING64, TILE_RING64_WIDE, TILE_RING64_KSPLIT, TILE_128, TILE_RING256X128, TILE_P8, TILE_F32_VALU, TILE_F32_MFMA,
  TILE_F32X3_MFMA) = range(9)
+# gsl_attn_kernel: what gsl_attention_kernel_choice returns; its `direction` argument
+(ATTN_FWD_LONG, ATTN_FWD_T64, ATTN_FWD_PERSISTENT, ATTN_FWD_1024, ATTN_FWD_512, ATTN_FWD_F32_LONG, ATTN_FWD_F32, ATTN_BWD_LONG, ATTN_BWD_T64,
+ ATTN_BWD_MERGED, ATTN_BWD_FUSED_1024, ATTN_BWD_FUSED_512, ATTN_BWD_F32_LONG, ATTN_BWD_F32, ATTN_FWD_CLS, ATTN_FWD_CLS_LONG,
+ ATTN_BWD_CLS) = range(17)
+ATTN_DIRECTIONS = {"fwd": 0, "bwd": 1, "cls_fwd": 2, "cls_bwd": 3}
 NORM_SPLIT = 8
 SEED_ON_DEVICE = 0x80000000   # flag bit of a `site` argument: `seed` is a device pointer to a uint64 (HIP-graph replays)
 
@@ -53,6 +58,7 @@ SIGNATURES = {
     "gsl_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp],
     "gsl_attention_fwd_cls": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp],
     "gsl_attention_bwd_cls": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _vp],
+    "gsl_attention_kernel_choice": [_i, _i, _i, _i, _i, _i],
     "gsl_lora_grad_ws_elems": [_i, _i, _i],
     "gsl_lora_grad": [_vp, _l, _vp, _i, _vp, _l, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "gsl_lora_grad_batch_ws_elems": [_vp, _i],

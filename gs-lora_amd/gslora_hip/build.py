@@ -1,11 +1,12 @@
 """Build libgslora_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 Two libraries from the same sources:
-  libgslora_hip.so      the PRODUCT: the default kernels only, -fvisibility=hidden (exactly the entry points of include/gslora_hip.h
-                        are exported), no getenv() on any launch path.
-  libgslora_hip_dev.so  the LAB (-DGSL_DEV): additionally the GEMM variants that lost their A/Bs (csrc/gemm_dev_*.inc), the ablation /
-                        variant knobs and the cycle-stamp buffers that tools/bench_gemm*.py and tools/probes/ drive through the
-                        environment. Built on demand (`python -m gslora_hip.build --dev`), selected with GSLORA_HIP_LIB; never loaded
+  libgslora_hip.so      the PRODUCT: the kernels its launch rules reach (gemm_tile_choice, attn_kernel_choice) and no others,
+                        -fvisibility=hidden (exactly the entry points of include/gslora_hip.h are exported), no getenv() on any launch path.
+  libgslora_hip_dev.so  the LAB (-DGSL_DEV): additionally the GEMM variants that lost their A/Bs (csrc/gemm_dev_*.inc), the two-kernel
+                        attention backward at T > 64, and the ablation / variant knobs and cycle-stamp buffers that tools/bench_gemm*.py,
+                        tools/bench_attn.py and tools/probes/ drive through the environment (csrc/gemm_dev_launch.inc,
+                        csrc/attention_dev_launch.inc). Built on demand (`python -m gslora_hip.build --dev`), selected with GSLORA_HIP_LIB; never loaded
                         by default.
 """
 import os
@@ -19,7 +20,7 @@ SOURCES = ["gemm.hip", "norm.hip", "lora.hip", "patch.hip", "head.hip", "loss.hi
 # namespace gsl_h16, behind hidden h16_<entry> symbols that the exported entry points forward to (csrc/gsl_common.h, csrc/gsl_h16.h)
 SOURCES_F16 = ["gemm.hip", "attention.hip"]
 HEADERS = ["gsl_common.h", "gsl_h16.h", "exports.map", "gelu_g8_table.inc"]
-DEV_ONLY = ["gemm_dev_a.inc", "gemm_dev_b.inc", "gemm_dev_c.inc", "gemm_dev_launch.inc", "gemm_w4.inc", "gemm_o4.inc"]
+DEV_ONLY = ["gemm_dev_a.inc", "gemm_dev_b.inc", "gemm_dev_c.inc", "gemm_dev_launch.inc", "gemm_w4.inc", "gemm_o4.inc", "attention_dev_launch.inc"]
 OUT = os.path.join(HERE, "libgslora_hip.so")
 OUT_DEV = os.path.join(HERE, "libgslora_hip_dev.so")
 

@@ -253,6 +253,12 @@ def gemm_tile_choice(M, N, K, dtype, has_out2=False, in_kernel_lora=False, f32_m
     return int(L.load().gsl_gemm_tile_choice(int(M), int(N), int(K), gemm_code(dtype, f32_mode), 1 if has_out2 else 0, 1 if in_kernel_lora else 0))
 
 
+def attention_kernel(B, T, H, dtype, layout=0, direction="fwd"):
+    """The kernel(s) attention_fwd / attention_bwd / attention_fwd_cls / attention_bwd_cls (direction "fwd", "bwd", "cls_fwd", "cls_bwd")
+    launch for this shape in the product library: one of _lib.ATTN_* (gsl_attention_kernel_choice), -1 where the entry point refuses."""
+    return int(L.load().gsl_attention_kernel_choice(int(B), int(T), int(H), code(dtype), int(layout), L.ATTN_DIRECTIONS[direction]))
+
+
 def _share_ldo(what, epilogue, out, res, aux, out2):
     """The kernels index res, the aux of EPI_MUL and the out2 of EPI_BIAS_GELU with the row stride of `out` (ldo): row slices and column
     blocks are accepted for them, a row stride that differs from out's is refused. Every other aux / out2 (the LayerNorm column vector,

@@ -220,7 +220,7 @@ GSL_API int gsl_layernorm_bwd(const void* dy, const void* x, long x_row_stride, 
  * Token limit: 2 <= T <= GSL_ATTN_MAX_T (1025 = a 32 x 32 patch grid plus the cls token) for gsl_attention_fwd, gsl_attention_bwd and
  * gsl_attention_fwd_cls; a longer sequence fails with GSL_ERR_ARG. Up to 224 tokens (256 for the cls forward) an item's K / V sit in LDS
  * whole; above, they stream through LDS in 64-row panels with an online softmax (same output formats, same lse). gsl_attention_bwd_cls
- * takes any T. */
+ * takes any T. Which kernel a call launches is a function of the shape alone: gsl_attention_kernel_choice below. */
 #define GSL_ATTN_MAX_T 1025
 GSL_API int gsl_attention_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, float scale, int dtype, int qkv_layout, gsl_stream_t s);
 /* dqkv[dtype] [B*T,3*H*64] (token-major, always); delta_ws f32 [B,H,T] scratch. */
@@ -239,6 +239,31 @@ GSL_API int gsl_attention_fwd_cls(const void* qkv, const void* q_cls, void* o_cl
  * = 0; dq_cls unused); 2: writes dkv [B*T, 2*H*64] into `dqkv` and the query gradients into dq_cls [B, H*64]. */
 GSL_API int gsl_attention_bwd_cls(const void* qkv, const void* q_cls, const void* o, const void* d_o_cls, const float* lse, void* dqkv,
                                   void* dq_cls, int B, int T, int H, float scale, int dtype, int qkv_layout, int cls_compact, gsl_stream_t s);
+
+/* The kernel rule: the kernel(s) one of the four entry points above launches — a function of (B*H, T, dtype, direction) and the device's CU
+ * count (256 when no device is present), the same one the launches call. direction: 0 gsl_attention_fwd, 1 gsl_attention_bwd,
+ * 2 gsl_attention_fwd_cls, 3 gsl_attention_bwd_cls. The development build's GSL_ATTN_* knobs apply after it. Returns a gsl_attn_kernel, or
+ * -1 for arguments the entry point refuses with GSL_ERR_ARG (sizes, T > GSL_ATTN_MAX_T, dtype, qkv_layout). "items" = B*H. */
+enum gsl_attn_kernel {
+  GSL_ATTN_FWD_LONG = 0,         /* 16-bit, T > 224: K / V panels streamed through LDS, online softmax                            */
+  GSL_ATTN_FWD_T64 = 1,          /* 16-bit, T <= 64: one item per workgroup, four key tiles, 256 threads                          */
+  GSL_ATTN_FWD_PERSISTENT = 2,   /* 16-bit, 64 < T <= 208, items >= 2 CUs: persistent wave-specialised, one workgroup of 1024 per CU */
+  GSL_ATTN_FWD_1024 = 3,         /* 16-bit, 64 < T <= 224, items < CUs: one item per workgroup, sixteen waves                     */
+  GSL_ATTN_FWD_512 = 4,          /* 16-bit, 64 < T <= 224 otherwise: one item per workgroup, eight waves                          */
+  GSL_ATTN_FWD_F32_LONG = 5,     /* f32, T > 224                                                                                  */
+  GSL_ATTN_FWD_F32 = 6,          /* f32, T <= 224: matrix-core kernel (64-row panel up to T = 64, else 224 rows)                  */
+  GSL_ATTN_BWD_LONG = 7,         /* 16-bit, T > 224: dQ kernel, then dK / dV kernel, over streamed panels                         */
+  GSL_ATTN_BWD_T64 = 8,          /* 16-bit, T <= 64: dQ kernel, then dK / dV kernel, 256 threads                                  */
+  GSL_ATTN_BWD_MERGED = 9,       /* 16-bit, 192 < T <= 208, items >= 8 CUs: persistent, every score tile computed once            */
+  GSL_ATTN_BWD_FUSED_1024 = 10,  /* 16-bit, 64 < T <= 224, items < CUs: both phases in one launch, sixteen waves                  */
+  GSL_ATTN_BWD_FUSED_512 = 11,   /* 16-bit, 64 < T <= 224 otherwise: both phases in one launch, eight waves                       */
+  GSL_ATTN_BWD_F32_LONG = 12,    /* f32, T > 224: dQ kernel, then dK / dV kernel                                                  */
+  GSL_ATTN_BWD_F32 = 13,         /* f32, T <= 224: the matrix-core dQ and dK / dV kernels (panel as in the forward)               */
+  GSL_ATTN_FWD_CLS = 14,         /* cls forward, T <= 256 (either dtype)                                                          */
+  GSL_ATTN_FWD_CLS_LONG = 15,    /* cls forward, T > 256: 256-key chunks with an online max / sum                                 */
+  GSL_ATTN_BWD_CLS = 16          /* cls backward, any T                                                                           */
+};
+GSL_API int gsl_attention_kernel_choice(int B, int T, int H, int dtype, int qkv_layout, int direction);
 
 /* ---- K9 LoRA gradient (skinny, reduction over M rows): G[n*gsn + j*gsj] (+)= sum_m Y[m,n] * U[m,j]
  * Y[dtype] [M,N] with row stride ldy >= N elements (a column block of a wider tensor is allowed), U[dtype] [M,ldu] (first r columns

@@ -238,6 +238,8 @@ def test_development_build_variants_on_the_probes(ops, monkeypatch, variant, T, 
     two-kernel backward at its default tiling (bf16) and the fused backward."""
     from gslora_hip import _lib as L
     B, H = 2, 2
+    # four items, fewer than CUs: the product library runs the sixteen-wave forms of the per-item forward and of the fused backward at all four T
+    assert ops.attention_kernel(B, T, H, dt) == L.ATTN_FWD_1024 and ops.attention_kernel(B, T, H, dt, direction="bwd") == L.ATTN_BWD_FUSED_1024
     c = get_case(tag, B, T, H, dt)
     o, lse = ops.attention_fwd(c["qkv"], B, T, H, SCALE)
     dqkv = ops.attention_bwd(c["qkv"], o, c["d_o"], lse, B, T, H, SCALE)

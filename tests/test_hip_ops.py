@@ -323,12 +323,13 @@ def test_attention_fwd_persistent_bit_identical_to_per_item_kernel(ops, B, T, H,
     """bf16, 64 < T <= 208, B*H >= 2 x CUs: the persistent wave-specialised forward (3 loader waves + 13 compute waves per CU) must
     reproduce the one-item-per-workgroup kernel bit for bit (same fragments, same operation order) — including the ragged last round
     of items and the zero rows of the panels."""
+    from gslora_hip import _lib as L
     dt = torch.bfloat16
     scale = 64 ** -0.5
+    assert ops.attention_kernel(B, T, H, dt) == L.ATTN_FWD_PERSISTENT      # what the product library runs at this shape
     qkv = rnd(B * T, 3 * H * 64, seed=31, scale=1.3).cuda().to(dt)
     o1, lse1 = ops.attention_fwd(qkv, B, T, H, scale)
     o1b, lse1b = ops.attention_fwd(qkv, B, T, H, scale)
-    from gslora_hip import _lib as L
     monkeypatch.setenv("GSL_ATTN_PERSISTENT", "0")      # a knob of the development build only
     with L.use_dev():
         o0, lse0 = ops.attention_fwd(qkv, B, T, H, scale)
@@ -339,13 +340,15 @@ def test_attention_fwd_persistent_bit_identical_to_per_item_kernel(ops, B, T, H,
 @pytest.mark.parametrize("B,T,H", [(3, 197, 8), (2, 150, 4), (5, 224, 2), (150, 197, 8), (131, 150, 12), (300, 224, 2), (3, 193, 4), (3, 192, 4), (5, 208, 4), (3, 209, 2)])
 def test_attention_bwd_fused_bit_identical_to_two_kernel_form(ops, B, T, H, monkeypatch):
     """bf16, T > 64: the single-launch backward (dQ phase then dK/dV phase over the same LDS panels) == the dQ kernel + the dK/dV kernel."""
+    from gslora_hip import _lib as L
     dt = torch.bfloat16
     scale = 64 ** -0.5
+    # what the product library runs at this shape: one of the two fused forms (sixteen waves per item below one item per CU, eight from there)
+    assert ops.attention_kernel(B, T, H, dt, direction="bwd") in (L.ATTN_BWD_FUSED_1024, L.ATTN_BWD_FUSED_512)
     qkv = rnd(B * T, 3 * H * 64, seed=21, scale=1.3).cuda().to(dt)
     o, lse = ops.attention_fwd(qkv, B, T, H, scale)
     d_o = rnd(B * T, H * 64, seed=22).cuda().to(dt)
     fused = ops.attention_bwd(qkv, o, d_o, lse, B, T, H, scale)
-    from gslora_hip import _lib as L
     monkeypatch.setenv("GSL_ATTN_BWD_SPLIT", "1")       # a knob of the development build only
     with L.use_dev():
         split = ops.attention_bwd(qkv, o, d_o, lse, B, T, H, scale)
@@ -471,14 +474,15 @@ def test_gemm_store_compact_second_output(ops, dt, M):
 def test_attention_bwd_product_library_at_step_size_equals_fused_kernel(ops, dt, monkeypatch):
     """The PRODUCT library at a batch that takes the merged kernel there (8 items per CU: 264 images x 8 heads), head-major input as in the step,
     against the development build's fused kernel: bit-identical."""
+    from gslora_hip import _lib as L
     B, T, H = 264, 197, 8
     scale = 64 ** -0.5
+    assert ops.attention_kernel(B, T, H, dt, layout=1, direction="bwd") == L.ATTN_BWD_MERGED
     qkv = rnd(B * T, 3 * H * 64, seed=51, scale=1.2).cuda().to(dt)
     qin = _to_head_major(qkv, B, T, H)
     o, lse = ops.attention_fwd(qin, B, T, H, scale, layout=1)
     d_o = rnd(B * T, H * 64, seed=52).cuda().to(dt)
     prod = ops.attention_bwd(qin, o, d_o, lse, B, T, H, scale, layout=1)
-    from gslora_hip import _lib as L
     monkeypatch.setenv("GSL_ATTN_BWD_MERGED", "0")      # a knob of the development build only
     with L.use_dev():
         fused = ops.attention_bwd(qin, o, d_o, lse, B, T, H, scale, layout=1)
