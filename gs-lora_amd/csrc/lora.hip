@@ -68,12 +68,17 @@ template <> struct LgRaw<float> {
 
 // block = 256 threads = CG column groups x RP row phases (RP = 256 / CG in {1,2,4}); the RP phases walk
 // interleaved rows of the block's row range and are combined through LDS in a fixed order.
-template <typename T, int R>
+// NC > 1 (ranks above 16, R == 16): the rank runs as NC chunks of 16 columns, one pass over the block's rows per chunk, into the partial
+// layout part[split][n][16 * NC]; exactly the columns [0, r) of U are read (the rest of the last chunk is zero in LDS). This form is
+// the parity mode and the edge shapes, so Y is read NC times rather than holding V x 16 x NC accumulators (which would spill).
+template <typename T, int R, int NC = 1>
 __global__ __launch_bounds__(256) void lora_grad_partial_kernel(const T* __restrict__ Y, long ldy, const T* __restrict__ U, int ldu,
                                                                 float* __restrict__ part, int M, int N, int rows_per_split,
-                                                                int CG) {
+                                                                int CG, int r) {
   fp16_sat_on();
+  static_assert(NC == 1 || R == 16, "chunks are 16 columns wide");
   constexpr int V = LgVec<T>::V;
+  constexpr int RT = R * NC;      // row length of the partial layout
   __shared__ float us[LG_ROWS][R];
   extern __shared__ __attribute__((aligned(16))) float red[];   // (RP-1) * CG * V * R floats
   const int ncol = N / V;
@@ -83,6 +88,8 @@ __global__ __launch_bounds__(256) void lora_grad_partial_kernel(const T* __restr
   const bool active = cg < ncol;
   const int split = blockIdx.y;
   const int r0 = split * rows_per_split, r1 = min(M, r0 + rows_per_split);
+  for (int ch = 0; ch < NC; ++ch) {      // one pass over the block's rows per 16-column chunk (NC == 1: the one pass; body kept at its indentation)
+  const int j0 = ch * R;
   float acc[V][R];
 #pragma unroll
   for (int i = 0; i < V; ++i)
@@ -98,7 +105,7 @@ __global__ __launch_bounds__(256) void lora_grad_partial_kernel(const T* __restr
     __syncthreads();
     for (int t = threadIdx.x; t < LG_ROWS * R; t += blockDim.x) {
       const int rr = t / R, j = t % R;
-      us[rr][j] = (rr < nr) ? Elem<T>::ld(U + (size_t)(rb + rr) * ldu + j) : 0.f;
+      us[rr][j] = (rr < nr && (NC == 1 || j0 + j < r)) ? Elem<T>::ld(U + (size_t)(rb + rr) * ldu + j0 + j) : 0.f;
     }
     raw_t cur[LGF], nxt[LGF];
     if (active) {
@@ -157,12 +164,13 @@ __global__ __launch_bounds__(256) void lora_grad_partial_kernel(const T* __restr
     }
   }
   if (active && phase == 0) {
-    float* p = part + ((size_t)split * N + (size_t)cg * V) * R;
+    float* p = part + ((size_t)split * N + (size_t)cg * V) * RT + j0;
 #pragma unroll
     for (int i = 0; i < V; ++i)
 #pragma unroll
-      for (int j = 0; j < R; ++j) p[i * R + j] = acc[i][j];
+      for (int j = 0; j < R; ++j) p[i * RT + j] = acc[i][j];
   }
+  }      // ch
 }
 
 // ---- MFMA form of the partial sums (bf16 operands, N % 256 == 0): G^T-free contraction over the ROW index.
@@ -179,18 +187,31 @@ typedef __attribute__((ext_vector_type(8))) __bf16 lg_bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 lg_f16x8_t;
 typedef __attribute__((ext_vector_type(4))) float lg_f32x4_t;
 constexpr int LGM_CN = 256, LGM_YLD = LGM_CN + 16, LGM_ULD = 32, LGM_K = 32;
+// row length of the U slab in LDS for NB 16-column B-fragments. One fragment keeps the 32 it always had. Wider slabs are padded by 8
+// elements: rows are then 20 / 36 dwords apart, the sixteen rows of a transpose read start at sixteen different multiples of 4 dwords
+// (mod 64) and every bank is touched exactly twice by the 64 x 8 bytes of the read — its two-pass minimum; rows stay 16-byte aligned.
+constexpr int lgm_uld(int NB) { return NB == 1 ? LGM_ULD : 16 * NB + 8; }
+constexpr int LGM_YS_ELEMS = 2 * LGM_K * LGM_YLD;
+constexpr int lgm_us_elems(int NB) { return 2 * LGM_K * lgm_uld(NB); }
 
-// body of one workgroup: column block bxi (256 columns of Y), row split `split`; R = padded rank of the partial layout (8 or 16)
+// body of one workgroup: column block bxi (256 columns of Y), row split `split`.
+// NB = number of 16-column B-fragments of U: 1 -> R = padded rank of the partial layout (8 or 16), r unused, columns 0..15 of U are read;
+// 2 / 4 -> R = 32 / 64, and the 8-column chunks [0, 8 * ceil(r / 8)) of U are read, the others are zeros in LDS. A 32-row slab of Y is
+// staged once and each of its four A-fragments per wave meets all NB B-fragments: Y crosses HBM once whatever the rank.
 // F16: the operands are IEEE fp16 (dtype GSL_F16) instead of bf16 — the same bytes through the same LDS path, the other MFMA opcode
-template <bool F16>
+template <bool F16, int NB>
 __device__ __forceinline__ void lgm_block(const bf16_t* __restrict__ Y, long ldy, const bf16_t* __restrict__ U, int ldu,
-                                          float* __restrict__ part, int M, int N, int rows_per_split, int R, int bxi, int split) {
-  __shared__ __attribute__((aligned(16))) bf16_t ys[2][LGM_K * LGM_YLD];
-  __shared__ __attribute__((aligned(16))) bf16_t us[2][LGM_K * LGM_ULD];
+                                          float* __restrict__ part, int M, int N, int rows_per_split, int R, int r_live, int bxi, int split,
+                                          bf16_t* __restrict__ ys, bf16_t* __restrict__ us) {
+  constexpr int ULD = lgm_uld(NB), CH = 2 * NB;      // CH 8-column chunks per row of the U slab
+  constexpr int YB = LGM_K * LGM_YLD, UB = LGM_K * ULD;      // elements per LDS buffer
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n0 = bxi * LGM_CN;
   const int r0 = split * rows_per_split, r1 = min(M, r0 + rows_per_split);
   const int lc = tid & 31, lr = tid >> 5;
+  const int urow = tid / CH, uch = tid % CH;
+  const bool uthread = tid < LGM_K * CH;
+  const bool uload = uthread && (NB == 1 || uch * 8 < r_live);
   uint4 yreg[4], ureg = make_uint4(0, 0, 0, 0);
   auto gload = [&](int rb) {
 #pragma unroll
@@ -198,19 +219,21 @@ __device__ __forceinline__ void lgm_block(const bf16_t* __restrict__ Y, long ldy
       const int r = rb + lr + 8 * i;
       yreg[i] = (r < r1) ? *reinterpret_cast<const uint4*>(Y + (size_t)r * ldy + n0 + lc * 8) : make_uint4(0, 0, 0, 0);
     }
-    if (tid < 64) {
-      const int r = rb + (tid >> 1);
-      ureg = (r < r1) ? *reinterpret_cast<const uint4*>(U + (size_t)r * ldu + (tid & 1) * 8) : make_uint4(0, 0, 0, 0);
+    if (uload) {
+      const int r = rb + urow;
+      ureg = (r < r1) ? *reinterpret_cast<const uint4*>(U + (size_t)r * ldu + uch * 8) : make_uint4(0, 0, 0, 0);
     }
   };
   auto lstore = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(&ys[buf][(lr + 8 * i) * LGM_YLD + lc * 8]) = yreg[i];
-    if (tid < 64) *reinterpret_cast<uint4*>(&us[buf][(tid >> 1) * LGM_ULD + (tid & 1) * 8]) = ureg;
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(&ys[buf * YB + (lr + 8 * i) * LGM_YLD + lc * 8]) = yreg[i];
+    if (uthread) *reinterpret_cast<uint4*>(&us[buf * UB + urow * ULD + uch * 8]) = ureg;
   };
-  lg_f32x4_t acc[4];
+  lg_f32x4_t acc[4][NB];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = lg_f32x4_t{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[t][b] = lg_f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int g = lane >> 4, i16 = lane & 15;
   const int trow = 4 * g + (i16 >> 2), tcol = (i16 & 3) * 4;       // this lane's piece of a 4 x 16 block (transpose-read address)
   gload(r0);
@@ -221,37 +244,48 @@ __device__ __forceinline__ void lgm_block(const bf16_t* __restrict__ Y, long ldy
     const int buf = it & 1;
     const bool more = rb + LGM_K < r1;
     if (more) gload(rb + LGM_K);
-    union { lg_v4s_t h[2]; lg_bf16x8_t v; lg_f16x8_t w; } bf;
-    bf.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lg_lds_v4s_p)(&us[buf][trow * LGM_ULD + tcol]));
-    bf.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lg_lds_v4s_p)(&us[buf][(trow + 16) * LGM_ULD + tcol]));
+    union { lg_v4s_t h[2]; lg_bf16x8_t v; lg_f16x8_t w; } bf[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      bf[b].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lg_lds_v4s_p)(&us[buf * UB + trow * ULD + b * 16 + tcol]));
+      bf[b].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lg_lds_v4s_p)(&us[buf * UB + (trow + 16) * ULD + b * 16 + tcol]));
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       union { lg_v4s_t h[2]; lg_bf16x8_t v; lg_f16x8_t w; } af;
-      const bf16_t* p = &ys[buf][trow * LGM_YLD + wave * 64 + t * 16 + tcol];
+      const bf16_t* p = &ys[buf * YB + trow * LGM_YLD + wave * 64 + t * 16 + tcol];
       af.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lg_lds_v4s_p)(p));
       af.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lg_lds_v4s_p)(p + 16 * LGM_YLD));
-      if constexpr (F16) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af.w, bf.w, acc[t], 0, 0, 0);
-      else acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf.v, acc[t], 0, 0, 0);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if constexpr (F16) acc[t][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af.w, bf[b].w, acc[t][b], 0, 0, 0);
+        else acc[t][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf[b].v, acc[t][b], 0, 0, 0);
+      }
     }
     if (more) lstore(buf ^ 1);
     __syncthreads();
   }
-  // acc[t][r] = G[n = n0 + wave*64 + t*16 + 4g + r][j = lane & 15]
-  if (i16 < R) {
+  // acc[t][b][r] = G[n = n0 + wave*64 + t*16 + 4g + r][j = 16 b + (lane & 15)]
+  if (NB > 1 || i16 < R) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int n = n0 + wave * 64 + t * 16 + 4 * g + r;
-        part[((size_t)split * N + n) * R + i16] = acc[t][r];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) part[((size_t)split * N + n) * R + b * 16 + i16] = acc[t][b][r];
       }
   }
 }
+// R = 8 / 16: one B-fragment (r_live unused); R = 32 / 64: R / 16 of them
 template <int R, bool F16>
 __global__ __launch_bounds__(256) void lora_grad_mfma_kernel(const bf16_t* __restrict__ Y, long ldy, const bf16_t* __restrict__ U, int ldu,
-                                                             float* __restrict__ part, int M, int N, int rows_per_split) {
+                                                             float* __restrict__ part, int M, int N, int rows_per_split, int r_live) {
   fp16_sat_on();
-  lgm_block<F16>(Y, ldy, U, ldu, part, M, N, rows_per_split, R, blockIdx.x, blockIdx.y);
+  constexpr int NB = R <= 16 ? 1 : R / 16;
+  __shared__ __attribute__((aligned(16))) bf16_t ys[LGM_YS_ELEMS];
+  __shared__ __attribute__((aligned(16))) bf16_t us[lgm_us_elems(NB)];
+  lgm_block<F16, NB>(Y, ldy, U, ldu, part, M, N, rows_per_split, R, r_live, blockIdx.x, blockIdx.y, ys, us);
 }
 
 // ---- batched form: every LoRA-gradient reduction of a backward pass in two launches (the launch-bound regime: few-shot batches run 24
@@ -264,14 +298,22 @@ struct LgbEntry {
 };
 struct LgbArgs { int n; LgbEntry e[LGB_MAX]; };
 
-template <bool F16>
+// MAXNB = 1: every entry has R <= 16 (the launch as it always was). MAXNB = 4: entries of any R in {8, 16, 32, 64}; the workgroup takes
+// the body of its entry's R (a workgroup-uniform choice, made once), all bodies share one LDS allocation.
+template <bool F16, int MAXNB>
 __global__ __launch_bounds__(256) void lora_grad_batch_partial_kernel(const LgbArgs a, float* __restrict__ ws) {
   fp16_sat_on();
+  __shared__ __attribute__((aligned(16))) bf16_t ys[LGM_YS_ELEMS];
+  __shared__ __attribute__((aligned(16))) bf16_t us[lgm_us_elems(MAXNB)];
   int d = 0;
   for (int k = 1; k < a.n; ++k) d = ((int)blockIdx.x >= a.e[k].wg0) ? k : d;
   const LgbEntry& e = a.e[d];
   const int local = (int)blockIdx.x - e.wg0;
-  lgm_block<F16>(e.Y, e.ldy, e.U, e.ldu, ws + e.ws0, e.M, e.N, e.rps, e.R, local % e.bx, local / e.bx);
+  if constexpr (MAXNB > 1) {
+    if (e.R == 64) { lgm_block<F16, 4>(e.Y, e.ldy, e.U, e.ldu, ws + e.ws0, e.M, e.N, e.rps, 64, e.r, local % e.bx, local / e.bx, ys, us); return; }
+    if (e.R == 32) { lgm_block<F16, 2>(e.Y, e.ldy, e.U, e.ldu, ws + e.ws0, e.M, e.N, e.rps, 32, e.r, local % e.bx, local / e.bx, ys, us); return; }
+  }
+  lgm_block<F16, 1>(e.Y, e.ldy, e.U, e.ldu, ws + e.ws0, e.M, e.N, e.rps, e.R, e.r, local % e.bx, local / e.bx, ys, us);
 }
 // fixed-order sum of an entry's splits, output strides (+ accumulate) applied on the way out
 __global__ __launch_bounds__(256) void lora_grad_batch_reduce_kernel(const LgbArgs a, const float* __restrict__ ws, const float* __restrict__ gscale) {
@@ -302,6 +344,10 @@ static inline void lgm_plan(int M, int N, int& bx, int& nsplit, int& rps) {
   nsplit = (M + rps - 1) / rps;
 }
 static inline bool lgm_usable(int M, int N, int ldu, int dtype) { return dtype != GSL_F32 && (N % LGM_CN) == 0 && ldu >= 16 && M >= 64; }
+// padded rank of the partial layout part[split][n][R]
+static inline int lg_padded_rank(int r) { return r <= 8 ? 8 : (r <= 16 ? 16 : (r <= 32 ? 32 : 64)); }
+// columns of U the 16-byte-aligned MFMA form reads: 0..15 up to rank 16 (the contract it always had), whole 8-column chunks above
+static inline int lgm_u_cols(int r) { return r <= 16 ? 16 : ((r + 7) / 8) * 8; }
 
 // level 1: thread (idx, sb) sums LG_FAN consecutive splits  -> part2[sb][idx]
 __global__ __launch_bounds__(256) void lora_grad_reduce1_kernel(const float* __restrict__ part, float* __restrict__ part2,
@@ -355,6 +401,13 @@ __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __re
   }
 }
 
+static inline void lg_reduce2(hipStream_t st, const float* part2, float* G, long gsn, long gsj, int N, int r, int R, int nslab, int accumulate,
+                              const float* gscale) {
+#define GSL_LGR2(RR) hipLaunchKernelGGL(lora_grad_reduce2_kernel<RR>, dim3((N * RR + 255) / 256), dim3(256), 0, st, part2, G, gsn, gsj, N, r, nslab, accumulate, gscale)
+  if (R == 8) GSL_LGR2(8); else if (R == 16) GSL_LGR2(16); else if (R == 32) GSL_LGR2(32); else GSL_LGR2(64);
+#undef GSL_LGR2
+}
+
 static inline void lg_plan(int M, int N, int V, int R, int& CG, int& bx, int& nsplit, int& rps) {
   const int ncol = N / V;
   CG = ncol >= 256 ? 256 : ((ncol > 64 || R > 8) ? 128 : 64);   // keeps the phase-combine LDS <= 48 KB
@@ -369,11 +422,11 @@ static inline void lg_plan(int M, int N, int V, int R, int& CG, int& bx, int& ns
 }
 
 extern "C" long gsl_lora_grad_ws_elems(int M, int N, int r) {
-  const int R = (r <= 8) ? 8 : 16;
+  const int R = lg_padded_rank(r);
   long best = 0;
   for (int V = 4; V <= 8; V += 4) {
     int CG, bx, nsplit, rps;
-    lg_plan(M, N, V, R, CG, bx, nsplit, rps);
+    lg_plan(M, N, V, R > 16 ? 16 : R, CG, bx, nsplit, rps);
     const long slabs = (long)nsplit + (nsplit + LG_FAN - 1) / LG_FAN;
     if (slabs > best) best = slabs;
   }
@@ -389,12 +442,12 @@ extern "C" long gsl_lora_grad_ws_elems(int M, int N, int r) {
 extern "C" int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, float* G, long gsn, long gsj, int M, int N, int r,
                              int dtype, int accumulate, float* ws, const float* gscale, gsl_stream_t s) {
   GSL_CHECK_ARG(Y && U && G && ws && M > 0 && N > 0 && ldy >= N, "null/size");
-  GSL_CHECK_ARG(r >= 1 && r <= 16 && ldu >= 16 && (ldu % 8) == 0, "r in [1,16], ldu >= 16 (zero-padded)");
+  GSL_CHECK_ARG(r >= 1 && r <= 64 && ldu >= 16 && ldu >= r && (ldu % 8) == 0, "r in [1,64], ldu >= max(16, r) (zero-padded), ldu % 8 == 0");
   GSL_CHECK_ARG(dtype == GSL_F32 || dtype == GSL_BF16 || dtype == GSL_F16, "dtype");
   const int V = (dtype != GSL_F32) ? 8 : 4;
   GSL_CHECK_ARG((N % V) == 0, "N must be a multiple of the vector width");
   hipStream_t st = as_stream(s);
-  const int R = (r <= 8) ? 8 : 16;
+  const int R = lg_padded_rank(r);
   int CG, bx, nsplit, rps;
   {
 #ifdef GSL_DEV
@@ -403,40 +456,43 @@ extern "C" int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, fl
 #else
     const bool want = true;
 #endif
-    if (want && lgm_usable(M, N, ldu, dtype) && (reinterpret_cast<uintptr_t>(U) % 16) == 0 && (reinterpret_cast<uintptr_t>(Y) % 16) == 0 &&
+    if (want && lgm_usable(M, N, ldu, dtype) && ldu >= lgm_u_cols(r) && (reinterpret_cast<uintptr_t>(U) % 16) == 0 && (reinterpret_cast<uintptr_t>(Y) % 16) == 0 &&
         ((size_t)ldu * 2) % 16 == 0 && ((size_t)ldy * 2) % 16 == 0) {
       lgm_plan(M, N, bx, nsplit, rps);
-#define GSL_LGM(RR, FF) hipLaunchKernelGGL((lora_grad_mfma_kernel<RR, FF>), dim3(bx, nsplit), dim3(256), 0, st, (const bf16_t*)Y, ldy, (const bf16_t*)U, ldu, ws, M, N, rps)
-      if (dtype == GSL_F16) { if (R == 8) GSL_LGM(8, true); else GSL_LGM(16, true); }
-      else { if (R == 8) GSL_LGM(8, false); else GSL_LGM(16, false); }
+#define GSL_LGM(RR, FF) hipLaunchKernelGGL((lora_grad_mfma_kernel<RR, FF>), dim3(bx, nsplit), dim3(256), 0, st, (const bf16_t*)Y, ldy, (const bf16_t*)U, ldu, ws, M, N, rps, r)
+      if (dtype == GSL_F16) { if (R == 8) GSL_LGM(8, true); else if (R == 16) GSL_LGM(16, true); else if (R == 32) GSL_LGM(32, true); else GSL_LGM(64, true); }
+      else { if (R == 8) GSL_LGM(8, false); else if (R == 16) GSL_LGM(16, false); else if (R == 32) GSL_LGM(32, false); else GSL_LGM(64, false); }
 #undef GSL_LGM
       int rc0 = check_launch("gsl_lora_grad(mfma partial)");
       if (rc0) return rc0;
       const int totm = N * R;
       if (nsplit <= 160 && totm >= 8192) {     // few splits, many outputs: one launch (measured 166 -> 162 us at N = 2048; at N = 512 the two-level form wins)
-        if (R == 8) hipLaunchKernelGGL(lora_grad_reduce_kernel<8>, dim3((totm + 63) / 64), dim3(256), 0, st, ws, G, gsn, gsj, N, r, nsplit, accumulate, gscale);
-        else hipLaunchKernelGGL(lora_grad_reduce_kernel<16>, dim3((totm + 63) / 64), dim3(256), 0, st, ws, G, gsn, gsj, N, r, nsplit, accumulate, gscale);
+#define GSL_LGR(RR) hipLaunchKernelGGL(lora_grad_reduce_kernel<RR>, dim3((totm + 63) / 64), dim3(256), 0, st, ws, G, gsn, gsj, N, r, nsplit, accumulate, gscale)
+        if (R == 8) GSL_LGR(8); else if (R == 16) GSL_LGR(16); else if (R == 32) GSL_LGR(32); else GSL_LGR(64);
+#undef GSL_LGR
         return check_launch("gsl_lora_grad(reduce)");
       }
       float* part2m = ws + (size_t)nsplit * N * R;
       int nslabm = (nsplit + LG_FAN - 1) / LG_FAN;
       if (nslabm == 1) { part2m = ws; nslabm = nsplit; }      // one slab: the second level sums the splits itself, in the same order (one launch less)
       else hipLaunchKernelGGL(lora_grad_reduce1_kernel, dim3((totm + 255) / 256, nslabm), dim3(256), 0, st, ws, part2m, totm, nsplit);
-      if (R == 8) hipLaunchKernelGGL(lora_grad_reduce2_kernel<8>, dim3((totm + 255) / 256), dim3(256), 0, st, part2m, G, gsn, gsj, N, r, nslabm, accumulate, gscale);
-      else hipLaunchKernelGGL(lora_grad_reduce2_kernel<16>, dim3((totm + 255) / 256), dim3(256), 0, st, part2m, G, gsn, gsj, N, r, nslabm, accumulate, gscale);
+      lg_reduce2(st, part2m, G, gsn, gsj, N, r, R, nslabm, accumulate, gscale);
       return check_launch("gsl_lora_grad(reduce)");
     }
   }
-  lg_plan(M, N, V, R, CG, bx, nsplit, rps);
+  const int RK = R > 16 ? 16 : R;      // accumulator columns of the kernel: above rank 16 it runs R / 16 chunks of 16
+  lg_plan(M, N, V, RK, CG, bx, nsplit, rps);
   const int RP = 256 / CG;
-  const size_t red_bytes = (size_t)(RP - 1) * CG * V * R * sizeof(float);
+  const size_t red_bytes = (size_t)(RP - 1) * CG * V * RK * sizeof(float);
   float* part2 = ws + (size_t)nsplit * N * R;
-#define LAUNCH(TT, RR)                                                                                                   \
-  hipLaunchKernelGGL((lora_grad_partial_kernel<TT, RR>), dim3(bx, nsplit), dim3(256), red_bytes, st, (const TT*)Y, ldy, (const TT*)U, \
-                     ldu, ws, M, N, rps, CG)
-  if (dtype == GSL_BF16) { if (R == 8) LAUNCH(bf16_t, 8); else LAUNCH(bf16_t, 16); }
-  else if (dtype == GSL_F16) { if (R == 8) LAUNCH(f16_t, 8); else LAUNCH(f16_t, 16); }
-  else { if (R == 8) LAUNCH(float, 8); else LAUNCH(float, 16); }
+#define LAUNCH(TT, RR, NC)                                                                                                   \
+  hipLaunchKernelGGL((lora_grad_partial_kernel<TT, RR, NC>), dim3(bx, nsplit), dim3(256), red_bytes, st, (const TT*)Y, ldy, (const TT*)U, \
+                     ldu, ws, M, N, rps, CG, r)
+#define LAUNCH_R(TT) do { if (R == 8) LAUNCH(TT, 8, 1); else if (R == 16) LAUNCH(TT, 16, 1); else if (R == 32) LAUNCH(TT, 16, 2); else LAUNCH(TT, 16, 4); } while (0)
+  if (dtype == GSL_BF16) LAUNCH_R(bf16_t);
+  else if (dtype == GSL_F16) LAUNCH_R(f16_t);
+  else LAUNCH_R(float);
+#undef LAUNCH_R
 #undef LAUNCH
   int rc = check_launch("gsl_lora_grad(partial)");
   if (rc) return rc;
@@ -444,8 +500,7 @@ extern "C" int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, fl
   int nslab = (nsplit + LG_FAN - 1) / LG_FAN;
   if (nslab == 1) { part2 = ws; nslab = nsplit; }
   else hipLaunchKernelGGL(lora_grad_reduce1_kernel, dim3((tot + 255) / 256, nslab), dim3(256), 0, st, ws, part2, tot, nsplit);
-  if (R == 8) hipLaunchKernelGGL(lora_grad_reduce2_kernel<8>, dim3((tot + 255) / 256), dim3(256), 0, st, part2, G, gsn, gsj, N, r, nslab, accumulate, gscale);
-  else hipLaunchKernelGGL(lora_grad_reduce2_kernel<16>, dim3((tot + 255) / 256), dim3(256), 0, st, part2, G, gsn, gsj, N, r, nslab, accumulate, gscale);
+  lg_reduce2(st, part2, G, gsn, gsj, N, r, R, nslab, accumulate, gscale);
   return check_launch("gsl_lora_grad(reduce)");
 }
 
@@ -509,8 +564,8 @@ __global__ void gnorm_final_kernel(const float* __restrict__ partial, const int3
   }
 }
 
-static int lgb_plan(const gsl_lgrad_desc* descs, int n, LgbArgs* out, long* ws_elems, int* nwg, int* nrb) {
-  long ws = 0; int wg = 0, rb = 0;
+static int lgb_plan(const gsl_lgrad_desc* descs, int n, LgbArgs* out, long* ws_elems, int* nwg, int* nrb, int* max_R = nullptr) {
+  long ws = 0; int wg = 0, rb = 0, maxR = 0;
   // row splits: the launch as a whole should fill the chip about four times over (1024 workgroups), not every entry on its own
   long sum_bx = 0;
   for (int k = 0; k < n; ++k) sum_bx += descs[k].N > 0 ? descs[k].N / LGM_CN : 0;
@@ -518,13 +573,15 @@ static int lgb_plan(const gsl_lgrad_desc* descs, int n, LgbArgs* out, long* ws_e
   for (int k = 0; k < n; ++k) {
     const gsl_lgrad_desc& d = descs[k];
     GSL_CHECK_ARG(d.Y && d.U && d.G && d.M > 0 && d.N > 0 && d.ldy >= d.N, "null/size");
-    GSL_CHECK_ARG(d.r >= 1 && d.r <= 16 && d.ldu >= 16 && (d.ldu % 8) == 0 && (d.ldy % 8) == 0 && (d.N % LGM_CN) == 0, "r in [1,16], ldu >= 16, N % 256 == 0, 16-byte rows");
+    GSL_CHECK_ARG(d.r >= 1 && d.r <= 64 && d.ldu >= lgm_u_cols(d.r) && (d.ldu % 8) == 0 && (d.ldy % 8) == 0 && (d.N % LGM_CN) == 0,
+                  "r in [1,64], ldu >= 16 (above rank 16: >= 8 * ceil(r / 8)), N % 256 == 0, 16-byte rows");
     GSL_CHECK_ARG((reinterpret_cast<uintptr_t>(d.Y) % 16) == 0 && (reinterpret_cast<uintptr_t>(d.U) % 16) == 0, "16-byte aligned operands");
     const int bx = d.N / LGM_CN, steps = (d.M + LGM_K - 1) / LGM_K;
     int nsplit = min(steps, split_target);
     const int rps = ((steps + nsplit - 1) / nsplit) * LGM_K;
     nsplit = (d.M + rps - 1) / rps;
-    const int R = d.r <= 8 ? 8 : 16;
+    const int R = lg_padded_rank(d.r);
+    if (R > maxR) maxR = R;
     if (out) {
       LgbEntry& e = out->e[k];
       e.Y = (const bf16_t*)d.Y; e.U = (const bf16_t*)d.U; e.G = d.G; e.ldy = d.ldy; e.gsn = d.gsn; e.gsj = d.gsj; e.ws0 = ws;
@@ -539,6 +596,7 @@ static int lgb_plan(const gsl_lgrad_desc* descs, int n, LgbArgs* out, long* ws_e
   if (ws_elems) *ws_elems = ws;
   if (nwg) *nwg = wg;
   if (nrb) *nrb = rb;
+  if (max_R) *max_R = maxR;
   return GSL_OK;
 }
 
@@ -560,11 +618,16 @@ extern "C" int gsl_lora_grad_batch(const gsl_lgrad_desc* descs, int n, float* ws
   hipStream_t st = as_stream(s);
   for (int k0 = 0; k0 < n; k0 += LGB_MAX) {
     LgbArgs a;
-    int nwg = 0, nrb = 0;
-    const int rc = lgb_plan(descs + k0, min(LGB_MAX, n - k0), &a, nullptr, &nwg, &nrb);
+    int nwg = 0, nrb = 0, maxR = 0;
+    const int rc = lgb_plan(descs + k0, min(LGB_MAX, n - k0), &a, nullptr, &nwg, &nrb, &maxR);
     if (rc) return rc;
-    if (dtype == GSL_F16) hipLaunchKernelGGL(lora_grad_batch_partial_kernel<true>, dim3(nwg), dim3(256), 0, st, a, ws);
-    else hipLaunchKernelGGL(lora_grad_batch_partial_kernel<false>, dim3(nwg), dim3(256), 0, st, a, ws);
+    if (maxR <= 16) {      // ranks up to 16 only: the launch they always had
+      if (dtype == GSL_F16) hipLaunchKernelGGL((lora_grad_batch_partial_kernel<true, 1>), dim3(nwg), dim3(256), 0, st, a, ws);
+      else hipLaunchKernelGGL((lora_grad_batch_partial_kernel<false, 1>), dim3(nwg), dim3(256), 0, st, a, ws);
+    } else {
+      if (dtype == GSL_F16) hipLaunchKernelGGL((lora_grad_batch_partial_kernel<true, 4>), dim3(nwg), dim3(256), 0, st, a, ws);
+      else hipLaunchKernelGGL((lora_grad_batch_partial_kernel<false, 4>), dim3(nwg), dim3(256), 0, st, a, ws);
+    }
     hipLaunchKernelGGL(lora_grad_batch_reduce_kernel, dim3(nrb), dim3(256), 0, st, a, (const float*)ws, gscale);
     const int rc2 = check_launch("gsl_lora_grad_batch");
     if (rc2) return rc2;

@@ -17,6 +17,19 @@ def check_num_tokens(model, T):
                                   f"{ATTN_MAX_T} (GSL_ATTN_MAX_T: a 32 x 32 patch grid plus the cls token)")
 
 
+LORA_MAX_RANK = 64      # the LoRA K segment of the GEMMs is 64 columns wide (PADK in vit_runner.py)
+
+
+def check_lora_rank(model, rank, attention_site=False):
+    """Refuse, at construction, a LoRA rank the 64-column LoRA K segment of the GEMMs does not hold."""
+    if rank > LORA_MAX_RANK:
+        raise NotImplementedError(f"{model}: lora_rank {rank} exceeds {LORA_MAX_RANK}, the width of the LoRA K segment of the gs-lora_amd "
+                                  f"GEMMs (64 columns)")
+    if attention_site and 3 * rank > LORA_MAX_RANK:
+        raise NotImplementedError(f"{model}: 3 * lora_rank = {3 * rank} must not exceed {LORA_MAX_RANK} for lora_pos Attention: the q / k / v "
+                                  f"adapters share the one 64-column LoRA K segment of the QKV GEMM (lora_rank <= {LORA_MAX_RANK // 3})")
+
+
 DT = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}      # (fp16: MFMA operand format of the "fp16" mode; also the forward residual stream of both 16-bit modes)
 
 
@@ -471,9 +484,11 @@ class _LgradDesc(ctypes.Structure):      # mirrors struct gsl_lgrad_desc (includ
 
 
 def lora_grad_batchable(Y, U, r):
-    """Can this reduction ride in gsl_lora_grad_batch (16-bit MFMA form: 256-column blocks, 16-byte rows)?"""
+    """Can this reduction ride in gsl_lora_grad_batch (16-bit MFMA form: 256-column blocks, 16-byte rows)? The form reads columns 0..15
+    of U up to rank 16 and the 8-column chunks [0, 8 * ceil(r / 8)) above: a row of U must be at least that long."""
+    ucols = 16 if r <= 16 else -(-r // 8) * 8
     return (Y.dtype in (torch.bfloat16, torch.float16) and U.dtype == Y.dtype and Y.is_cuda and Y.stride(1) == 1 and U.stride(1) == 1
-            and Y.shape[1] % 256 == 0 and Y.stride(0) % 8 == 0 and U.stride(0) % 8 == 0 and U.stride(0) >= 16 and 1 <= r <= 16
+            and Y.shape[1] % 256 == 0 and Y.stride(0) % 8 == 0 and U.stride(0) % 8 == 0 and U.stride(0) >= ucols and 1 <= r <= LORA_MAX_RANK
             and Y.data_ptr() % 16 == 0 and U.data_ptr() % 16 == 0)
 
 

@@ -364,7 +364,8 @@ class ViTRunner:
         ent = self._packs.get(key)
         if ent is None or ent["ptr"] != param.data_ptr() or ent["dev"] != param.device:
             rows, cols = param.shape
-            si, sj, pr, pc, ro, ld = self.PACK_GEOM[kind](rows, cols, min(rows, cols))
+            rank = rows if kind.startswith("A") else cols      # lora_A is [r, in], lora_B is [out, r] (min(rows, cols) is wrong where r > dim)
+            si, sj, pr, pc, ro, ld = self.PACK_GEOM[kind](rows, cols, rank)
             out = torch.empty(ro, ld, device=param.device, dtype=dtype)
             ent = dict(ptr=param.data_ptr(), dev=param.device, param=param, out=out, geom=(si, sj, pr, pc), version=None)
             self._packs[key] = ent

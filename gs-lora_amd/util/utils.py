@@ -261,6 +261,8 @@ def replace_ffn_with_lora(model, rank=8):
     layers are freshly initialised — the frozen FFN weights come from the checkpoint the driver loads afterwards
     (train_own_forget_cl.py:250-262)."""
     import loralib as lora
+    from gslora_hip.ops import check_lora_rank
+    check_lora_rank(type(model).__name__, rank)      # refused here, where the adapters are attached, not in the first forward
     for _, module in list(model.named_modules()):
         if hasattr(module, "mlp"):
             ffn = module.mlp

@@ -18,7 +18,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from gslora_hip.ops import check_num_tokens
+from gslora_hip.ops import check_lora_rank, check_num_tokens
 from gslora_hip.vit_runner import BlockSpec, ModelSpec
 from .vit_face import HipModelMixin, compute_dtype_of, DEFAULT_DTYPE
 
@@ -144,6 +144,7 @@ class ModifiedViT(HipModelMixin, nn.Module):
         if rank is not None and rank > 0 and hasattr(blocks[0].l1, "merged") is False:
             raise NotImplementedError("FFN linears must be loralib.Linear (util.utils.replace_ffn_with_lora)")
         check_num_tokens("ModifiedViT", enc.pos_embedding.shape[1])
+        check_lora_rank("ModifiedViT", rank or 0)
         head = self.heads.head
         return ModelSpec(patch_size=patch, num_tokens=enc.pos_embedding.shape[1], dim=D, heads=heads, attn_scale=64 ** -0.5,
                          ln_eps=float(enc.ln.eps), dropout_p=float(layers[0].dropout.p), emb_dropout_p=float(enc.dropout.p),

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 import loralib as lora
-from gslora_hip.ops import check_num_tokens
+from gslora_hip.ops import check_lora_rank, check_num_tokens
 from gslora_hip.vit_runner import BlockSpec, ModelSpec, ViTRunner
 
 MIN_NUM_PATCHES = 16
@@ -324,6 +324,7 @@ class ViT_face(HipModelMixin, nn.Module):
         if patch_dim % 64 or dim % 64 or mlp_dim % 64:
             raise NotImplementedError("gs-lora_amd GEMM tiles need patch_dim, dim and mlp_dim to be multiples of 64")
         check_num_tokens("ViT_face", num_patches + 1)
+        check_lora_rank("ViT_face", lora_rank, attention_site=(lora_pos == "Attention"))
         self.patch_size = patch_size
         self.pos_embedding = nn.Parameter(torch.randn(1, num_patches + 1, dim))
         self.patch_to_embedding = nn.Linear(patch_dim, dim)

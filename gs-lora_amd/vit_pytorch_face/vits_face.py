@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from gslora_hip.ops import check_num_tokens, unfold_geometry
+from gslora_hip.ops import check_lora_rank, check_num_tokens, unfold_geometry
 
 from .vit_face import DEFAULT_DTYPE, MIN_NUM_PATCHES, _HEADS, HipModelMixin, Transformer, ViT_face, compute_dtype_of
 
@@ -41,6 +41,7 @@ class ViTs_face(HipModelMixin, nn.Module):
             raise ValueError(f"ViTs_face: nn.Unfold({ac_patch_size}, stride={patch_size}, padding={pad}) cuts {lh * lw} windows from a "
                              f"{image_size} px image, more than the {num_patches} rows of pos_embedding after the cls row")
         check_num_tokens("ViTs_face", lh * lw + 1)
+        check_lora_rank("ViTs_face", lora_rank)
         self.patch_size = patch_size
         self.soft_split = nn.Unfold(kernel_size=(ac_patch_size, ac_patch_size), stride=(patch_size, patch_size), padding=(pad, pad))
         self.pos_embedding = nn.Parameter(torch.randn(1, num_patches + 1, dim))

@@ -267,7 +267,13 @@ GSL_API int gsl_attention_kernel_choice(int B, int T, int H, int dtype, int qkv_
 
 /* ---- K9 LoRA gradient (skinny, reduction over M rows): G[n*gsn + j*gsj] (+)= sum_m Y[m,n] * U[m,j]
  * Y[dtype] [M,N] with row stride ldy >= N elements (a column block of a wider tensor is allowed), U[dtype] [M,ldu] (first r columns
- * used, r <= 16; columns r..15 must be readable zeros or belong to other adapters whose products are discarded).
+ * used, 1 <= r <= 64, ldu >= max(16, r), ldu % 8 == 0). Which columns of U are READ (U may itself be a column block of a wider tensor):
+ *   r <= 16: columns 0..15 — columns r..15 must be readable zeros or belong to other adapters whose products are discarded;
+ *   r > 16:  the form for 16-bit operands with 16-byte aligned U / Y and rows (N % 256 == 0, M >= 64, ldu >= 8 * ceil(r / 8)) reads
+ *            the columns [0, 8 * ceil(r / 8)); every other form reads exactly the columns [0, r). Nothing else is read, and no result
+ *            depends on a column outside [0, r). An aligned block at column offset c of a 64-wide tensor has c % 8 == 0, so
+ *            c + r <= 64 gives c + 8 * ceil(r / 8) <= 64: the block may end at the row end.
+ * The partial sums are laid out part[split][n][R] with the padded rank R in {8, 16, 32, 64}; the sums keep a fixed order (no atomics).
  * ws f32 >= gsl_lora_grad_ws_elems(). gscale (nullable): device {S, 1/S} of a loss-scaled backward (see gsl_head_bwd): the sums are
  * multiplied by 1/S before they are stored / accumulated. */
 GSL_API long gsl_lora_grad_ws_elems(int M, int N, int r);
@@ -275,7 +281,8 @@ GSL_API int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, float
                   int M, int N, int r, int dtype, int accumulate, float* ws, const float* gscale, gsl_stream_t s);
 /* The same for n reductions in two launches per 24 descriptors (the launch-bound regime: a few-shot step runs 24 of them). 16-bit operands
  * only (dtype GSL_BF16 or GSL_F16, one format per call; gscale as above), N % 256 == 0, 16-byte aligned rows; any M >= 1. `descs` is a HOST array — the launches carry the descriptors by value, so a captured
- * HIP graph keeps them. The G of one call must not overlap. ws: gsl_lora_grad_batch_ws_elems(descs, n) floats (-1: invalid descriptor). */
+ * HIP graph keeps them. The G of one call must not overlap. Entries of different ranks (1 <= r <= 64) may share a call; every entry runs
+ * the aligned 16-bit form of gsl_lora_grad (the same bits as the single call), so U, ldu and the columns read follow its rule. ws: gsl_lora_grad_batch_ws_elems(descs, n) floats (-1: invalid descriptor). */
 typedef struct gsl_lgrad_desc {
   const void* Y; long ldy; const void* U; int ldu; int M; int N; int r; int accumulate; int pad_; float* G; long gsn, gsj;
 } gsl_lgrad_desc;
