@@ -801,9 +801,222 @@ static void head_wgrad_launch_ct(const float* dlogits, const float* emb, const f
     hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 16>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
 }
 
+// The class-tiled form, C > HEAD_TILED_C: d What [C, D] = G^T . e-hat on v_mfma_f32_16x16x4_f32, the instruction and
+// the summation rule of head_logits_tiled_kernel / head_de_tiled_kernel. A workgroup owns a tile of CT = 16 NI classes and ALL D columns
+// (NW waves of 16 NJ columns each), so the row-wise epilogue of the cosine heads runs on the accumulators and the call stays one launch
+// without a workspace. It walks the batch in K tiles of BK images, ascending: every element of dW is ONE chain from 0 over ascending b
+// with zero-filled padding to the K tile's end — no split of B over waves or workgroups, no atomics; row c depends on neither C nor CT.
+// The per-class kernel read all of emb per TWO classes; this one reads it per 16 or 64, and dlogits (the large operand) exactly once:
+// workgroup i owns the columns [CT i, CT i + CT) of every dlogits row.
+//   staging  wave w loads the rows w, w + NW, ... of the K tile, a lane the float4 chunks 4 lane + 256 q of a row: the row's squared norm is
+//            a sum over the lane's chunks (q ascending) and one wave reduction, an order fixed by D alone, taken from the registers the row
+//            is staged through (emb is read once). e-hat = emb / max(||emb||, 1e-12) is what goes to LDS; the linear kind stores emb as is.
+//   G        cs * dlogits, the ArcFace label column times arc_dphi(cos_y[b]): head_de_tiled_kernel's expressions. Rows of dlogits start at
+//            any dword (C is arbitrary): scalar loads, 16 NI consecutive classes per image.
+//   loads    unconditional on clamped in-bounds addresses, zeros selected when the registers are staged (see head_logits_tiled_kernel);
+//            the next K tile's loads are issued before this tile's MFMAs.
+//   dbias    (linear) the threads of the first CT columns add the tile's G column in image order: the same ascending chain.
+//   epilogue head_wgrad_kernel's expression, a wave per class row (through the e-hat panel): ||W_c||^2 and W_c . d What_c are a lane's
+//            columns lane, lane + 64, ... in ascending order and one wave reduction, an order fixed by D alone.
+// Preconditions, checked by the caller: D % 4 == 0 and emb 16-byte aligned (the float4 loads of emb). W, dlogits and dW are scalar accesses.
+// No LDS array is sized by B or C.
+template <int KIND, int NW, int NI, int NJ>
+__global__ __launch_bounds__(NW * 64) void head_wgrad_tiled_kernel(const float* __restrict__ dlogits, const float* __restrict__ emb,
+                                                                  const float* __restrict__ W, const int64_t* __restrict__ label,
+                                                                  const float* __restrict__ cos_y, float* __restrict__ dW,
+                                                                  float* __restrict__ dbias, int B, int C, int D, float cs, ArcMargin arc) {
+  constexpr int NT = NW * 64, CT = 16 * NI, DW = NW * 16 * NJ;      // threads, classes and columns of the workgroup (DW >= D)
+  constexpr int BK = DW > 512 ? 8 : 16;                             // images per K tile (the e-hat panel stays at 33 KB)
+  constexpr int LDE = DW + 16;                                      // row stride of the [image][column] panel: 16 fc + fr covers the 64 banks once
+  constexpr int LDG = CT == 16 ? 16 : CT + 16;                      // ... and of the [image][class] panel
+  constexpr int RPW = BK / NW, NQ = (DW + 255) / 256;               // staging of e-hat: rows per wave, float4 chunks per lane and row
+  constexpr int NG = (BK * CT + NT - 1) / NT;                       // staging of G: elements per thread
+  constexpr bool GFULL = NG * NT == BK * CT;
+  constexpr int PR = DW > 512 ? 8 : 16, LDP = DW + 4, NC = DW / 64;  // epilogue: class rows per pass through the panel, their stride (16 fc + fr
+  static_assert(PR * LDP <= BK * LDE, "the epilogue reuses Es");     // over a fragment store), 64-column chunks of a row
+  __shared__ __attribute__((aligned(16))) float Es[BK * LDE];
+  __shared__ float Gs[BK * LDG];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t c0 = (size_t)blockIdx.x * CT;
+  auto lastc = [&](size_t c) { return c < (size_t)C ? c : (size_t)C - 1; };      // the class, or the last one: a clamped row
+  struct Regs {      // a K tile on its way from memory to LDS
+    float4 re[RPW][NQ];
+    float rg[NG], rcy[NG];
+    int64_t ry[NG];
+  };
+  auto fetch = [&](Regs& R, int k0) {
+    auto& re = R.re; auto& rg = R.rg; auto& rcy = R.rcy; auto& ry = R.ry;
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      const float* er = emb + (size_t)min(k0 + wave + NW * i, B - 1) * D;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) re[i][q] = *reinterpret_cast<const float4*>(er + min(4 * lane + 256 * q, D - 4));
+    }
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const int idx = tid + NT * i, b = min(k0 + min(idx / CT, BK - 1), B - 1);
+      rg[i] = dlogits[(size_t)b * C + lastc(c0 + idx % CT)];
+      if constexpr (KIND == HEAD_ARCFACE) { ry[i] = label[b]; rcy[i] = cos_y[b]; }
+    }
+  };
+  // registers -> LDS: zeros for what lies outside the tensors, the row norms, the margin's derivative
+  auto stage = [&](Regs& R, int k0) {
+    auto& re = R.re; auto& rg = R.rg; auto& rcy = R.rcy; auto& ry = R.ry;
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+      const int r = wave + NW * i;
+      const bool live = k0 + r < B;
+      float ss = 0.f;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {      // (D % 4 == 0: a float4 lies inside the row or outside it)
+        const float4 v = keep4(live && 4 * lane + 256 * q < D, re[i][q]);
+        re[i][q] = v;
+        ss += v.x * v.x; ss += v.y * v.y; ss += v.z * v.z; ss += v.w * v.w;
+      }
+      if constexpr (KIND != HEAD_LINEAR) {
+        const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) re[i][q] = make_float4(re[i][q].x * inv, re[i][q].y * inv, re[i][q].z * inv, re[i][q].w * inv);
+      }
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+        if (4 * lane + 256 * q < DW) *reinterpret_cast<float4*>(&Es[r * LDE + 4 * lane + 256 * q]) = re[i][q];
+    }
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const int idx = tid + NT * i, r = idx / CT, cl = idx % CT;
+      if (GFULL || idx < BK * CT) {
+        const size_t c = c0 + cl;
+        const bool live = k0 + r < B && c < (size_t)C;
+        float v = live ? rg[i] : 0.f;
+        if constexpr (KIND != HEAD_LINEAR) v *= cs;
+        if constexpr (KIND == HEAD_ARCFACE) { if (live && ry[i] == (int64_t)c) v *= arc_dphi(rcy[i], arc); }
+        Gs[r * LDG + cl] = v;
+      }
+    }
+  };
+  head_f32x4_t acc[NI][NJ];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = head_f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;
+  const int fr = lane & 15, fc = lane >> 4;
+  const int wcol = wave * 16 * NJ;
+  const int nk = (B + BK - 1) / BK;
+  auto tile = [&](Regs& R, int kt) {
+    stage(R, kt * BK);
+    wg_barrier_lds();
+    if (kt + 1 < nk) fetch(R, (kt + 1) * BK);      // the next tile's loads fly under this tile's MFMAs
+#pragma unroll
+    for (int ks = 0; ks < BK / 4; ++ks) {
+      float gf[NI], ef[NJ];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) gf[i] = Gs[(ks * 4 + fc) * LDG + i * 16 + fr];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) ef[j] = Es[(ks * 4 + fc) * LDE + wcol + j * 16 + fr];
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(gf[i], ef[j], acc[i][j], 0, 0, 0);
+    }
+    if constexpr (KIND == HEAD_LINEAR) {
+      if (dbias && tid < CT) {
+#pragma unroll
+        for (int k = 0; k < BK; ++k) bsum += Gs[k * LDG + tid];
+      }
+    }
+    wg_barrier_lds();      // every wave has read the panels before the next tile overwrites them
+  };
+  Regs r0;
+  fetch(r0, 0);
+  for (int kt = 0; kt < nk; ++kt) tile(r0, kt);
+  if constexpr (KIND == HEAD_LINEAR) {
+    if (dbias && tid < CT && c0 + tid < (size_t)C) dbias[c0 + tid] = bsum;
+  }
+  // Epilogue. A lane holds the classes 4 fc + r, column fr of every fragment; the rows go through the (now free) e-hat panel, PR classes at
+  // a time, so that a WAVE finishes a class row with its lanes over the columns: the row's two sums are a lane's columns (ascending) and
+  // one wave reduction, W is read once, and W loads / dW stores are whole 256-byte runs of a row. (Finishing the rows on the accumulators
+  // — 64-byte runs, two passes over W, the sums across waves through LDS — spilled 60 - 150 registers at 64 classes x 512 / 1024 columns.)
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int h = 0; h < 16 / PR; ++h) {
+      if (PR == 16 || (fc >> 1) == h) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) Es[((4 * fc + r) & (PR - 1)) * LDP + wcol + j * 16 + fr] = acc[i][j][r];
+      }
+      wg_barrier_lds();
+      for (int rr = wave; rr < PR; rr += NW) {
+        const size_t c = c0 + i * 16 + h * PR + rr;
+        if (c >= (size_t)C) break;      // (uniform over the wave; the barriers are outside this loop)
+        float f[NC], w[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+          f[q] = Es[rr * LDP + lane + 64 * q];
+          if constexpr (KIND != HEAD_LINEAR) w[q] = W[c * D + min(lane + 64 * q, D - 1)];
+        }
+        if constexpr (KIND == HEAD_LINEAR) {
+#pragma unroll
+          for (int q = 0; q < NC; ++q)
+            if (lane + 64 * q < D) dW[c * D + lane + 64 * q] = f[q];
+        } else {
+          float ss = 0.f, dot = 0.f;
+#pragma unroll
+          for (int q = 0; q < NC; ++q) {
+            w[q] = lane + 64 * q < D ? w[q] : 0.f;
+            ss += w[q] * w[q];
+            dot += w[q] * f[q];
+          }
+          const float raw = sqrtf(wave_sum(ss));
+          dot = wave_sum(dot);
+          const float nrm = fmaxf(raw, 1e-12f);
+#pragma unroll
+          for (int q = 0; q < NC; ++q)
+            if (lane + 64 * q < D) dW[c * D + lane + 64 * q] = (raw >= 1e-12f) ? (f[q] - (w[q] / nrm) * (dot / nrm)) / nrm : f[q] / nrm;
+        }
+      }
+      wg_barrier_lds();      // the panel is read before the next PR rows overwrite it
+    }
+}
+
+// Which tile (B = 1024, D = 512, CosFace, microseconds, profiles/head_large_c.md): 16 classes on 8 waves 167 / 221 / 224 / 296 / 435 at
+// C = 8192 / 10 572 / 12 288 / 16 384 / 24 576; 64 classes on 4 waves 262 up to 16 384 (at most one workgroup per CU: the time of one
+// workgroup), then 394, and 1196 at 93 431, where the 16-class tile (then still on 4 waves) took 1616: 11.7 GB of emb reads from L2.
+constexpr int HWT_WIDE_C = 16384;      // classes from which a workgroup takes 64 and not 16
+
+#define GSL_HWT(NW_, NI_, NJ_)                                                                                                          \
+  hipLaunchKernelGGL((head_wgrad_tiled_kernel<KIND, NW_, NI_, NJ_>), dim3((C - 1) / (16 * NI_) + 1), dim3(64 * NW_), 0, as_stream(s), dlogits, \
+                     emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc)
+template <int KIND>
+static void head_wgrad_tiled_launch(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y,
+                                    float* dW, float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
+  if (C >= HWT_WIDE_C) {      // 64 classes a workgroup
+    if (D <= 128) GSL_HWT(4, 4, 2);
+    else if (D <= 256) GSL_HWT(4, 4, 4);
+    else if (D <= 512) GSL_HWT(4, 4, 8);
+    else GSL_HWT(8, 4, 8);
+  } else {      // 16 classes a workgroup on 8 waves: few workgroups (65 at C = 1025), so each brings two waves per SIMD of its own to cover
+                // the LDS and barrier latencies of a K tile (4 waves: 150 us at C = 1025 and 2048; 8 waves: 107 / 109 us)
+    if (D <= 128) GSL_HWT(8, 1, 1);
+    else if (D <= 256) GSL_HWT(8, 1, 2);
+    else if (D <= 512) GSL_HWT(8, 1, 4);
+    else GSL_HWT(8, 1, 8);
+  }
+}
+#undef GSL_HWT
+
 template <int KIND>
 static void head_wgrad_launch(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
                               float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
+  // Above HEAD_TILED_C classes the class-tiled kernel, where its loads are legal: D % 4 == 0 and emb 16-byte aligned. A call that does not
+  // meet them is not refused (the entry point always took any C and any D <= 1024): it runs the per-class kernel below, as it always did.
+  if (C > HEAD_TILED_C && (D % 4) == 0 && (((uintptr_t)emb) & 15) == 0) {
+    head_wgrad_tiled_launch<KIND>(dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc, s);
+    return;
+  }
   // A workgroup per class up to 256 classes. The cosine heads need every row's norm, so a workgroup reads all of emb whatever part of
   // dW it owns: splitting the columns over more workgroups would shorten no wave's chain of rounds and multiply the L2 traffic, and
   // splitting the batch would need a second pass or float atomics. Many classes: two per workgroup, which read every row once for both.

@@ -655,7 +655,10 @@ HEAD_WGRAD_KINDS = {"cosface": 0, "arcface": 1, "linear": 2, "softmax": 2}      
 def head_wgrad(dlogits, emb, W, head_kind, cos_s=64.0, m=0.5, easy_margin=False, label=None, cos_y=None, bias=False, dW=None, dbias=None):
     """d loss / d W of the head from the upstream dlogits [B, C] (gsl_head_wgrad): emb [B, D] is the head forward's (un-normalised)
     embedding, W [C, D] the raw weight. head_kind "cosface" | "arcface" (needs the forward's label and cos_y) | "linear" / "softmax"
-    (bias=True: also d loss / d bias). Returns (dW, dbias or None): freshly allocated unless given, every element stored."""
+    (bias=True: also d loss / d bias). Returns (dW, dbias or None): freshly allocated unless given, every element stored.
+    Dispatch inside the library, on the call alone: C <= 1024 (HEAD_TILED_C) runs the per-class kernel; C > 1024 the class-tiled
+    matrix-core kernel when D % 4 == 0 and emb is 16-byte aligned (every element one chain over ascending b: the linear kind equals
+    gemm_nt(dlogits.T, emb.T) bit for bit), and the per-class kernel otherwise — never a refusal. Any C, D <= 1024."""
     kind = HEAD_WGRAD_KINDS[head_kind]
     _need(dlogits, emb, W, label, cos_y, dW, dbias)
     B, C = dlogits.shape

@@ -360,9 +360,20 @@ GSL_API int gsl_head_bwd_margin(const float* dlogits, const float* demb, const v
  *   d What_c = sum_b G[b,c] emb_b / max(||emb_b||, 1e-12);  dW_c = (d What_c - What_c (What_c . d What_c)) / ||W_c||, What_c = W_c / ||W_c||;
  *   ||W_c|| < 1e-12: dW_c = d What_c / 1e-12 (the derivative of F.normalize's clamp, as torch).
  *   linear: dW_c = sum_b dlogits[b,c] emb_b and, with dbias != NULL, dbias_c = sum_b dlogits[b,c]. dbias must be NULL for the cosine heads.
- * dW [C,D] and dbias [C] are plain stores of every element (no pre-zeroing, no accumulation). No allocation, no sync, no atomics: the sum
- * over b runs in an order fixed by (B, C, D) — per wave ascending, the 16 waves of a workgroup added in wave order — so two calls agree
- * bit for bit; capturable in a HIP graph. Any B >= 1, any C >= 1 (no buffer is sized by C), D <= 1024. */
+ * dW [C,D] and dbias [C] are plain stores of every element (no pre-zeroing, no accumulation), nothing else is written. No allocation, no
+ * sync, no atomics, no workspace; two calls agree bit for bit; capturable in a HIP graph. Any B >= 1, any C >= 1 (no buffer is sized by B or
+ * C; indices are size_t, B*C may exceed 2^31), D <= 1024.
+ * Dispatch, on the call alone:
+ *   C <= 1024  the per-class kernel (a workgroup of 16 waves per one or two classes): the sum over b runs per wave ascending, the 16 waves
+ *              added in wave order — an order fixed by (B, C, D). The bits are what they always were.
+ *   C > 1024   the class-tiled kernel, when its preconditions hold: D % 4 == 0 and emb 16-byte aligned (it loads emb as float4; dlogits,
+ *              whose rows start at any dword, W and dW need no alignment). d What = G^T e-hat on v_mfma_f32_16x16x4_f32 (exact f32), a
+ *              workgroup per 16 classes (C < 16384) or 64 classes, all D columns, ONE launch. Order of summation: every element of dW
+ *              (and dbias) is one chain from 0 over ascending b, with zero-filled padding to the end of the last tile of 16 images (8 at
+ *              D > 512) — no split of B over waves or workgroups. Row c of dW depends on neither C nor the tile c falls in; the linear
+ *              kind equals gsl_gemm_nt(dlogits^T, emb^T) in f32 bit for bit. Row norms: a wave per row, an order fixed by D.
+ *   C > 1024 and a precondition not met: the call falls back to the per-class kernel. It is never refused for its alignment or its D:
+ *              the argument checks are the same at every C. */
 GSL_API int gsl_head_wgrad(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y,
                  float* dW, float* dbias, int B, int C, int D, int head_kind, float cos_s, double m, int easy_margin,
                  gsl_stream_t s);

@@ -10,10 +10,21 @@ the last run. Not part of bench.py.
   (b) step     gs_lora_step on ViT-P8S8 (112 px, depth 6, dim 512, CosFace, LoRA r = 8, dropout 0.1, fp16) at batch 512 + 512 — bench.py's
                config 2 — with num_class = 10 572 against num_class = 100, alternating.
 
-    python tools/bench_head_large_c.py [--warmup 5] [--iters 20] [--step-iters 8] [--no-step] [--classes 1000,1024,...]
+  (c) probe    head_probe_step (head only trainable, the same model, fp16) at batch 512 with num_class = 100 and 10 572, alternating
+               (--probe-step): the step whose backward is the one gsl_head_wgrad launch.
+
+    python tools/bench_head_large_c.py [--warmup 5] [--iters 20] [--step-iters 8] [--no-step] [--probe-step] [--classes 1000,1024,...]
+    python tools/bench_head_large_c.py --wgrad-acceptance NEW1.json,NEW2.json PARENT1.json,PARENT2.json
+
+Every run also reports head_wgrad over the tiled head_bwd f32 of the same run ("wgrad_over_head_bwd_f32"): two kernels of equal FLOPs.
 
 The acceptance rule of the tiled kernels is evaluated and printed ("acceptance"): time(C) <= time_old(1024) * C / 1024 for the forward and the
 backward at C = 2048 and 10 572, and fp16 loss-scaled backward < 1.25 x the plain one at C = 10 572. Exits non-zero when it does not hold.
+
+The class-tiled weight gradient is judged against the PARENT build, not against a rule inside one library: run the tool several times on one
+box, whole runs alternating between the two libraries (GSLORA_HIP_LIB, the way tools/ab_libs.sh compares builds), keep each run's JSON line,
+and hand the files to --wgrad-acceptance (no GPU needed). With the mean of the runs' medians: head_wgrad at C = 10 572 and 93 431 takes at
+most HALF the parent's time, at C = 1025 and 2048 it is not slower, and the C <= 1024 rows are reported. Exits non-zero when it does not hold.
 """
 import argparse
 import json
@@ -86,6 +97,7 @@ def bench_kernels(args, C):
     want[torch.arange(B, device="cuda"), label] -= S * M
     res["logits_vs_torch_max_abs"] = round((want - logits).abs().max().item(), 7)
     res["path"] = "tiled" if C > ops.HEAD_TILED_C else "per-image"
+    res["wgrad_over_head_bwd_f32"] = round(res["head_wgrad"]["median_us"] / res["head_bwd_f32"]["median_us"], 3)
     return res
 
 
@@ -114,6 +126,49 @@ def bench_step(args):
     return res
 
 
+def bench_probe_step(args):
+    from gslora_hip.optim import create_optimizer
+    from gslora_hip.step import head_probe_step
+    from types import SimpleNamespace
+    from vit_pytorch_face import ViT_face
+    crit = torch.nn.CrossEntropyLoss()
+    runs = {}
+    for C in (100, 10572):
+        torch.manual_seed(1337)
+        m = ViT_face(loss_type="CosFace", GPU_ID=[0], num_class=C, dropout=0.1, emb_dropout=0.1, **GEO)
+        for n, p in m.named_parameters():      # train/backbone_forget_main.py:596-600
+            p.requires_grad = "loss" in n
+        m = m.cuda().set_compute_dtype("fp16").train()
+        opt = create_optimizer(SimpleNamespace(opt="adamw", lr=1e-3, weight_decay=0.05, opt_eps=1e-8, opt_betas=None), m)
+        x, y = torch.rand(args.batch, 3, 112, 112, device="cuda"), torch.randint(0, C, (args.batch,), device="cuda")
+        runs[f"num_class_{C}"] = (lambda m=m, opt=opt, x=x, y=y: head_probe_step(m, opt, crit, x, y))
+    t = alternate(runs, 3, args.step_iters)
+    res = {k: {"median_ms": round(statistics.median(v) / 1e3, 3), "min_ms": round(min(v) / 1e3, 3)} for k, v in t.items()}
+    res["batch"] = args.batch
+    return res
+
+
+def wgrad_acceptance(new_files, parent_files):
+    """Mean over the runs of a library of head_wgrad's median, per C; new / parent. -> (table, missed)"""
+    def load(files):
+        runs = [json.loads(open(f).read().strip().splitlines()[-1])["kernels_B1024_D512"] for f in files.split(",")]
+        return {C: statistics.mean(r[C]["head_wgrad"]["median_us"] for r in runs) for C in runs[0] if all(C in r for r in runs)}, runs
+    new, new_runs = load(new_files)
+    old, _ = load(parent_files)
+    out, missed = {}, []
+    for C in sorted(set(new) & set(old), key=int):
+        ratio = new[C] / old[C]
+        bwd = statistics.mean(r[C]["head_bwd_f32"]["median_us"] for r in new_runs)
+        out[C] = {"new_us": round(new[C], 1), "parent_us": round(old[C], 1), "new_over_parent": round(ratio, 4),
+                  "new_over_head_bwd_f32": round(new[C] / bwd, 3)}
+        bound = 0.5 if int(C) in (10572, 93431) else 1.0 if int(C) in (1025, 2048) else None
+        if bound is not None:
+            out[C]["bound"] = bound
+            if ratio > bound:
+                missed.append(f"C={C}: {ratio:.3f} > {bound}")
+    return out, missed
+
+
 def acceptance(k):
     """time(C) <= time_old(1024) * C / 1024, no margin; the loss-scaled backward below 1.25 x the plain one at 10 572 classes."""
     out = {}
@@ -137,12 +192,20 @@ def main():
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--classes", default="1000,1024,1025,2048,10572,93431")
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--probe-step", action="store_true")
+    ap.add_argument("--wgrad-acceptance", nargs=2, metavar=("NEW_JSONS", "PARENT_JSONS"))
     args = ap.parse_args()
+    if args.wgrad_acceptance:
+        table, missed = wgrad_acceptance(*args.wgrad_acceptance)
+        print(json.dumps({"head_wgrad_new_against_parent": table}))
+        sys.exit(f"acceptance missed: {', '.join(missed)}" if missed else 0)
     kernels = {str(C): bench_kernels(args, C) for C in map(int, args.classes.split(","))}
     acc = acceptance(kernels)
     out = {"kernels_B1024_D512": kernels, "acceptance": acc}
     if not args.no_step:
         out["step_config2_fp16"] = bench_step(args)
+    if args.probe_step:
+        out["probe_step_fp16"] = bench_probe_step(args)
     print(json.dumps(out))
     bad = [k for k, v in acc.items() if (v >= 1.25 if k.startswith("fp16") else v > 1.0)]
     if bad:
