@@ -10,6 +10,15 @@
 
 using namespace gsl;
 
+// The maximum of the overflow guard. fmaxf returns the operand that is not a NaN, so a NaN gradient would never reach gmax and the optimizer
+// would apply the step; here a NaN, once seen, stays (and, non-negative, its bit pattern orders above Inf's in the unsigned atomicMax).
+__device__ __forceinline__ float guard_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float wave_guard_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = guard_max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
 template <int NPL>
 struct RowIO {
   static constexpr int VEC = (NPL % 4 == 0) ? 4 : 1;
@@ -84,7 +93,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   const int wpb = blockDim.x >> 6;
   float g[NPL];
   IO::load(gamma, lane, g);
-  float am = 0.f;      // overflow guard: largest |dy| read and |dx| stored by this wave (gmax != nullptr)
+  float am = 0.f;      // overflow guard: largest |dy| read and |dx| stored by this wave, NaN once either was a NaN (gmax != nullptr)
   for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < M; row += gridDim.x * wpb) {
     float xv[NPL], gy[NPL];
     IO::load(x + (size_t)row * xs, lane, xv);
@@ -93,7 +102,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     float s1 = 0.f, s2 = 0.f;
     if (gmax) {
 #pragma unroll
-      for (int i = 0; i < NPL; ++i) am = fmaxf(am, fabsf(gy[i]));
+      for (int i = 0; i < NPL; ++i) am = guard_max(am, fabsf(gy[i]));
     }
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
@@ -113,7 +122,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     }
     if (gmax) {
 #pragma unroll
-      for (int i = 0; i < NPL; ++i) am = fmaxf(am, fabsf(gy[i]));
+      for (int i = 0; i < NPL; ++i) am = guard_max(am, fabsf(gy[i]));
     }
     IO::store(dx + (size_t)row * (cls_T ? (long)D : ios), lane, gy);
     if (dxb) {
@@ -134,7 +143,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     }
   }
   if (gmax) {      // non-negative floats order like their bit patterns; the plain read keeps the atomics to the few waves that raise the maximum
-    am = wave_max(am);
+    am = wave_guard_max(am);
     if (lane == 0 && !(am <= *gmax)) atomicMax(reinterpret_cast<unsigned int*>(gmax), __float_as_uint(am));
   }
 }
@@ -296,6 +305,7 @@ extern "C" int gsl_layernorm_fwd(const void* x, long x_row_stride, const float* 
   GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16),
                 "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)");
   GSL_CHECK_ARG((x_row_stride % 4) == 0, "row stride alignment");
+  GSL_CHECK_ARG(x_row_stride >= D, "x_row_stride below the row length D");
 #define CALL(N) ln_fwd_launch<N>(x, x_row_stride, gamma, beta, eps, y, mean, rstd, M, dtype, x_dtype, as_stream(s))
   GSL_DISPATCH_D(D, CALL)
 #undef CALL
@@ -311,6 +321,8 @@ extern "C" int gsl_layernorm_bwd(const void* dy, const void* x, long x_row_strid
   GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16),
                 "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)");
   GSL_CHECK_ARG((x_row_stride % 4) == 0, "row stride alignment");
+  GSL_CHECK_ARG(x_row_stride >= D, "x_row_stride below the row length D");
+  GSL_CHECK_ARG(io_row_stride <= 0 || io_row_stride >= D, "io_row_stride between 0 and the row length D (rows of dx would overlap)");
   GSL_CHECK_ARG(dres_cls_T >= 0 && (dres_cls_T == 0 || (dres && dres != dx)), "dres_cls_T: compact dres, out of place");
   const DropCfg drop = make_drop(p_drop, seed, site);
   const long ios = io_row_stride > 0 ? io_row_stride : D, drs = drop_row_stride > 0 ? drop_row_stride : D;
@@ -328,6 +340,7 @@ extern "C" int gsl_layernorm_fwd_lora(const void* x, long x_row_stride, const fl
   GSL_CHECK_ARG(x && gamma && beta && y && mean && rstd && P && u && M > 0, "null/size");
   GSL_CHECK_ARG(D == 512 || D == 768, "width (512 or 768)");
   GSL_CHECK_ARG((x_row_stride % 8) == 0 && (ldp % 8) == 0 && ldp >= D, "row stride alignment");
+  GSL_CHECK_ARG(x_row_stride >= D, "x_row_stride below the row length D");
   const int grid = min((M + 63) / 64, 256 * 4);
   if (D == 512)
     hipLaunchKernelGGL((ln_fwd_lora_kernel<16>), dim3(grid), dim3(256), 0, as_stream(s), (const bf16_t*)x, x_row_stride, gamma, beta, eps,

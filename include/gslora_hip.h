@@ -207,7 +207,9 @@ GSL_API int gsl_layernorm_fwd_lora(const void* x, long x_row_stride, const float
  * leaving the cls-row-only backward of the last block is exactly zero off the cls rows: no zero-filled tensor is written or read.)
  * gmax (nullable; the overflow guard of the loss-scaled fp16 backward, round 6): device f32, raised (atomic max) to the largest |value| this call
  * read in dy or stored in dx — gscale + 2 of gsl_head_bwd. Every gradient of the chain passes a LayerNorm backward; a saturated 16-bit store
- * anywhere upstream (an operand of +-65504) or in the stream shows here as gmax >= 65504. */
+ * anywhere upstream (an operand of +-65504) or in the stream shows here as gmax >= 65504. A NaN read in dy or stored in dx (a NaN in x or
+ * dres gets there) makes gmax a NaN, and stays one: the guard is then non-finite, which gsl_adamw_flat and gsl_head_bwd act on.
+ * x_row_stride >= D; io_row_stride 0 (= D) or >= D. */
 GSL_API int gsl_layernorm_bwd(const void* dy, const void* x, long x_row_stride, const float* gamma,
                       const float* mean, const float* rstd, const void* dres,
                       void* dx, long io_row_stride, void* dxb, int M, int D, int dtype, int stream_dtype, int x_dtype,
@@ -466,7 +468,10 @@ GSL_API int gsl_adamw_flat(float* p, const float* g, float* m, float* v, long n,
 GSL_API int gsl_adamw_flat_dev(float* p, const float* g, float* m, float* v, long n, const float* lr_dev, float beta1, float beta2,
                        float eps, float wd, const int64_t* step_dev, const float* guard, gsl_stream_t s);
 
-/* ---- helpers: f32 -> dtype casts for the frozen-weight caches and padded LoRA operands. */
+/* ---- helpers: f32 -> dtype casts for the frozen-weight caches and padded LoRA operands. Round to nearest even; a FINITE value beyond the
+ * largest finite value of the 16-bit type saturates to it — +-65504 in fp16 and, as measured on the MI355X (the kernels set the
+ * saturation mode bit, which the bf16 convert honours too), +-3.3895e38 (0x7f7f) in bf16, where rounding alone would give Inf —; Inf and
+ * NaN stay Inf and NaN (tests/test_hip_flat_edges.py). gsl_transpose_cast and gsl_pack_pad convert the same way. */
 GSL_API int gsl_cast(const float* in, void* out, long n, int dtype, gsl_stream_t s);
 /* out[dtype] [C,R] = in[R,C]^T */
 GSL_API int gsl_transpose_cast(const float* in, void* out, int R, int C, int dtype, gsl_stream_t s);

@@ -6,17 +6,21 @@ a sum or a 0 * x product shows in the result. Outputs: the whole buffer holds a 
 so an element the kernel leaves unwritten misses the reference), and bands_intact() finds a store outside the view. A contiguous view of
 any rank sits between two bands; a two-dimensional view can also be a column block of wider rows (leading dimension `ld`, column offset
 `col0`) with rows `row_step` apart and `pad_rows` whole rows behind the last one: then the pad columns between the view's columns and `ld`,
-the rows between two rows of the view and the rows behind it belong to the bands."""
+the rows between two rows of the view and the rows behind it belong to the bands.
+
+The default sentinel is a value a kernel can store by chance where the range of the results is wide (0x5A5A is 203.25 in fp16): an output
+can ask for one of NAN_SENTINEL instead, a NaN with a payload that no arithmetic produces (`sentinel=NAN_SENTINEL[dtype]`)."""
 import math
 
 import torch
 
 BAND = 16384            # elements in front of and behind every placement: a multiple of 64, so a view keeps its 16-byte alignment
 SENTINEL = {1: (torch.uint8, 0x5A), 2: (torch.int16, 0x5A5A), 4: (torch.int32, 0x5A5A5A5A), 8: (torch.int64, 0x5A5A5A5A5A5A5A5A)}
+NAN_SENTINEL = {torch.float16: 0x7E5A, torch.bfloat16: 0x7FDA, torch.float32: 0x7FDA5A5A}
 
 
 class Banded:
-    def __init__(self, shape, dtype, src=None, *, ld=None, col0=0, row_step=1, pad_rows=0, device="cuda"):
+    def __init__(self, shape, dtype, src=None, *, ld=None, col0=0, row_step=1, pad_rows=0, device="cuda", sentinel=None):
         shape = tuple(shape)
         if ld is None and col0 == 0 and row_step == 1 and pad_rows == 0:
             rows, cols = 1, math.prod(shape)      # contiguous, any rank
@@ -30,6 +34,8 @@ class Banded:
         self.nrow = (rows - 1) * row_step + 1 + pad_rows            # rows of length ld the placement covers
         self.buf = torch.empty(2 * BAND + self.nrow * ld, device=device, dtype=dtype)
         self.itype, self.sent = SENTINEL[self.buf.element_size()]
+        if sentinel is not None:
+            self.sent = sentinel
         self.is_input = src is not None
         first = BAND + col0
         self.view = (self.buf[first:first + cols].view(shape) if strides is None
