@@ -15,9 +15,17 @@ inline int fail(int code, const char* fmt, const char* a = "", long b = 0, long 
   snprintf(g_err, sizeof(g_err), fmt, a, b, c);
   return code;
 }
-#define GSL_CHECK_ARG(cond, msg)                                                        \
+// GSL_CHECK_ARG_AS: the same refusal from a check function that several entry points share; `who` is the name of the entry point that reports
+#define GSL_CHECK_ARG_AS(who, cond, msg)                                                \
   do {                                                                                  \
-    if (!(cond)) return gsl::fail(GSL_ERR_ARG, "%s: argument check failed: " msg " (%ld,%ld)", __func__, 0, 0); \
+    if (!(cond)) return gsl::fail(GSL_ERR_ARG, "%s: argument check failed: " msg " (%ld,%ld)", who, 0, 0); \
+  } while (0)
+#define GSL_CHECK_ARG(cond, msg) GSL_CHECK_ARG_AS(__func__, cond, msg)
+// a shared check function's refusal (or a launch error) leaves the entry point as it is
+#define GSL_TRY(call)                                                                   \
+  do {                                                                                  \
+    const int rc_ = (call);                                                             \
+    if (rc_ != GSL_OK) return rc_;                                                      \
   } while (0)
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
@@ -304,6 +312,41 @@ __device__ __forceinline__ void gelu_pair_fast(float a, float& g, float& gp) {
   const float cdf = 0.5f + copysignf(fmaf(-ph, e, 0.5f), a);
   g = a * cdf;
   gp = fmaf(a * 0.39894228040143268f, e, cdf);
+}
+
+// ------------------------------------------------------------------ host side: the dtypes of a row kernel (LayerNorm, the head)
+// A call names up to three element types: T, the operand format `dtype` (what the GEMMs read: y, dxb), S, the residual-GRADIENT stream
+// (stream_dtype: dres, dx) and X, the saved forward residual stream (x_dtype). The rule, once:
+//   S  f32, or the operand format of a 16-bit mode
+//   X  f32; fp16 in either 16-bit mode (round 4: the forward stream of the speed mode); bf16 only with bf16 operands
+// `dtype` itself is checked by the caller (each entry point has its own text for it). A forward has no S: it passes GSL_F32.
+inline int check_row_dtypes(const char* who, int dtype, int stream_dtype, int x_dtype) {
+  GSL_CHECK_ARG_AS(who, stream_dtype == GSL_F32 || (stream_dtype == dtype && dtype != GSL_F32),
+                   "stream dtype (f32, or the operand format of a 16-bit mode)");
+  GSL_CHECK_ARG_AS(who, x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16),
+                   "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)");
+  return GSL_OK;
+}
+template <typename T> struct TypeTag { using type = T; };
+// f(TypeTag<T>, TypeTag<S>, TypeTag<X>) for a triple check_row_dtypes accepted, dtype one of GSL_F32 / GSL_BF16 / GSL_F16: the eleven legal
+// rows. A caller that ignores S (stream_dtype = GSL_F32: the forwards) instantiates their six (T, X) pairs and nothing else.
+template <typename F>
+inline void dispatch_row_types(int dtype, int stream_dtype, int x_dtype, F&& f) {
+  const TypeTag<float> f32{}; const TypeTag<bf16_t> b16{}; const TypeTag<f16_t> h16{};
+  const bool s16 = stream_dtype != GSL_F32;
+  if (dtype == GSL_F16) {      // fp16 operands (round 5): the backward runs on loss-scaled gradients
+    if (x_dtype == GSL_F16) { if (s16) f(h16, h16, h16); else f(h16, f32, h16); }
+    else { if (s16) f(h16, h16, f32); else f(h16, f32, f32); }
+  } else if (dtype == GSL_BF16) {
+    if (x_dtype == GSL_F16) { if (s16) f(b16, b16, h16); else f(b16, f32, h16); }
+    else if (x_dtype == GSL_BF16) { if (s16) f(b16, b16, b16); else f(b16, f32, b16); }
+    else { if (s16) f(b16, b16, f32); else f(b16, f32, f32); }
+  } else f(f32, f32, f32);      // GSL_F32
+}
+// f(TypeTag<E>) for one tensor format on its own (the stream a head forward reads, the operands of a LoRA-gradient reduction)
+template <typename F>
+inline void dispatch_elem_type(int dtype, F&& f) {
+  if (dtype == GSL_F16) f(TypeTag<f16_t>{}); else if (dtype == GSL_BF16) f(TypeTag<bf16_t>{}); else f(TypeTag<float>{});
 }
 
 inline hipStream_t as_stream(gsl_stream_t s) { return reinterpret_cast<hipStream_t>(s); }

@@ -4,6 +4,7 @@
 //       where the reference's sqrt returns NaN at |cos| > 1 (rounding) and an infinite gradient at |cos| = 1.
 // The losses behind it are in loss.hip, the patch gathers in front of the network in patch.hip.
 #include <cmath>
+#include <type_traits>
 
 #include "gsl_common.h"
 
@@ -32,6 +33,18 @@ constexpr int HEAD_MAXD = 1024;
 // head kinds of the margin entry points, a template argument of both kernels: the margin code of a kind exists only in its own
 // instantiations. HEAD_COSFACE also covers the plain linear head (runtime flag `linear`, as in gsl_head_fwd / gsl_head_bwd).
 constexpr int HEAD_COSFACE = 0, HEAD_ARCFACE = 1;
+constexpr int HEAD_LINEAR = 2;      // head_kind of gsl_head_wgrad only: the plain classifier (no normalisation, no margin)
+template <int V> using HeadInt = std::integral_constant<int, V>;      // a tile or kind constant on its way into a template argument
+// The one place a head_kind becomes the KIND template value: f(HeadInt<KIND>). WGRAD: the caller is the weight gradient, whose kernels
+// exist for HEAD_LINEAR too (the forward and backward kernels do not: their linear head is the run-time flag).
+template <bool WGRAD = false, typename F>
+static void head_for_kind(int kind, F&& f) {
+  if (kind == HEAD_ARCFACE) return f(HeadInt<HEAD_ARCFACE>{});
+  if constexpr (WGRAD) {
+    if (kind == HEAD_LINEAR) return f(HeadInt<HEAD_LINEAR>{});
+  }
+  f(HeadInt<HEAD_COSFACE>{});
+}
 // ArcFace constants (vit_face.py:98-101), computed on the host in double and passed as float
 struct ArcMargin {
   float cos_m, sin_m, th, mm;
@@ -248,76 +261,99 @@ __global__ __launch_bounds__(256) void head_logits_tiled_kernel(const float* __r
     }
 }
 
-// the argument checks of the class-tiled path, for all four entry points (a macro: GSL_CHECK_ARG reports the caller's name)
-// `used`: the call touches the [B, C] / [C, D] tensors at all (logits / dlogits given)
-#define GSL_HEAD_TILED_CHECKS(used)                                                                                                  \
-  GSL_CHECK_ARG(!(used) || C <= HEAD_TILED_C || ((long long)B * C < (1ll << 31) && (long long)C * D < (1ll << 31)),                  \
-                "C out of range: above 1024 classes B*C and C*D must stay below 2^31 elements");                                    \
-  GSL_CHECK_ARG(!(used) || C <= HEAD_TILED_C || ((((uintptr_t)Wn) | ((uintptr_t)emb)) & 15) == 0,                                    \
-                "above 1024 classes Wn and emb must be 16-byte aligned (the tiled kernels load float4)")
-
-template <int KIND>
-static void head_fwd_launch(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
-                            const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C, float cos_s,
-                            float cos_m, const float* head_bias, int linear_head, int pool_mean, ArcMargin arc, float* cos_y, gsl_stream_t s) {
-  if (logits && C > HEAD_TILED_C) {      // class-tiled: the per-image kernel stops behind emb / mean / rstd, the logits are a GEMM of their own
-    head_fwd_launch<KIND>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, nullptr, B, D, C, cos_s, cos_m, head_bias, linear_head,
-                          pool_mean, arc, cos_y, s);
-    const int nblk = ((B + HL_BM - 1) / HL_BM) * ((C + HL_BN - 1) / HL_BN);
-    hipLaunchKernelGGL((head_logits_tiled_kernel<KIND>), dim3(nblk), dim3(256), 0, as_stream(s), (const float*)emb, Wn, label, logits, B, D, C,
-                       cos_s, cos_m, head_bias, linear_head, arc, cos_y);
-    return;
-  }
-  const int nthr = B <= 128 ? 1024 : 256;      // one workgroup per image: with few images give each one 16 waves (100 class rows in two rounds)
-  if (x_dtype == GSL_F16)
-    hipLaunchKernelGGL((head_fwd_kernel<f16_t, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const f16_t*)x, T, gamma, beta, eps, Wn, label,
-                       emb, mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean, arc, cos_y);
-  else if (x_dtype == GSL_BF16)
-    hipLaunchKernelGGL((head_fwd_kernel<bf16_t, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const bf16_t*)x, T, gamma, beta, eps, Wn, label,
-                       emb, mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean, arc, cos_y);
-  else
-    hipLaunchKernelGGL((head_fwd_kernel<float, KIND>), dim3(B), dim3(nthr), 0, as_stream(s), (const float*)x, T, gamma, beta, eps, Wn, label,
-                       emb, mean, rstd, logits, D, C, cos_s, cos_m, head_bias, linear_head, pool_mean, arc, cos_y);
-}
-
-extern "C" int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
-                            const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C,
-                            float cos_s, float cos_m, const float* head_bias, int linear_head, int pool_mean, gsl_stream_t s) {
-  GSL_CHECK_ARG(x_dtype == GSL_F32 || x_dtype == GSL_BF16 || x_dtype == GSL_F16, "x dtype");
-  GSL_CHECK_ARG(x && gamma && beta && emb && mean && rstd && B > 0 && T > 0, "null/size");
-  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");
-  GSL_CHECK_ARG(!logits || (Wn && C > 0), "Wn required for logits");
-  GSL_HEAD_TILED_CHECKS(logits != nullptr);
-  head_fwd_launch<HEAD_COSFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
-                                linear_head, pool_mean, ArcMargin{}, nullptr, s);
-  return check_launch("gsl_head_fwd");
-}
+// ------------------------------------------------------------------ host side of the forward and the backward
+// One head call as the host side passes it around: an entry point fills one by name, then checks it and launches from it.
+struct HeadCall {
+  const char* who;                                            // the entry point: the name in front of a refusal or a launch error
+  const void* x; int x_dtype, T; const float *gamma, *beta; float eps;      // the stream [B, T, D] and the head's LayerNorm
+  const float *Wn, *hbias; const int64_t* label;
+  float *emb, *mean, *rstd, *cos_y;                           // written by the forward, read by the backward (cos_y: ArcFace only)
+  float* logits;
+  const float *dlogits, *demb; void *dx, *dxb;                // backward
+  int B, D, C; float cos_s, cos_m;
+  int dtype, stream_dtype;                                    // backward: T and S of the kernels (check_row_dtypes; X is x_dtype)
+  DropCfg drop; int linear, pool_mean, compact;
+  float *gscale, *amax_ws; int target_exp;                    // loss-scaled backward (fp16 operands); amax_ws also holds d e-hat above 1024 classes
+  int kind; ArcMargin arc;
+  const float* W; float *dW, *dbias;                          // weight gradient
+  hipStream_t st;
+};
 
 // ArcFace constants of margin m (vit_face.py:98-101): math.cos / math.sin in double, as the reference computes them, then float
 static ArcMargin arc_margin(double m, int easy_margin) {
   const double pi = 3.14159265358979323846;      // math.pi
   return ArcMargin{(float)std::cos(m), (float)std::sin(m), (float)std::cos(pi - m), (float)(std::sin(pi - m) * m), easy_margin ? 1 : 0};
 }
+static void head_set_kind(HeadCall& c, int head_kind, double m, int easy_margin) {
+  c.kind = head_kind;
+  c.arc = head_kind == HEAD_ARCFACE ? arc_margin(m, easy_margin) : ArcMargin{};
+}
+
+// what the class-tiled kernels ask for; `used`: the call touches the [B, C] / [C, D] tensors at all (logits / dlogits given)
+static int head_check_tiled(const HeadCall& c, bool used) {
+  GSL_CHECK_ARG_AS(c.who, !used || c.C <= HEAD_TILED_C || ((long long)c.B * c.C < (1ll << 31) && (long long)c.C * c.D < (1ll << 31)),
+                   "C out of range: above 1024 classes B*C and C*D must stay below 2^31 elements");
+  GSL_CHECK_ARG_AS(c.who, !used || c.C <= HEAD_TILED_C || ((((uintptr_t)c.Wn) | ((uintptr_t)c.emb)) & 15) == 0,
+                   "above 1024 classes Wn and emb must be 16-byte aligned (the tiled kernels load float4)");
+  return GSL_OK;
+}
+
+static int head_fwd_check(const HeadCall& c) {
+  GSL_CHECK_ARG_AS(c.who, c.kind == HEAD_COSFACE || c.kind == HEAD_ARCFACE, "head_kind: 0 (CosFace) or 1 (ArcFace)");
+  GSL_CHECK_ARG_AS(c.who, c.x_dtype == GSL_F32 || c.x_dtype == GSL_BF16 || c.x_dtype == GSL_F16, "x dtype");
+  GSL_CHECK_ARG_AS(c.who, c.x && c.gamma && c.beta && c.emb && c.mean && c.rstd && c.B > 0 && c.T > 0, "null/size");
+  GSL_CHECK_ARG_AS(c.who, c.D > 0 && c.D <= HEAD_MAXD && (c.D % 4) == 0, "D <= 1024, D%4==0");
+  GSL_CHECK_ARG_AS(c.who, !c.logits || (c.Wn && c.C > 0), "Wn required for logits");
+  GSL_TRY(head_check_tiled(c, c.logits != nullptr));
+  GSL_CHECK_ARG_AS(c.who, c.kind != HEAD_ARCFACE || !c.linear, "ArcFace is a cosine head (linear_head = 0)");
+  GSL_CHECK_ARG_AS(c.who, c.kind != HEAD_ARCFACE || !c.logits || (c.label && c.cos_y), "ArcFace logits need label and cos_y [B]");
+  return GSL_OK;
+}
+
+static int head_fwd_launch(const HeadCall& c) {
+  // class-tiled: the per-image kernel stops behind emb / mean / rstd (no logits), the logits are a GEMM of their own
+  const bool tiled = c.logits && c.C > HEAD_TILED_C;
+  float* const own_logits = tiled ? nullptr : c.logits;
+  const int nthr = c.B <= 128 ? 1024 : 256;      // one workgroup per image: with few images give each one 16 waves (100 class rows in two rounds)
+  head_for_kind(c.kind, [&](auto kind) {
+    constexpr int KIND = decltype(kind)::value;
+    dispatch_elem_type(c.x_dtype, [&](auto x) {
+      using X = typename decltype(x)::type;
+      hipLaunchKernelGGL((head_fwd_kernel<X, KIND>), dim3(c.B), dim3(nthr), 0, c.st, (const X*)c.x, c.T, c.gamma, c.beta, c.eps, c.Wn, c.label, c.emb,
+                         c.mean, c.rstd, own_logits, c.D, c.C, c.cos_s, c.cos_m, c.hbias, c.linear, c.pool_mean, c.arc, c.cos_y);
+    });
+    if (tiled) {
+      const int nblk = ((c.B + HL_BM - 1) / HL_BM) * ((c.C + HL_BN - 1) / HL_BN);
+      hipLaunchKernelGGL((head_logits_tiled_kernel<KIND>), dim3(nblk), dim3(256), 0, c.st, (const float*)c.emb, c.Wn, c.label, c.logits, c.B, c.D, c.C,
+                         c.cos_s, c.cos_m, c.hbias, c.linear, c.arc, c.cos_y);
+    }
+  });
+  return check_launch(c.who);
+}
+
+extern "C" int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
+                            const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C,
+                            float cos_s, float cos_m, const float* head_bias, int linear_head, int pool_mean, gsl_stream_t s) {
+  HeadCall c{};      // the margin form with the CosFace kind and no cos_y
+  c.who = __func__; c.x = x; c.x_dtype = x_dtype; c.T = T; c.gamma = gamma; c.beta = beta; c.eps = eps; c.Wn = Wn; c.label = label; c.emb = emb;
+  c.mean = mean; c.rstd = rstd; c.logits = logits; c.B = B; c.D = D; c.C = C; c.cos_s = cos_s; c.cos_m = cos_m; c.hbias = head_bias;
+  c.linear = linear_head; c.pool_mean = pool_mean; c.st = as_stream(s);
+  head_set_kind(c, HEAD_COSFACE, 0.0, 0);
+  GSL_TRY(head_fwd_check(c));
+  return head_fwd_launch(c);
+}
 
 extern "C" int gsl_head_fwd_margin(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps, const float* Wn,
                                    const int64_t* label, float* emb, float* mean, float* rstd, float* logits, int B, int D, int C,
                                    float cos_s, float cos_m, const float* head_bias, int linear_head, int pool_mean, int head_kind,
                                    double m, int easy_margin, float* cos_y, gsl_stream_t s) {
-  GSL_CHECK_ARG(head_kind == HEAD_COSFACE || head_kind == HEAD_ARCFACE, "head_kind: 0 (CosFace) or 1 (ArcFace)");
-  GSL_CHECK_ARG(x_dtype == GSL_F32 || x_dtype == GSL_BF16 || x_dtype == GSL_F16, "x dtype");
-  GSL_CHECK_ARG(x && gamma && beta && emb && mean && rstd && B > 0 && T > 0, "null/size");
-  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");
-  GSL_CHECK_ARG(!logits || (Wn && C > 0), "Wn required for logits");
-  GSL_HEAD_TILED_CHECKS(logits != nullptr);
-  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !linear_head, "ArcFace is a cosine head (linear_head = 0)");
-  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !logits || (label && cos_y), "ArcFace logits need label and cos_y [B]");
-  if (head_kind == HEAD_ARCFACE)
-    head_fwd_launch<HEAD_ARCFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
-                                  linear_head, pool_mean, arc_margin(m, easy_margin), cos_y, s);
-  else
-    head_fwd_launch<HEAD_COSFACE>(x, x_dtype, T, gamma, beta, eps, Wn, label, emb, mean, rstd, logits, B, D, C, cos_s, cos_m, head_bias,
-                                  linear_head, pool_mean, ArcMargin{}, nullptr, s);
-  return check_launch("gsl_head_fwd_margin");
+  HeadCall c{};
+  c.who = __func__; c.x = x; c.x_dtype = x_dtype; c.T = T; c.gamma = gamma; c.beta = beta; c.eps = eps; c.Wn = Wn; c.label = label; c.emb = emb;
+  c.mean = mean; c.rstd = rstd; c.logits = logits; c.B = B; c.D = D; c.C = C; c.cos_s = cos_s; c.cos_m = cos_m; c.hbias = head_bias;
+  c.linear = linear_head; c.pool_mean = pool_mean; c.cos_y = cos_y; c.st = as_stream(s);
+  head_set_kind(c, head_kind, m, easy_margin);
+  GSL_TRY(head_fwd_check(c));
+  return head_fwd_launch(c);
 }
 
 // Stage 1 of the class-tiled backward: ws [B, D] = G . Wn with G[b, c] = cs * dlogits[b, c], the ArcFace label column times
@@ -562,71 +598,75 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 // tools/emu_operand_precision.py): the largest gradient operand anywhere in the backward is 1.2x the head's, so the chain peaks near 2.5e3
 // (26x below fp16's 65504; stores saturate, they never produce Inf), and the LoRA-gradient error is flat for S between 2^6 and 2^20.
 constexpr int GSL_GRAD_TARGET_EXP = 11;
-template <int KIND, bool WS = false>
-static void head_bwd_launch(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma, const float* mean,
-                            const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb, int B, int D, int C, float cos_s, int dtype,
-                            int stream_dtype, DropCfg drop, int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int texp,
-                            ArcMargin arc, const float* cos_y, const int64_t* label, gsl_stream_t s) {
-  if constexpr (!WS) {
-    if (C > HEAD_TILED_C) {      // class-tiled: d e-hat once into amax_ws [B, B + B D), then the per-image kernel without its class loop
-      float* de = amax_ws + B;
-      if (dlogits) {
-        const int nblk = ((B + HD_BM - 1) / HD_BM) * ((D + HD_BN - 1) / HD_BN);
-        hipLaunchKernelGGL((head_de_tiled_kernel<KIND>), dim3(nblk), dim3(256), 0, as_stream(s), dlogits, Wn, label, cos_y, de, B, D, C, cos_s, arc);
-      }
-      head_bwd_launch<KIND, true>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, de, dx, dxb, B, D, C, cos_s, dtype, stream_dtype, drop,
-                                  linear_head, pool_mean, compact, gscale, amax_ws, texp, arc, cos_y, label, s);
-      return;
-    }
-  }
-#define GSL_HB(T_, S_, X_)                                                                                                         \
-  do {                                                                                                                              \
-    if (gscale)                                                                                                                     \
-      hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND, WS>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma, \
-                         mean, rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, amax_ws,        \
-                         (const float*)nullptr, 0, gscale, texp, arc, cos_y, label);                                                 \
-    hipLaunchKernelGGL((head_bwd_kernel<T_, S_, X_, KIND, WS>), dim3(B), dim3(256), 0, as_stream(s), dlogits, demb, (const X_*)x, T, gamma,   \
-                       mean, rstd, emb, Wn, (S_*)dx, (T_*)dxb, D, C, cos_s, drop, linear_head, pool_mean, compact, (float*)nullptr,   \
-                       (const float*)(gscale ? amax_ws : nullptr), B, gscale, texp, arc, cos_y, label);                              \
-  } while (0)
-  if (dtype == GSL_F16 && stream_dtype == GSL_F16 && x_dtype == GSL_F16) GSL_HB(f16_t, f16_t, f16_t);
-  else if (dtype == GSL_F16 && stream_dtype == GSL_F16) GSL_HB(f16_t, f16_t, float);
-  else if (dtype == GSL_F16 && x_dtype == GSL_F16) GSL_HB(f16_t, float, f16_t);
-  else if (dtype == GSL_F16) GSL_HB(f16_t, float, float);
-  else if (dtype == GSL_BF16 && stream_dtype == GSL_BF16 && x_dtype == GSL_F16) GSL_HB(bf16_t, bf16_t, f16_t);
-  else if (dtype == GSL_BF16 && x_dtype == GSL_F16) GSL_HB(bf16_t, float, f16_t);
-  else if (dtype == GSL_BF16 && stream_dtype == GSL_BF16 && x_dtype == GSL_BF16) GSL_HB(bf16_t, bf16_t, bf16_t);
-  else if (dtype == GSL_BF16 && stream_dtype == GSL_BF16) GSL_HB(bf16_t, bf16_t, float);
-  else if (dtype == GSL_BF16 && x_dtype == GSL_BF16) GSL_HB(bf16_t, float, bf16_t);
-  else if (dtype == GSL_BF16) GSL_HB(bf16_t, float, float);
-  else GSL_HB(float, float, float);      // GSL_F32 (the callers reject any other dtype)
-#undef GSL_HB
+
+static int head_bwd_check(const HeadCall& c) {
+  GSL_CHECK_ARG_AS(c.who, c.kind == HEAD_COSFACE || c.kind == HEAD_ARCFACE, "head_kind: 0 (CosFace) or 1 (ArcFace)");
+  GSL_CHECK_ARG_AS(c.who, c.x && c.gamma && c.mean && c.rstd && c.emb && c.dx && c.B > 0 && c.T >= 1, "null/size");
+  GSL_CHECK_ARG_AS(c.who, c.D > 0 && c.D <= HEAD_MAXD && (c.D % 4) == 0, "D <= 1024, D%4==0");
+  GSL_CHECK_ARG_AS(c.who, c.C <= HEAD_TILED_C || c.amax_ws,
+                   "C > 1024 needs the workspace amax_ws [B*(D+1)] (d e-hat of the class-tiled backward), also without gscale");
+  GSL_TRY(head_check_tiled(c, c.dlogits != nullptr));
+  GSL_CHECK_ARG_AS(c.who, !c.dlogits || c.Wn, "Wn required with dlogits");
+  GSL_CHECK_ARG_AS(c.who, !(c.compact && c.pool_mean), "compact cls-row gradients need pool = 'cls'");
+  GSL_CHECK_ARG_AS(c.who, !c.gscale || c.amax_ws, "gscale (loss-scaled gradients) needs amax_ws [B]");
+  GSL_CHECK_ARG_AS(c.who, c.target_exp == 0 || (c.target_exp >= 4 && c.target_exp <= 15), "target_exp: 0 (default 11) or 4 .. 15");
+  GSL_TRY(check_row_dtypes(c.who, c.dtype, c.stream_dtype, c.x_dtype));
+  GSL_CHECK_ARG_AS(c.who, c.kind != HEAD_ARCFACE || !c.linear, "ArcFace is a cosine head (linear_head = 0)");
+  GSL_CHECK_ARG_AS(c.who, c.kind != HEAD_ARCFACE || !c.dlogits || (c.label && c.cos_y), "ArcFace dlogits need label and cos_y [B]");
+  if (c.dtype != GSL_F16 && c.dtype != GSL_BF16 && c.dtype != GSL_F32) return fail(GSL_ERR_ARG, "%s: bad dtype %ld", c.who, c.dtype);
+  return GSL_OK;
 }
 
-// the argument checks of both backward entry points (a macro: GSL_CHECK_ARG reports the caller's name)
-#define GSL_HEAD_BWD_CHECKS()                                                                                                        \
-  GSL_CHECK_ARG(x && gamma && mean && rstd && emb && dx && B > 0 && T >= 1, "null/size");                                          \
-  GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD && (D % 4) == 0, "D <= 1024, D%4==0");                                                       \
-  GSL_CHECK_ARG(C <= HEAD_TILED_C || amax_ws, "C > 1024 needs the workspace amax_ws [B*(D+1)] (d e-hat of the class-tiled backward), also without gscale"); \
-  GSL_HEAD_TILED_CHECKS(dlogits != nullptr);                                                                                         \
-  GSL_CHECK_ARG(!dlogits || Wn, "Wn required with dlogits");                                                                         \
-  GSL_CHECK_ARG(!(compact && pool_mean), "compact cls-row gradients need pool = 'cls'");                                            \
-  GSL_CHECK_ARG(!gscale || amax_ws, "gscale (loss-scaled gradients) needs amax_ws [B]");                                            \
-  GSL_CHECK_ARG(target_exp == 0 || (target_exp >= 4 && target_exp <= 15), "target_exp: 0 (default 11) or 4 .. 15");                \
-  GSL_CHECK_ARG(stream_dtype == GSL_F32 || (stream_dtype == dtype && dtype != GSL_F32), "stream dtype (f32, or the operand format of a 16-bit mode)"); \
-  GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16), \
-                "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)")
+// The per-image kernel. WS = false: `src` is Wn and the kernel runs the class loop; WS = true: `src` is d e-hat [B, D], left in the
+// workspace by head_de_tiled_kernel. Loss-scaled (gscale): two launches, the second reads what the first wrote.
+template <int KIND, bool WS>
+static void head_bwd_rows(const HeadCall& c, const float* src) {
+  const int texp = c.target_exp ? c.target_exp : GSL_GRAD_TARGET_EXP;
+  dispatch_row_types(c.dtype, c.stream_dtype, c.x_dtype, [&](auto t, auto s, auto x) {
+    using T = typename decltype(t)::type;
+    using S = typename decltype(s)::type;
+    using X = typename decltype(x)::type;
+    auto pass = [&](float* amax_out, const float* amax_in, int n_amax) {
+      hipLaunchKernelGGL((head_bwd_kernel<T, S, X, KIND, WS>), dim3(c.B), dim3(256), 0, c.st, c.dlogits, c.demb, (const X*)c.x, c.T, c.gamma, c.mean,
+                         c.rstd, c.emb, src, (S*)c.dx, (T*)c.dxb, c.D, c.C, c.cos_s, c.drop, c.linear, c.pool_mean, c.compact, amax_out, amax_in,
+                         n_amax, c.gscale, texp, c.arc, c.cos_y, c.label);
+    };
+    if (c.gscale) pass(c.amax_ws, nullptr, 0);                    // the amax pass: every image's largest |stream gradient| into amax_ws [B]
+    pass(nullptr, c.gscale ? c.amax_ws : nullptr, c.B);           // the main pass: the stores, times the power of two those maxima select
+  });
+}
+
+static int head_bwd_launch(const HeadCall& c) {
+  head_for_kind(c.kind, [&](auto kind) {
+    constexpr int KIND = decltype(kind)::value;
+    if (c.C <= HEAD_TILED_C) {
+      head_bwd_rows<KIND, false>(c, c.Wn);
+      return;
+    }
+    // class-tiled: d e-hat once into amax_ws [B, B + B D), then the per-image kernel without its class loop
+    float* de = c.amax_ws + c.B;
+    if (c.dlogits) {
+      const int nblk = ((c.B + HD_BM - 1) / HD_BM) * ((c.D + HD_BN - 1) / HD_BN);
+      hipLaunchKernelGGL((head_de_tiled_kernel<KIND>), dim3(nblk), dim3(256), 0, c.st, c.dlogits, c.Wn, c.label, (const float*)c.cos_y, de, c.B, c.D,
+                         c.C, c.cos_s, c.arc);
+    }
+    head_bwd_rows<KIND, true>(c, de);
+  });
+  return check_launch(c.who);
+}
 
 extern "C" int gsl_head_bwd(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
                             const float* mean, const float* rstd, const float* emb, const float* Wn, void* dx, void* dxb,
                             int B, int D, int C, float cos_s, int dtype, int stream_dtype, float p_drop, uint64_t seed, uint32_t site,
                             int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int target_exp, gsl_stream_t s) {
-  GSL_HEAD_BWD_CHECKS();
-  if (dtype != GSL_F16 && dtype != GSL_BF16 && dtype != GSL_F32) return fail(GSL_ERR_ARG, "gsl_head_bwd: bad dtype%s %ld", "", dtype);
-  head_bwd_launch<HEAD_COSFACE>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, Wn, dx, dxb, B, D, C, cos_s, dtype, stream_dtype,
-                                make_drop(p_drop, seed, site), linear_head, pool_mean, compact, gscale, amax_ws,
-                                target_exp ? target_exp : GSL_GRAD_TARGET_EXP, ArcMargin{}, nullptr, nullptr, s);
-  return check_launch("gsl_head_bwd");
+  HeadCall c{};      // the margin form with the CosFace kind, no cos_y and no label
+  c.who = __func__; c.dlogits = dlogits; c.demb = demb; c.x = x; c.x_dtype = x_dtype; c.T = T; c.gamma = gamma; c.mean = const_cast<float*>(mean);
+  c.rstd = const_cast<float*>(rstd); c.emb = const_cast<float*>(emb); c.Wn = Wn; c.dx = dx; c.dxb = dxb; c.B = B; c.D = D; c.C = C; c.cos_s = cos_s;
+  c.dtype = dtype; c.stream_dtype = stream_dtype; c.drop = make_drop(p_drop, seed, site); c.linear = linear_head; c.pool_mean = pool_mean;
+  c.compact = compact; c.gscale = gscale; c.amax_ws = amax_ws; c.target_exp = target_exp; c.st = as_stream(s);
+  head_set_kind(c, HEAD_COSFACE, 0.0, 0);
+  GSL_TRY(head_bwd_check(c));
+  return head_bwd_launch(c);
 }
 
 extern "C" int gsl_head_bwd_margin(const float* dlogits, const float* demb, const void* x, int x_dtype, int T, const float* gamma,
@@ -634,22 +674,16 @@ extern "C" int gsl_head_bwd_margin(const float* dlogits, const float* demb, cons
                                    int B, int D, int C, float cos_s, int dtype, int stream_dtype, float p_drop, uint64_t seed, uint32_t site,
                                    int linear_head, int pool_mean, int compact, float* gscale, float* amax_ws, int target_exp, int head_kind,
                                    double m, int easy_margin, const float* cos_y, const int64_t* label, gsl_stream_t s) {
-  GSL_CHECK_ARG(head_kind == HEAD_COSFACE || head_kind == HEAD_ARCFACE, "head_kind: 0 (CosFace) or 1 (ArcFace)");
-  GSL_HEAD_BWD_CHECKS();
-  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !linear_head, "ArcFace is a cosine head (linear_head = 0)");
-  GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || !dlogits || (label && cos_y), "ArcFace dlogits need label and cos_y [B]");
-  if (dtype != GSL_F16 && dtype != GSL_BF16 && dtype != GSL_F32) return fail(GSL_ERR_ARG, "gsl_head_bwd_margin: bad dtype%s %ld", "", dtype);
-  const int texp = target_exp ? target_exp : GSL_GRAD_TARGET_EXP;
-  const DropCfg drop = make_drop(p_drop, seed, site);
-  if (head_kind == HEAD_ARCFACE)
-    head_bwd_launch<HEAD_ARCFACE>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, Wn, dx, dxb, B, D, C, cos_s, dtype, stream_dtype, drop,
-                                  linear_head, pool_mean, compact, gscale, amax_ws, texp, arc_margin(m, easy_margin), cos_y, label, s);
-  else
-    head_bwd_launch<HEAD_COSFACE>(dlogits, demb, x, x_dtype, T, gamma, mean, rstd, emb, Wn, dx, dxb, B, D, C, cos_s, dtype, stream_dtype, drop,
-                                  linear_head, pool_mean, compact, gscale, amax_ws, texp, ArcMargin{}, nullptr, nullptr, s);
-  return check_launch("gsl_head_bwd_margin");
+  HeadCall c{};
+  c.who = __func__; c.dlogits = dlogits; c.demb = demb; c.x = x; c.x_dtype = x_dtype; c.T = T; c.gamma = gamma; c.mean = const_cast<float*>(mean);
+  c.rstd = const_cast<float*>(rstd); c.emb = const_cast<float*>(emb); c.Wn = Wn; c.dx = dx; c.dxb = dxb; c.B = B; c.D = D; c.C = C; c.cos_s = cos_s;
+  c.dtype = dtype; c.stream_dtype = stream_dtype; c.drop = make_drop(p_drop, seed, site); c.linear = linear_head; c.pool_mean = pool_mean;
+  c.compact = compact; c.gscale = gscale; c.amax_ws = amax_ws; c.target_exp = target_exp; c.cos_y = const_cast<float*>(cos_y); c.label = label;
+  c.st = as_stream(s);
+  head_set_kind(c, head_kind, m, easy_margin);
+  GSL_TRY(head_bwd_check(c));
+  return head_bwd_launch(c);
 }
-#undef GSL_HEAD_BWD_CHECKS
 
 // ------------------------------------------------------------------ K10w head weight gradient (the linear-probe step)
 // d loss / d W of the head from the upstream dlogits: what autograd gives for F.linear(F.normalize(emb), F.normalize(W)) * s with the
@@ -663,7 +697,6 @@ extern "C" int gsl_head_bwd_margin(const float* dlogits, const float* demb, cons
 // the columns lane, lane + 64, ... of the image's row, so the row norm is one wave reduction and the row is read once for the CT classes),
 // then the 16 partial sums are added in wave order through LDS. The order of every sum is fixed by (B, C, D): no atomics, bit-repeatable.
 // Nothing in LDS is sized by C; every element of dW (and dbias) is stored.
-constexpr int HEAD_LINEAR = 2;      // head_kind of gsl_head_wgrad only: the plain classifier (no normalisation, no margin)
 constexpr int HW_WAVES = 16;
 
 // KM: the columns a lane holds of one row (D <= 64 * KM), so that D = 512 pays for 8 and not for HEAD_MAXD / 64 = 16.
@@ -787,18 +820,6 @@ __global__ __launch_bounds__(1024) void head_wgrad_kernel(const float* __restric
       if (in) dW[(size_t)c * D + tid] = (raw >= 1e-12f) ? (f - (w / nrm) * (dot / nrm)) / nrm : f / nrm;
     }
   }
-}
-
-template <int KIND, int CT>
-static void head_wgrad_launch_ct(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
-                                 float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
-  const dim3 grid((C + CT - 1) / CT), block(HW_WAVES * 64);
-  if (D <= 256)
-    hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 4>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
-  else if (D <= 512)
-    hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 8>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
-  else
-    hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, 16>), grid, block, 0, as_stream(s), dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc);
 }
 
 // The class-tiled form, C > HEAD_TILED_C: d What [C, D] = G^T . e-hat on v_mfma_f32_16x16x4_f32, the instruction and
@@ -987,43 +1008,59 @@ __global__ __launch_bounds__(NW * 64) void head_wgrad_tiled_kernel(const float* 
 // workgroup), then 394, and 1196 at 93 431, where the 16-class tile (then still on 4 waves) took 1616: 11.7 GB of emb reads from L2.
 constexpr int HWT_WIDE_C = 16384;      // classes from which a workgroup takes 64 and not 16
 
-#define GSL_HWT(NW_, NI_, NJ_)                                                                                                          \
-  hipLaunchKernelGGL((head_wgrad_tiled_kernel<KIND, NW_, NI_, NJ_>), dim3((C - 1) / (16 * NI_) + 1), dim3(64 * NW_), 0, as_stream(s), dlogits, \
-                     emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc)
-template <int KIND>
-static void head_wgrad_tiled_launch(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y,
-                                    float* dW, float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
-  if (C >= HWT_WIDE_C) {      // 64 classes a workgroup
-    if (D <= 128) GSL_HWT(4, 4, 2);
-    else if (D <= 256) GSL_HWT(4, 4, 4);
-    else if (D <= 512) GSL_HWT(4, 4, 8);
-    else GSL_HWT(8, 4, 8);
-  } else {      // 16 classes a workgroup on 8 waves: few workgroups (65 at C = 1025), so each brings two waves per SIMD of its own to cover
-                // the LDS and barrier latencies of a K tile (4 waves: 150 us at C = 1025 and 2048; 8 waves: 107 / 109 us)
-    if (D <= 128) GSL_HWT(8, 1, 1);
-    else if (D <= 256) GSL_HWT(8, 1, 2);
-    else if (D <= 512) GSL_HWT(8, 1, 4);
-    else GSL_HWT(8, 1, 8);
-  }
-}
-#undef GSL_HWT
-
-template <int KIND>
-static void head_wgrad_launch(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
-                              float* dbias, int B, int C, int D, float cs, ArcMargin arc, gsl_stream_t s) {
+// The rule of gsl_head_wgrad: (C, D, alignment of emb) -> the form and its tile constants, as template arguments:
+//   tiled(NW, NI, NJ)   head_wgrad_tiled_kernel: NW waves, 16 NI classes a workgroup, 16 NJ columns a wave (NW 16 NJ >= D)
+//   per_class(CT, KM)   head_wgrad_kernel: CT classes a workgroup, KM columns a lane (64 KM >= D)
+template <typename FT, typename FC>
+static void head_wgrad_rule(int C, int D, const float* emb, FT&& tiled, FC&& per_class) {
   // Above HEAD_TILED_C classes the class-tiled kernel, where its loads are legal: D % 4 == 0 and emb 16-byte aligned. A call that does not
   // meet them is not refused (the entry point always took any C and any D <= 1024): it runs the per-class kernel below, as it always did.
   if (C > HEAD_TILED_C && (D % 4) == 0 && (((uintptr_t)emb) & 15) == 0) {
-    head_wgrad_tiled_launch<KIND>(dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc, s);
+    if (C >= HWT_WIDE_C) {      // 64 classes a workgroup
+      if (D <= 128) tiled(HeadInt<4>{}, HeadInt<4>{}, HeadInt<2>{});
+      else if (D <= 256) tiled(HeadInt<4>{}, HeadInt<4>{}, HeadInt<4>{});
+      else if (D <= 512) tiled(HeadInt<4>{}, HeadInt<4>{}, HeadInt<8>{});
+      else tiled(HeadInt<8>{}, HeadInt<4>{}, HeadInt<8>{});
+    } else {      // 16 classes a workgroup on 8 waves: few workgroups (65 at C = 1025), so each brings two waves per SIMD of its own to cover
+                  // the LDS and barrier latencies of a K tile (4 waves: 150 us at C = 1025 and 2048; 8 waves: 107 / 109 us)
+      if (D <= 128) tiled(HeadInt<8>{}, HeadInt<1>{}, HeadInt<1>{});
+      else if (D <= 256) tiled(HeadInt<8>{}, HeadInt<1>{}, HeadInt<2>{});
+      else if (D <= 512) tiled(HeadInt<8>{}, HeadInt<1>{}, HeadInt<4>{});
+      else tiled(HeadInt<8>{}, HeadInt<1>{}, HeadInt<8>{});
+    }
     return;
   }
   // A workgroup per class up to 256 classes. The cosine heads need every row's norm, so a workgroup reads all of emb whatever part of
   // dW it owns: splitting the columns over more workgroups would shorten no wave's chain of rounds and multiply the L2 traffic, and
   // splitting the batch would need a second pass or float atomics. Many classes: two per workgroup, which read every row once for both.
-  if (C <= 256)
-    head_wgrad_launch_ct<KIND, 1>(dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc, s);
-  else
-    head_wgrad_launch_ct<KIND, 2>(dlogits, emb, W, label, cos_y, dW, dbias, B, C, D, cs, arc, s);
+  if (C <= 256) {
+    if (D <= 256) per_class(HeadInt<1>{}, HeadInt<4>{});
+    else if (D <= 512) per_class(HeadInt<1>{}, HeadInt<8>{});
+    else per_class(HeadInt<1>{}, HeadInt<16>{});
+  } else {
+    if (D <= 256) per_class(HeadInt<2>{}, HeadInt<4>{});
+    else if (D <= 512) per_class(HeadInt<2>{}, HeadInt<8>{});
+    else per_class(HeadInt<2>{}, HeadInt<16>{});
+  }
+}
+
+static int head_wgrad_launch(const HeadCall& c) {
+  head_for_kind<true>(c.kind, [&](auto kind) {
+    constexpr int KIND = decltype(kind)::value;
+    head_wgrad_rule(
+        c.C, c.D, c.emb,
+        [&](auto nw, auto ni, auto nj) {
+          constexpr int NW = decltype(nw)::value, NI = decltype(ni)::value, NJ = decltype(nj)::value;
+          hipLaunchKernelGGL((head_wgrad_tiled_kernel<KIND, NW, NI, NJ>), dim3((c.C - 1) / (16 * NI) + 1), dim3(64 * NW), 0, c.st, c.dlogits,
+                             (const float*)c.emb, c.W, c.label, (const float*)c.cos_y, c.dW, c.dbias, c.B, c.C, c.D, c.cos_s, c.arc);
+        },
+        [&](auto ct, auto km) {
+          constexpr int CT = decltype(ct)::value, KM = decltype(km)::value;
+          hipLaunchKernelGGL((head_wgrad_kernel<KIND, CT, KM>), dim3((c.C + CT - 1) / CT), dim3(HW_WAVES * 64), 0, c.st, c.dlogits,
+                             (const float*)c.emb, c.W, c.label, (const float*)c.cos_y, c.dW, c.dbias, c.B, c.C, c.D, c.cos_s, c.arc);
+        });
+  });
+  return check_launch(c.who);
 }
 
 extern "C" int gsl_head_wgrad(const float* dlogits, const float* emb, const float* W, const int64_t* label, const float* cos_y, float* dW,
@@ -1034,11 +1071,9 @@ extern "C" int gsl_head_wgrad(const float* dlogits, const float* emb, const floa
   GSL_CHECK_ARG(D > 0 && D <= HEAD_MAXD, "D <= 1024");
   GSL_CHECK_ARG(head_kind != HEAD_ARCFACE || (label && cos_y), "ArcFace needs label and cos_y [B]");
   GSL_CHECK_ARG(head_kind == HEAD_LINEAR || !dbias, "dbias belongs to the linear head");
-  if (head_kind == HEAD_ARCFACE)
-    head_wgrad_launch<HEAD_ARCFACE>(dlogits, emb, W, label, cos_y, dW, nullptr, B, C, D, cos_s, arc_margin(m, easy_margin), s);
-  else if (head_kind == HEAD_LINEAR)
-    head_wgrad_launch<HEAD_LINEAR>(dlogits, emb, W, nullptr, nullptr, dW, dbias, B, C, D, 1.0f, ArcMargin{}, s);
-  else
-    head_wgrad_launch<HEAD_COSFACE>(dlogits, emb, W, nullptr, nullptr, dW, nullptr, B, C, D, cos_s, ArcMargin{}, s);
-  return check_launch("gsl_head_wgrad");
+  HeadCall c{};
+  c.who = __func__; c.dlogits = dlogits; c.emb = const_cast<float*>(emb); c.W = W; c.label = label; c.cos_y = const_cast<float*>(cos_y); c.dW = dW;
+  c.dbias = dbias; c.B = B; c.C = C; c.D = D; c.cos_s = head_kind == HEAD_LINEAR ? 1.0f : cos_s; c.st = as_stream(s);
+  head_set_kind(c, head_kind, m, easy_margin);
+  return head_wgrad_launch(c);
 }

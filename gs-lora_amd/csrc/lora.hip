@@ -5,6 +5,8 @@
 // vit_pytorch_face/vit_face.py:330,333), engine_cl.get_structure_loss (engine_cl.py:349-432),
 // util/cal_norm.get_norm_of_lora (util/cal_norm.py:4-146), torch.optim.AdamW via
 // timm.create_optimizer (train/train_own_forget_cl.py:811-813).
+#include <type_traits>
+
 #include "gsl_common.h"
 
 using namespace gsl;
@@ -333,17 +335,6 @@ __global__ __launch_bounds__(256) void lora_grad_batch_reduce_kernel(const LgbAr
   float* g = e.G + (size_t)n * e.gsn + (size_t)j * e.gsj;
   *g = e.acc ? (*g + s) : s;
 }
-static inline void lgm_plan(int M, int N, int& bx, int& nsplit, int& rps) {
-  bx = N / LGM_CN;
-  int target = 1024 / bx;                       // ~4 blocks per CU in total
-  if (target < 1) target = 1;
-  int steps = (M + LGM_K - 1) / LGM_K;          // 32-row slabs
-  nsplit = steps < target ? steps : target;
-  if (steps <= 64 && nsplit > LG_FAN) nsplit = LG_FAN;      // few rows (launch-bound regime): one slab of partials, no first reduction level
-  rps = ((steps + nsplit - 1) / nsplit) * LGM_K;
-  nsplit = (M + rps - 1) / rps;
-}
-static inline bool lgm_usable(int M, int N, int ldu, int dtype) { return dtype != GSL_F32 && (N % LGM_CN) == 0 && ldu >= 16 && M >= 64; }
 // padded rank of the partial layout part[split][n][R]
 static inline int lg_padded_rank(int r) { return r <= 8 ? 8 : (r <= 16 ? 16 : (r <= 32 ? 32 : 64)); }
 // columns of U the 16-byte-aligned MFMA form reads: 0..15 up to rank 16 (the contract it always had), whole 8-column chunks above
@@ -401,42 +392,121 @@ __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __re
   }
 }
 
-static inline void lg_reduce2(hipStream_t st, const float* part2, float* G, long gsn, long gsj, int N, int r, int R, int nslab, int accumulate,
-                              const float* gscale) {
-#define GSL_LGR2(RR) hipLaunchKernelGGL(lora_grad_reduce2_kernel<RR>, dim3((N * RR + 255) / 256), dim3(256), 0, st, part2, G, gsn, gsj, N, r, nslab, accumulate, gscale)
-  if (R == 8) GSL_LGR2(8); else if (R == 16) GSL_LGR2(16); else if (R == 32) GSL_LGR2(32); else GSL_LGR2(64);
-#undef GSL_LGR2
+// ------------------------------------------------------------------ host side of gsl_lora_grad
+// One reduction as the host side passes it around (gsl_lora_grad fills it by name after its argument checks).
+struct LgCall {
+  const void *Y, *U; float* G; long ldy, gsn, gsj; int ldu, M, N, r, dtype, accumulate;
+  float* ws; const float* gscale; hipStream_t st;
+};
+enum LgForm { LG_MFMA, LG_VALU };      // the partial kernel: lora_grad_mfma_kernel / lora_grad_partial_kernel
+// How a call runs and what it needs: the launches read it, gsl_lora_grad_ws_elems sizes the workspace from it.
+struct LgPlan {
+  LgForm form;
+  int R;                  // padded rank of the partial layout part[split][n][R]
+  int bx, nsplit, rps;    // grid of the partial kernel (column blocks x row splits), rows per split
+  int CG; size_t lds;     // VALU form: column groups of a workgroup, dynamic LDS bytes of its phase combine
+  bool one_launch;        // the reduce: lora_grad_reduce_kernel over all splits, or the two levels below
+  int nslab; long part2;  // two levels: slabs the second level sums and their offset in ws; part2 == 0: the splits themselves, no first level
+  long ws_elems;          // the partials and one first-level slab per LG_FAN splits, whether or not this reduce form writes them: what callers
+                          // have always been told to allocate
+};
+static LgPlan lg_plan(LgForm form, int M, int N, int r, int V) {
+  LgPlan p{};
+  p.form = form;
+  p.R = lg_padded_rank(r);
+  if (form == LG_MFMA) {
+    p.bx = N / LGM_CN;
+    const int target = max(1, 1024 / p.bx);           // ~4 blocks per CU in total
+    const int steps = (M + LGM_K - 1) / LGM_K;        // 32-row slabs
+    p.nsplit = min(steps, target);
+    if (steps <= 64 && p.nsplit > LG_FAN) p.nsplit = LG_FAN;      // few rows (launch-bound regime): one slab of partials, no first reduction level
+    p.rps = ((steps + p.nsplit - 1) / p.nsplit) * LGM_K;
+  } else {
+    const int RK = min(p.R, 16), ncol = N / V;        // accumulator columns of the kernel: above rank 16 it runs R / 16 chunks of 16
+    p.CG = ncol >= 256 ? 256 : ((ncol > 64 || RK > 8) ? 128 : 64);   // keeps the phase-combine LDS <= 48 KB
+    p.bx = (ncol + p.CG - 1) / p.CG;
+    const int target = max(1, 768 / p.bx);            // ~3 blocks per CU in total
+    p.nsplit = max(1, min((M + 127) / 128, target));  // at least 128 rows per split
+    p.rps = (M + p.nsplit - 1) / p.nsplit;
+    p.lds = (size_t)(256 / p.CG - 1) * p.CG * V * RK * sizeof(float);
+  }
+  p.nsplit = (M + p.rps - 1) / p.rps;
+  const int tot = N * p.R, nlevel1 = (p.nsplit + LG_FAN - 1) / LG_FAN;
+  // few splits, many outputs: one launch (measured 166 -> 162 us at N = 2048; at N = 512 the two-level form wins)
+  p.one_launch = form == LG_MFMA && p.nsplit <= 160 && tot >= 8192;
+  // one slab: the second level sums the splits itself, in the same order (one launch less)
+  p.nslab = nlevel1 == 1 ? p.nsplit : nlevel1;
+  p.part2 = nlevel1 == 1 ? 0 : (long)p.nsplit * tot;
+  p.ws_elems = ((long)p.nsplit + nlevel1) * N * p.R;
+  return p;
 }
 
-static inline void lg_plan(int M, int N, int V, int R, int& CG, int& bx, int& nsplit, int& rps) {
-  const int ncol = N / V;
-  CG = ncol >= 256 ? 256 : ((ncol > 64 || R > 8) ? 128 : 64);   // keeps the phase-combine LDS <= 48 KB
-  bx = (ncol + CG - 1) / CG;
-  int target = 768 / bx;                    // ~3 blocks per CU in total
-  if (target < 1) target = 1;
-  nsplit = (M + 127) / 128;                 // at least 128 rows per split
-  if (nsplit > target) nsplit = target;
-  if (nsplit < 1) nsplit = 1;
-  rps = (M + nsplit - 1) / nsplit;
-  nsplit = (M + rps - 1) / rps;
+// The development knob of this host part (development library only): GSL_LORA_GRAD_MFMA=0 forces the VALU kernel.
+static bool lg_mfma_wanted() {
+#ifdef GSL_DEV
+  const char* ev = getenv("GSL_LORA_GRAD_MFMA");
+  return !ev || atoi(ev) != 0;
+#else
+  return true;
+#endif
+}
+// The matrix-core form where its loads are legal: 16-bit operands, whole 256-column blocks, 16-byte aligned rows of Y and U, U as wide as
+// the form reads it; from 64 rows.
+static LgForm lg_form(const LgCall& c) {
+  const bool legal = c.dtype != GSL_F32 && (c.N % LGM_CN) == 0 && c.ldu >= 16 && c.M >= 64 && c.ldu >= lgm_u_cols(c.r) &&
+                     (reinterpret_cast<uintptr_t>(c.U) % 16) == 0 && (reinterpret_cast<uintptr_t>(c.Y) % 16) == 0 &&
+                     ((size_t)c.ldu * 2) % 16 == 0 && ((size_t)c.ldy * 2) % 16 == 0;
+  return lg_mfma_wanted() && legal ? LG_MFMA : LG_VALU;
 }
 
+template <int V> using LgInt = std::integral_constant<int, V>;
+// The padded-rank ladder, for all four kernel families: f(LgInt<R>), R = lg_padded_rank(r).
+template <typename F>
+static void lg_for_rank(int R, F&& f) {
+  if (R == 8) f(LgInt<8>{}); else if (R == 16) f(LgInt<16>{}); else if (R == 32) f(LgInt<32>{}); else f(LgInt<64>{});
+}
+
+static int lg_launch(const LgCall& c, const LgPlan& p) {
+  lg_for_rank(p.R, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    if (p.form == LG_MFMA) {
+      auto partial = [&](auto f16) {
+        hipLaunchKernelGGL((lora_grad_mfma_kernel<R, decltype(f16)::value>), dim3(p.bx, p.nsplit), dim3(256), 0, c.st, (const bf16_t*)c.Y, c.ldy,
+                           (const bf16_t*)c.U, c.ldu, c.ws, c.M, c.N, p.rps, c.r);
+      };
+      if (c.dtype == GSL_F16) partial(std::true_type{}); else partial(std::false_type{});
+    } else {
+      dispatch_elem_type(c.dtype, [&](auto t) {      // above rank 16: R / 16 chunks of 16 accumulator columns
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((lora_grad_partial_kernel<T, (R > 16 ? 16 : R), (R > 16 ? R / 16 : 1)>), dim3(p.bx, p.nsplit), dim3(256), p.lds, c.st,
+                           (const T*)c.Y, c.ldy, (const T*)c.U, c.ldu, c.ws, c.M, c.N, p.rps, p.CG, c.r);
+      });
+    }
+  });
+  GSL_TRY(check_launch(p.form == LG_MFMA ? "gsl_lora_grad(mfma partial)" : "gsl_lora_grad(partial)"));
+  const int tot = c.N * p.R;
+  lg_for_rank(p.R, [&](auto rank) {
+    constexpr int R = decltype(rank)::value;
+    if (p.one_launch) {
+      hipLaunchKernelGGL(lora_grad_reduce_kernel<R>, dim3((tot + 63) / 64), dim3(256), 0, c.st, c.ws, c.G, c.gsn, c.gsj, c.N, c.r, p.nsplit,
+                         c.accumulate, c.gscale);
+      return;
+    }
+    if (p.part2) hipLaunchKernelGGL(lora_grad_reduce1_kernel, dim3((tot + 255) / 256, p.nslab), dim3(256), 0, c.st, c.ws, c.ws + p.part2, tot, p.nsplit);
+    hipLaunchKernelGGL(lora_grad_reduce2_kernel<R>, dim3((tot + 255) / 256), dim3(256), 0, c.st, c.ws + p.part2, c.G, c.gsn, c.gsj, c.N, c.r, p.nslab,
+                       c.accumulate, c.gscale);
+  });
+  return check_launch("gsl_lora_grad(reduce)");
+}
+
+// vector width of the VALU form's 16-byte loads
+static inline int lg_vec(int dtype) { return dtype != GSL_F32 ? 8 : 4; }
+
+// The largest workspace a call with this (M, N, r) can need: either vector width, and the matrix-core form where N allows it.
 extern "C" long gsl_lora_grad_ws_elems(int M, int N, int r) {
-  const int R = lg_padded_rank(r);
-  long best = 0;
-  for (int V = 4; V <= 8; V += 4) {
-    int CG, bx, nsplit, rps;
-    lg_plan(M, N, V, R > 16 ? 16 : R, CG, bx, nsplit, rps);
-    const long slabs = (long)nsplit + (nsplit + LG_FAN - 1) / LG_FAN;
-    if (slabs > best) best = slabs;
-  }
-  if ((N % LGM_CN) == 0) {
-    int bx, nsplit, rps;
-    lgm_plan(M, N, bx, nsplit, rps);
-    const long slabs = (long)nsplit + (nsplit + LG_FAN - 1) / LG_FAN;
-    if (slabs > best) best = slabs;
-  }
-  return best * (long)N * R;
+  long best = max(lg_plan(LG_VALU, M, N, r, 4).ws_elems, lg_plan(LG_VALU, M, N, r, 8).ws_elems);
+  if ((N % LGM_CN) == 0) best = max(best, lg_plan(LG_MFMA, M, N, r, 8).ws_elems);
+  return best;
 }
 
 extern "C" int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, float* G, long gsn, long gsj, int M, int N, int r,
@@ -444,64 +514,11 @@ extern "C" int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, fl
   GSL_CHECK_ARG(Y && U && G && ws && M > 0 && N > 0 && ldy >= N, "null/size");
   GSL_CHECK_ARG(r >= 1 && r <= 64 && ldu >= 16 && ldu >= r && (ldu % 8) == 0, "r in [1,64], ldu >= max(16, r) (zero-padded), ldu % 8 == 0");
   GSL_CHECK_ARG(dtype == GSL_F32 || dtype == GSL_BF16 || dtype == GSL_F16, "dtype");
-  const int V = (dtype != GSL_F32) ? 8 : 4;
-  GSL_CHECK_ARG((N % V) == 0, "N must be a multiple of the vector width");
-  hipStream_t st = as_stream(s);
-  const int R = lg_padded_rank(r);
-  int CG, bx, nsplit, rps;
-  {
-#ifdef GSL_DEV
-    const char* ev = getenv("GSL_LORA_GRAD_MFMA");      // development knob (dev library only): 0 forces the VALU kernel
-    const bool want = !ev || atoi(ev) != 0;
-#else
-    const bool want = true;
-#endif
-    if (want && lgm_usable(M, N, ldu, dtype) && ldu >= lgm_u_cols(r) && (reinterpret_cast<uintptr_t>(U) % 16) == 0 && (reinterpret_cast<uintptr_t>(Y) % 16) == 0 &&
-        ((size_t)ldu * 2) % 16 == 0 && ((size_t)ldy * 2) % 16 == 0) {
-      lgm_plan(M, N, bx, nsplit, rps);
-#define GSL_LGM(RR, FF) hipLaunchKernelGGL((lora_grad_mfma_kernel<RR, FF>), dim3(bx, nsplit), dim3(256), 0, st, (const bf16_t*)Y, ldy, (const bf16_t*)U, ldu, ws, M, N, rps, r)
-      if (dtype == GSL_F16) { if (R == 8) GSL_LGM(8, true); else if (R == 16) GSL_LGM(16, true); else if (R == 32) GSL_LGM(32, true); else GSL_LGM(64, true); }
-      else { if (R == 8) GSL_LGM(8, false); else if (R == 16) GSL_LGM(16, false); else if (R == 32) GSL_LGM(32, false); else GSL_LGM(64, false); }
-#undef GSL_LGM
-      int rc0 = check_launch("gsl_lora_grad(mfma partial)");
-      if (rc0) return rc0;
-      const int totm = N * R;
-      if (nsplit <= 160 && totm >= 8192) {     // few splits, many outputs: one launch (measured 166 -> 162 us at N = 2048; at N = 512 the two-level form wins)
-#define GSL_LGR(RR) hipLaunchKernelGGL(lora_grad_reduce_kernel<RR>, dim3((totm + 63) / 64), dim3(256), 0, st, ws, G, gsn, gsj, N, r, nsplit, accumulate, gscale)
-        if (R == 8) GSL_LGR(8); else if (R == 16) GSL_LGR(16); else if (R == 32) GSL_LGR(32); else GSL_LGR(64);
-#undef GSL_LGR
-        return check_launch("gsl_lora_grad(reduce)");
-      }
-      float* part2m = ws + (size_t)nsplit * N * R;
-      int nslabm = (nsplit + LG_FAN - 1) / LG_FAN;
-      if (nslabm == 1) { part2m = ws; nslabm = nsplit; }      // one slab: the second level sums the splits itself, in the same order (one launch less)
-      else hipLaunchKernelGGL(lora_grad_reduce1_kernel, dim3((totm + 255) / 256, nslabm), dim3(256), 0, st, ws, part2m, totm, nsplit);
-      lg_reduce2(st, part2m, G, gsn, gsj, N, r, R, nslabm, accumulate, gscale);
-      return check_launch("gsl_lora_grad(reduce)");
-    }
-  }
-  const int RK = R > 16 ? 16 : R;      // accumulator columns of the kernel: above rank 16 it runs R / 16 chunks of 16
-  lg_plan(M, N, V, RK, CG, bx, nsplit, rps);
-  const int RP = 256 / CG;
-  const size_t red_bytes = (size_t)(RP - 1) * CG * V * RK * sizeof(float);
-  float* part2 = ws + (size_t)nsplit * N * R;
-#define LAUNCH(TT, RR, NC)                                                                                                   \
-  hipLaunchKernelGGL((lora_grad_partial_kernel<TT, RR, NC>), dim3(bx, nsplit), dim3(256), red_bytes, st, (const TT*)Y, ldy, (const TT*)U, \
-                     ldu, ws, M, N, rps, CG, r)
-#define LAUNCH_R(TT) do { if (R == 8) LAUNCH(TT, 8, 1); else if (R == 16) LAUNCH(TT, 16, 1); else if (R == 32) LAUNCH(TT, 16, 2); else LAUNCH(TT, 16, 4); } while (0)
-  if (dtype == GSL_BF16) LAUNCH_R(bf16_t);
-  else if (dtype == GSL_F16) LAUNCH_R(f16_t);
-  else LAUNCH_R(float);
-#undef LAUNCH_R
-#undef LAUNCH
-  int rc = check_launch("gsl_lora_grad(partial)");
-  if (rc) return rc;
-  const int tot = N * R;
-  int nslab = (nsplit + LG_FAN - 1) / LG_FAN;
-  if (nslab == 1) { part2 = ws; nslab = nsplit; }
-  else hipLaunchKernelGGL(lora_grad_reduce1_kernel, dim3((tot + 255) / 256, nslab), dim3(256), 0, st, ws, part2, tot, nsplit);
-  lg_reduce2(st, part2, G, gsn, gsj, N, r, R, nslab, accumulate, gscale);
-  return check_launch("gsl_lora_grad(reduce)");
+  GSL_CHECK_ARG((N % lg_vec(dtype)) == 0, "N must be a multiple of the vector width");
+  LgCall c{};
+  c.Y = Y; c.ldy = ldy; c.U = U; c.ldu = ldu; c.G = G; c.gsn = gsn; c.gsj = gsj; c.M = M; c.N = N; c.r = r; c.dtype = dtype;
+  c.accumulate = accumulate; c.ws = ws; c.gscale = gscale; c.st = as_stream(s);
+  return lg_launch(c, lg_plan(lg_form(c), M, N, r, lg_vec(dtype)));
 }
 
 // =====================================================================================

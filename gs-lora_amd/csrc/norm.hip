@@ -6,6 +6,8 @@
 // centred variance are wavefront reductions (two-pass, as torch does), 16-byte loads when the
 // per-lane count is a multiple of 4. Backward fuses the residual-gradient add and emits the
 // operand-dtype copy (with the consumer's dropout mask applied) that the next dX GEMM reads.
+#include <type_traits>
+
 #include "gsl_common.h"
 
 using namespace gsl;
@@ -148,45 +150,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   }
 }
 
-template <int NPL>
-static int ln_fwd_launch(const void* x, long xs, const float* gamma, const float* beta, float eps, void* y, float* mean,
-                         float* rstd, int M, int dtype, int xdtype, hipStream_t st) {
-  const int grid = min((M + 3) / 4, 256 * 8);
-#define GSL_LNF(T, X)                                                                                                              \
-  hipLaunchKernelGGL((ln_fwd_kernel<NPL, T, X>), dim3(grid), dim3(256), 0, st, (const X*)x, xs, gamma, beta, eps, (T*)y, mean, rstd, M)
-  if (dtype == GSL_F16 && xdtype == GSL_F16) GSL_LNF(f16_t, f16_t);      // fp16 operands (round 5): y is an fp16 MFMA operand
-  else if (dtype == GSL_F16) GSL_LNF(f16_t, float);
-  else if (dtype == GSL_BF16 && xdtype == GSL_F16) GSL_LNF(bf16_t, f16_t);
-  else if (dtype == GSL_BF16 && xdtype == GSL_BF16) GSL_LNF(bf16_t, bf16_t);
-  else if (dtype == GSL_BF16) GSL_LNF(bf16_t, float);
-  else GSL_LNF(float, float);
-#undef GSL_LNF
-  return check_launch("gsl_layernorm_fwd");
-}
-
-template <int NPL>
-static int ln_bwd_launch(const void* dy, const void* x, long xs, const float* gamma, const float* mean, const float* rstd,
-                         const void* dres, void* dx, long ios, void* dxb, int M, int dtype, int sdtype, int xdtype, DropCfg drop, long drs,
-                         int cls_T, float* gmax, hipStream_t st) {
-  const int grid = min((M + 3) / 4, 256 * 8);
-#define GSL_LNB(T, S, X)                                                                                                            \
-  hipLaunchKernelGGL((ln_bwd_kernel<NPL, T, S, X>), dim3(grid), dim3(256), 0, st, (const T*)dy, (const X*)x, xs, gamma, mean, rstd, \
-                     (const S*)dres, (S*)dx, ios, (T*)dxb, M, drop, drs, cls_T, gmax)
-  if (dtype == GSL_F16 && sdtype == GSL_F16 && xdtype == GSL_F16) GSL_LNB(f16_t, f16_t, f16_t);      // fp16 operands: loss-scaled gradients
-  else if (dtype == GSL_F16 && sdtype == GSL_F16) GSL_LNB(f16_t, f16_t, float);
-  else if (dtype == GSL_F16 && xdtype == GSL_F16) GSL_LNB(f16_t, float, f16_t);
-  else if (dtype == GSL_F16) GSL_LNB(f16_t, float, float);
-  else if (dtype == GSL_BF16 && sdtype == GSL_BF16 && xdtype == GSL_F16) GSL_LNB(bf16_t, bf16_t, f16_t);
-  else if (dtype == GSL_BF16 && xdtype == GSL_F16) GSL_LNB(bf16_t, float, f16_t);
-  else if (dtype == GSL_BF16 && sdtype == GSL_BF16 && xdtype == GSL_BF16) GSL_LNB(bf16_t, bf16_t, bf16_t);
-  else if (dtype == GSL_BF16 && sdtype == GSL_BF16) GSL_LNB(bf16_t, bf16_t, float);
-  else if (dtype == GSL_BF16 && xdtype == GSL_BF16) GSL_LNB(bf16_t, float, bf16_t);
-  else if (dtype == GSL_BF16) GSL_LNB(bf16_t, float, float);
-  else GSL_LNB(float, float, float);
-#undef GSL_LNB
-  return check_launch("gsl_layernorm_bwd");
-}
-
 // =====================================================================================
 // LayerNorm forward + LoRA down-projection in one pass (bf16 mode): xn = LN(x) and u = alpha * xn P^T for the rank-r adapter that reads
 // xn (FFN1's lora_A: the second K segment [xn | u] of the fused FFN1 GEMM, vit_face.py:330 + loralib Linear.forward). The separate
@@ -287,28 +250,91 @@ __global__ __launch_bounds__(256, (KS <= 16 ? 4 : 3)) void ln_fwd_lora_kernel(co
   }
 }
 
-#define GSL_DISPATCH_D(D, CALL)                                                             \
-  switch (D) {                                                                              \
-    case 64: return CALL(1);                                                                \
-    case 128: return CALL(2);                                                               \
-    case 256: return CALL(4);                                                               \
-    case 512: return CALL(8);                                                               \
-    case 768: return CALL(12);                                                              \
-    case 1024: return CALL(16);                                                             \
-    default: return fail(GSL_ERR_UNSUPPORTED, "%s: unsupported LayerNorm width %ld", __func__, (long)(D)); \
+// ------------------------------------------------------------------ host side
+// One LayerNorm call as the host side passes it around: each entry point fills one, by name, after its argument checks.
+struct LnCall {
+  const char* who;                                          // the entry point: the name in front of a refusal or a launch error
+  const void* x; long xs; const float *gamma, *beta; float eps; int M, D;
+  float *mean, *rstd;                                       // written by the forwards, read by the backward
+  int dtype, stream_dtype, x_dtype;                         // T, S, X of the kernels (check_row_dtypes)
+  void* y;                                                  // forwards: LN(x) as an operand (nullptr: statistics only)
+  const void *dy, *dres; void *dx, *dxb; long ios;          // backward: ios = row stride of dres / dx
+  DropCfg drop; long drs; int cls_T; float* gmax;
+  const void* P; int ldp; float alpha; void* u;             // the LoRA forward
+  hipStream_t st;
+};
+
+// the rows of x, for all three entry points: `aligned` is the caller's vector width (4 elements; 8, and P's rows too, in the LoRA form)
+static int ln_check_rows(const char* who, bool aligned, long x_row_stride, int D) {
+  GSL_CHECK_ARG_AS(who, aligned, "row stride alignment");
+  GSL_CHECK_ARG_AS(who, x_row_stride >= D, "x_row_stride below the row length D");
+  return GSL_OK;
+}
+
+// The widths the row-in-registers kernels exist for: f(NPL as an integral_constant), D = 64 * NPL.
+template <typename F>
+static int ln_for_width(const char* who, int D, F&& f) {
+  switch (D) {
+    case 64: return f(std::integral_constant<int, 1>{});
+    case 128: return f(std::integral_constant<int, 2>{});
+    case 256: return f(std::integral_constant<int, 4>{});
+    case 512: return f(std::integral_constant<int, 8>{});
+    case 768: return f(std::integral_constant<int, 12>{});
+    case 1024: return f(std::integral_constant<int, 16>{});
+    default: return fail(GSL_ERR_UNSUPPORTED, "%s: unsupported LayerNorm width %ld", who, (long)D);
   }
+}
+
+static int ln_fwd_launch(const LnCall& c) {
+  const int grid = min((c.M + 3) / 4, 256 * 8);
+  return ln_for_width(c.who, c.D, [&](auto npl) {
+    // a forward has no gradient stream: with S ignored the eleven rows of dispatch_row_types are six (T, X) pairs, exactly the six
+    // forward kernels there always were per width, so no kernel is instantiated that the ladder does not name
+    dispatch_row_types(c.dtype, GSL_F32, c.x_dtype, [&](auto t, auto, auto x) {
+      using T = typename decltype(t)::type;
+      using X = typename decltype(x)::type;
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(npl)::value, T, X>), dim3(grid), dim3(256), 0, c.st, (const X*)c.x, c.xs, c.gamma, c.beta, c.eps,
+                         (T*)c.y, c.mean, c.rstd, c.M);
+    });
+    return check_launch(c.who);
+  });
+}
+
+static int ln_bwd_launch(const LnCall& c) {
+  const int grid = min((c.M + 3) / 4, 256 * 8);
+  return ln_for_width(c.who, c.D, [&](auto npl) {
+    dispatch_row_types(c.dtype, c.stream_dtype, c.x_dtype, [&](auto t, auto s, auto x) {
+      using T = typename decltype(t)::type;
+      using S = typename decltype(s)::type;
+      using X = typename decltype(x)::type;
+      hipLaunchKernelGGL((ln_bwd_kernel<decltype(npl)::value, T, S, X>), dim3(grid), dim3(256), 0, c.st, (const T*)c.dy, (const X*)c.x, c.xs, c.gamma,
+                         c.mean, c.rstd, (const S*)c.dres, (S*)c.dx, c.ios, (T*)c.dxb, c.M, c.drop, c.drs, c.cls_T, c.gmax);
+    });
+    return check_launch(c.who);
+  });
+}
+
+static int ln_fwd_lora_launch(const LnCall& c) {
+  const int grid = min((c.M + 63) / 64, 256 * 4);
+  auto launch = [&](auto ks) {      // KS = D / 32 k-steps
+    hipLaunchKernelGGL((ln_fwd_lora_kernel<decltype(ks)::value>), dim3(grid), dim3(256), 0, c.st, (const bf16_t*)c.x, c.xs, c.gamma, c.beta, c.eps,
+                       (bf16_t*)c.y, c.mean, c.rstd, c.M, (const bf16_t*)c.P, c.ldp, c.alpha, (bf16_t*)c.u);
+  };
+  if (c.D == 512) launch(std::integral_constant<int, 16>{});
+  else launch(std::integral_constant<int, 24>{});
+  return check_launch(c.who);
+}
 
 extern "C" int gsl_layernorm_fwd(const void* x, long x_row_stride, const float* gamma, const float* beta, float eps,
                                  void* y, float* mean, float* rstd, int M, int D, int dtype, int x_dtype, gsl_stream_t s) {
   GSL_CHECK_ARG(x && gamma && beta && mean && rstd && M > 0, "null/size");      // y == nullptr: statistics only
   GSL_CHECK_ARG(dtype == GSL_F32 || dtype == GSL_BF16 || dtype == GSL_F16, "dtype");
-  GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16),
-                "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)");
-  GSL_CHECK_ARG((x_row_stride % 4) == 0, "row stride alignment");
-  GSL_CHECK_ARG(x_row_stride >= D, "x_row_stride below the row length D");
-#define CALL(N) ln_fwd_launch<N>(x, x_row_stride, gamma, beta, eps, y, mean, rstd, M, dtype, x_dtype, as_stream(s))
-  GSL_DISPATCH_D(D, CALL)
-#undef CALL
+  GSL_TRY(check_row_dtypes(__func__, dtype, GSL_F32, x_dtype));
+  GSL_TRY(ln_check_rows(__func__, (x_row_stride % 4) == 0, x_row_stride, D));
+  LnCall c{};
+  c.who = __func__; c.x = x; c.xs = x_row_stride; c.gamma = gamma; c.beta = beta; c.eps = eps; c.y = y; c.mean = mean; c.rstd = rstd;
+  c.M = M; c.D = D; c.dtype = dtype; c.x_dtype = x_dtype; c.st = as_stream(s);
+  return ln_fwd_launch(c);
 }
 
 extern "C" int gsl_layernorm_bwd(const void* dy, const void* x, long x_row_stride, const float* gamma, const float* mean,
@@ -317,19 +343,18 @@ extern "C" int gsl_layernorm_bwd(const void* dy, const void* x, long x_row_strid
                                  long drop_row_stride, int dres_cls_T, float* gmax, gsl_stream_t s) {
   GSL_CHECK_ARG(dy && x && gamma && mean && rstd && dx && M > 0, "null/size");
   GSL_CHECK_ARG(dtype == GSL_F32 || dtype == GSL_BF16 || dtype == GSL_F16, "dtype");
-  GSL_CHECK_ARG(stream_dtype == GSL_F32 || (stream_dtype == dtype && dtype != GSL_F32), "stream dtype (f32, or the operand format of a 16-bit mode)");
-  GSL_CHECK_ARG(x_dtype == GSL_F32 || ((x_dtype == GSL_BF16 || x_dtype == GSL_F16) && dtype == GSL_BF16) || (x_dtype == GSL_F16 && dtype == GSL_F16),
-                "x dtype (a 16-bit stream only in a 16-bit mode; bf16 stream only with bf16 operands)");
-  GSL_CHECK_ARG((x_row_stride % 4) == 0, "row stride alignment");
-  GSL_CHECK_ARG(x_row_stride >= D, "x_row_stride below the row length D");
+  GSL_TRY(check_row_dtypes(__func__, dtype, stream_dtype, x_dtype));
+  GSL_TRY(ln_check_rows(__func__, (x_row_stride % 4) == 0, x_row_stride, D));
   GSL_CHECK_ARG(io_row_stride <= 0 || io_row_stride >= D, "io_row_stride between 0 and the row length D (rows of dx would overlap)");
   GSL_CHECK_ARG(dres_cls_T >= 0 && (dres_cls_T == 0 || (dres && dres != dx)), "dres_cls_T: compact dres, out of place");
-  const DropCfg drop = make_drop(p_drop, seed, site);
-  const long ios = io_row_stride > 0 ? io_row_stride : D, drs = drop_row_stride > 0 ? drop_row_stride : D;
+  const long ios = io_row_stride > 0 ? io_row_stride : D;
   GSL_CHECK_ARG((ios % 4) == 0, "io row stride alignment");
-#define CALL(N) ln_bwd_launch<N>(dy, x, x_row_stride, gamma, mean, rstd, dres, dx, ios, dxb, M, dtype, stream_dtype, x_dtype, drop, drs, dres_cls_T, gmax, as_stream(s))
-  GSL_DISPATCH_D(D, CALL)
-#undef CALL
+  LnCall c{};
+  c.who = __func__; c.dy = dy; c.x = x; c.xs = x_row_stride; c.gamma = gamma; c.mean = const_cast<float*>(mean); c.rstd = const_cast<float*>(rstd);
+  c.dres = dres; c.dx = dx; c.ios = ios; c.dxb = dxb; c.M = M; c.D = D; c.dtype = dtype; c.stream_dtype = stream_dtype; c.x_dtype = x_dtype;
+  c.drop = make_drop(p_drop, seed, site); c.drs = drop_row_stride > 0 ? drop_row_stride : D; c.cls_T = dres_cls_T; c.gmax = gmax;
+  c.st = as_stream(s);
+  return ln_bwd_launch(c);
 }
 
 // LayerNorm forward that also emits u = alpha * LN(x) P^T (bf16 mode; P [>= 16, D] bf16 rows = lora_A rows zero-padded to 16; u [M, 64] bf16,
@@ -339,14 +364,10 @@ extern "C" int gsl_layernorm_fwd_lora(const void* x, long x_row_stride, const fl
                                       gsl_stream_t s) {
   GSL_CHECK_ARG(x && gamma && beta && y && mean && rstd && P && u && M > 0, "null/size");
   GSL_CHECK_ARG(D == 512 || D == 768, "width (512 or 768)");
-  GSL_CHECK_ARG((x_row_stride % 8) == 0 && (ldp % 8) == 0 && ldp >= D, "row stride alignment");
-  GSL_CHECK_ARG(x_row_stride >= D, "x_row_stride below the row length D");
-  const int grid = min((M + 63) / 64, 256 * 4);
-  if (D == 512)
-    hipLaunchKernelGGL((ln_fwd_lora_kernel<16>), dim3(grid), dim3(256), 0, as_stream(s), (const bf16_t*)x, x_row_stride, gamma, beta, eps,
-                       (bf16_t*)y, mean, rstd, M, (const bf16_t*)P, ldp, alpha, (bf16_t*)u);
-  else
-    hipLaunchKernelGGL((ln_fwd_lora_kernel<24>), dim3(grid), dim3(256), 0, as_stream(s), (const bf16_t*)x, x_row_stride, gamma, beta, eps,
-                       (bf16_t*)y, mean, rstd, M, (const bf16_t*)P, ldp, alpha, (bf16_t*)u);
-  return check_launch("gsl_layernorm_fwd_lora");
+  GSL_TRY(ln_check_rows(__func__, (x_row_stride % 8) == 0 && (ldp % 8) == 0 && ldp >= D, x_row_stride, D));
+  LnCall c{};
+  c.who = __func__; c.x = x; c.xs = x_row_stride; c.gamma = gamma; c.beta = beta; c.eps = eps; c.y = y; c.mean = mean; c.rstd = rstd;
+  c.M = M; c.D = D; c.P = P; c.ldp = ldp; c.alpha = alpha; c.u = u; c.st = as_stream(s);
+  return ln_fwd_lora_launch(c);
 }
+

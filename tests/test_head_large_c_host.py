@@ -97,7 +97,7 @@ def test_tiled_kernels_are_in_the_product_library():
     for name in (b"head_logits_tiled_kernel", b"head_de_tiled_kernel"):
         assert name in blob, name
     src = open(os.path.join(ROOT, "gs-lora_amd", "csrc", "head.hip")).read()
-    tiled = src[src.index("K10t class-tiled head"):src.index("template <int KIND>\nstatic void head_fwd_launch")]
+    tiled = src[src.index("K10t class-tiled head"):src.index("struct HeadCall {")]
     tiled += src[src.index("// Stage 1 of the class-tiled backward"):src.index("// compact != 0 (pool = 'cls' only)")]
     shared = re.findall(r"__shared__[^;]*;", tiled)
     assert len(shared) == 8
