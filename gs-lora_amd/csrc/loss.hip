@@ -78,7 +78,12 @@ __device__ __forceinline__ bool label_ok(long y, int n) { return y >= 0 && y < n
 __device__ __forceinline__ void nan_row(float* row, int n, int lane) {
   for (int c = lane; c < n; c += 64) row[c] = GSL_NAN;
 }
-__device__ __forceinline__ void grad_store(float* o, float g, int accumulate) { *o = accumulate ? (*o + g) : g; }
+// accumulate: fl(old + g) with g the value accumulate = 0 stores. Contraction is off here: fused into the product that forms g, the add
+// rounded once where the unrolled loop paired two elements and twice on the odd one behind them
+__device__ __forceinline__ void grad_store(float* o, float g, int accumulate) {
+#pragma clang fp contract(off)
+  *o = accumulate ? (*o + g) : g;
+}
 
 // ---- cross entropy of one row: loss, top-1 hit, and the log-sum-exp its gradient needs
 template <typename Row>
@@ -284,23 +289,26 @@ extern "C" int gsl_topk_hits(const float* logits, const int64_t* labels, int B, 
 // has_proto false: the prototype term is absent (kl_f / kl_r are not used).
 // =====================================================================================
 struct LossHyper { float beta, BND, alpha, w_f, w_r, BND_pro; };
+// torch's relu: a NaN stays a NaN (fmaxf(NaN, 0) is 0 — a NaN forget sum, from a label out of range or a class without a prototype, or
+// n_f = 0 in the pack, would leave a finite total and finite meters, and the deferred meter read would not stop the run)
+__device__ __forceinline__ float relu_nan(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 __device__ __forceinline__ void loss_scalar_tail(float ce_r, float ce_f, float kl_f, float kl_r, float hit_r, float hit_f, float n_r, float n_f,
                                                  const float* structure, bool has_proto, LossHyper h, float* total, float* meters,
                                                  float* coefs) {
 #pragma clang fp contract(off)
   const float loss_remain = ce_r / n_r;
   const float hinge_f = h.BND - ce_f / n_f;
-  const float loss_forget = fmaxf(hinge_f, 0.f);
+  const float loss_forget = relu_nan(hinge_f);
   const float st = structure ? structure[0] : 0.f;
   float pro_f = 0.f, pro_r = 0.f, hinge_p = 0.f;
-  if (has_proto) { hinge_p = h.BND_pro - kl_f / n_f; pro_f = h.w_f * fmaxf(hinge_p, 0.f); pro_r = h.w_r * (kl_r / n_r); }
+  if (has_proto) { hinge_p = h.BND_pro - kl_f / n_f; pro_f = h.w_f * relu_nan(hinge_p); pro_r = h.w_r * (kl_r / n_r); }
   const float tot = loss_forget * h.beta + loss_remain + st * h.alpha + (pro_f + pro_r);
   total[0] = tot;
   meters[0] = h.beta * loss_forget; meters[1] = loss_remain; meters[2] = tot; meters[3] = h.alpha * st;
   meters[4] = hit_f * (100.0f / n_f); meters[5] = hit_r * (100.0f / n_r); meters[7] = pro_r;
   // without the prototype term the reference still LOGS w_f * relu(BND_pro - 0) in losses_prototype_forget (engine_cl.py:103-110,
   // engine.py:118-125: prototype_loss_forget is the constant 0 there); the total does not contain it
-  meters[6] = has_proto ? pro_f : h.w_f * fmaxf(h.BND_pro, 0.f);
+  meters[6] = has_proto ? pro_f : h.w_f * relu_nan(h.BND_pro);
   coefs[0] = 1.0f / n_r;                                          // d total / d ce_r_sum
   coefs[1] = hinge_f > 0.f ? -h.beta / n_f : 0.f;                 // d total / d ce_f_sum   (relu'(0) = 0 as in torch)
   coefs[2] = (has_proto && hinge_p > 0.f) ? -h.w_f / n_f : 0.f;   // d total / d kl_f_sum

@@ -381,9 +381,16 @@ GSL_API int gsl_head_wgrad(const float* dlogits, const float* emb, const float* 
                  gsl_stream_t s);
 
 /* ---- K11 cross entropy (mean) + top-1 (engine_cl.py:65-78, util/utils.py:354-368).
- * out2 f32 [2] = { sum_i CE_i , #correct }; row_ws f32 [2*B] scratch (per-row loss / hit, summed in a fixed order). */
+ * out2 f32 [2] = { sum_i CE_i , #correct }; row_ws f32 [2*B] scratch (per-row loss / hit, summed in a fixed order).
+ * Row loss = lse - x[y] with lse = max + log(sum exp(x - max)): its absolute error is half an ulp of |lse| (not of the loss), see
+ * oracle/loss_probes.py for the bounds the tests hold every output to. A row counts as correct when its label is the FIRST index of the row
+ * maximum (torch.argmax's rule on ties). Non-finite logits: -inf outside the label's place is an ordinary value (finite loss, gradient
+ * exactly 0 there); -inf at the label gives +inf; +inf or NaN anywhere gives a NaN row loss, as torch does (the arg-max skips a NaN: the
+ * row's hit is that of its other logits). A label outside [0, C): NaN
+ * row loss (and sum), no hit, a NaN gradient row from gsl_ce_bwd; nothing outside the row is read or written. */
 GSL_API int gsl_ce_fwd(const float* logits, const int64_t* labels, float* out2, float* row_ws, int B, int C, gsl_stream_t s);
-/* dlogits (+)= coef[0] * scale * (softmax - onehot) ; coef is a DEVICE scalar (no host sync). */
+/* dlogits (+)= coef[0] * scale * (softmax - onehot) ; coef is a DEVICE scalar (no host sync). accumulate = 1: every element is fl(old + g)
+ * with g the value accumulate = 0 stores (two roundings, no fused multiply-add); the same holds for gsl_proto_kl_bwd / gsl_proto_l2_bwd. */
 GSL_API int gsl_ce_bwd(const float* logits, const int64_t* labels, const float* coef, float scale,
                float* dlogits, int B, int C, int accumulate, gsl_stream_t s);
 
@@ -406,7 +413,8 @@ GSL_API int gsl_proto_l2_bwd(const float* emb, const int64_t* labels, const floa
 /* ---- K11b precision@k for several k in one launch (util/utils.py:354-368): hits[j] = number of rows whose label is among the ks[j]
  * largest logits, counted as "fewer than ks[j] logits are strictly greater than the label's" (equal to output.topk(ks[j]) wherever the
  * ks[j]-th place is not tied). ks: HOST array of nk <= gsl_topk_max_k() positive ints (it travels in the kernel arguments);
- * hits: DEVICE int32 [nk], cleared by the call. An out-of-range label is never a hit. */
+ * hits: DEVICE int32 [nk], cleared by the call. An out-of-range label is never a hit. On a tie at the ks[j]-th place the rule counts every
+ * row whose label's logit EQUALS the ks[j]-th largest as a hit (torch.topk picks one of the equals); k >= C counts every valid row. */
 GSL_API int gsl_topk_max_k(void);
 GSL_API int gsl_topk_hits(const float* logits, const int64_t* labels, int B, int C, const int* ks, int nk, int* hits, gsl_stream_t s);
 
@@ -414,6 +422,10 @@ GSL_API int gsl_topk_hits(const float* logits, const int64_t* labels, int B, int
  *   total = beta*relu(BND - ce_f_sum/n_f) + ce_r_sum/n_r + alpha*structure + w_f*relu(BND_pro - kl_f_sum/n_f) + w_r*kl_r_sum/n_r
  * meters8 = [beta*loss_forget, loss_remain, total, alpha*structure, top1_forget %, top1_remain %, proto_f, proto_r],
  * coefs5 = d total / d {ce_r_sum, ce_f_sum, kl_f_sum, kl_r_sum, structure} (relu'(0) = 0). kl_* / structure nullable (term absent).
+ * Without the prototype term meters8[6] still logs w_f * relu(BND_pro), as the reference does; the total does not contain it.
+ * Every operation is a single f32 rounding in the order of the reference's torch expression (bit-equal to oracle/loss_probes.py tail32).
+ * relu keeps a NaN as torch's does: a NaN forget sum (a label out of range, a class without a prototype) gives a NaN total and NaN
+ * meters8[0] / [2] / [6]; the coefficient of a NaN hinge is 0. n_r > 0 and n_f > 0 are required.
  * All inputs and outputs are device scalars / small device arrays: no host sync. */
 GSL_API int gsl_loss_combine(const float* ce_r_sum, const float* ce_f_sum, const float* kl_f_sum, const float* kl_r_sum,
                      const float* structure, const float* hit_r, const float* hit_f, float n_r, float n_f,
@@ -422,7 +434,11 @@ GSL_API int gsl_loss_combine(const float* ce_r_sum, const float* ce_f_sum, const
 
 /* Data-parallel form of the scalar tail (SURVEY 8(e) collective C2; reference semantics train_own_forget_cl.py:494-497, engine_cl.py:78,99):
  * pack8 = the sum-all-reduced [ce_r_sum, ce_f_sum, hit_r, hit_f, n_r, n_f, kl_f_sum, kl_r_sum] — global batch sums and sizes, all on the
- * device. Same outputs as gsl_loss_combine; coefs5 are the derivatives with respect to THIS rank's local sums (= those of the global sums). */
+ * device. Same outputs as gsl_loss_combine; coefs5 are the derivatives with respect to THIS rank's local sums (= those of the global sums).
+ * n_r and n_f are device values and are NOT checked. n_f = 0 (no forget row on any rank; then ce_f_sum = hit_f = kl_f_sum = 0) gives
+ * what the reference's mean over an empty batch gives: 0 / 0 = NaN in the forget hinges, so total, meters8[0], [2], [4] and (with the
+ * prototype term) [6] are NaN, coefs5[1] = coefs5[2] = 0, and the remain-side outputs (meters8[1], [5], [7], coefs5[0], [3], [4]) are
+ * those of the remain rows alone. n_r = 0 likewise turns the remain side and the total NaN (coefs5[0] and [3] are +-inf). */
 GSL_API int gsl_loss_combine_pack(const float* pack8, const float* structure, int has_proto, float beta, float BND, float alpha, float w_f,
                           float w_r, float BND_pro, float* total, float* meters8, float* coefs5, gsl_stream_t s);
 /* The loss section of a single-process step in ONE launch (launch-bound batches): per-row CE / top-1 of logits [N,C] and prototype KL of
