@@ -2,6 +2,8 @@
 //   K10 cls-pool + LayerNorm + CosFace / ArcFace margin head (vit_face.py:540-546, 171-208, 72-143) fwd / bwd
 //       ArcFace departs from the reference in one place: sine = sqrt(max(1 - cos^2, 0)) and its derivative divides by max(sine, 1e-6),
 //       where the reference's sqrt returns NaN at |cos| > 1 (rounding) and an infinite gradient at |cos| = 1.
+//       F.normalize's clamp max(||v||, 1e-12) has derivative 0 below it: the backward (an embedding under the clamp) and the weight
+//       gradient (a row of W under it) then give d v = d v-hat / 1e-12 without the projection term, as autograd gives the reference.
 // The losses behind it are in loss.hip, the patch gathers in front of the network in patch.hip.
 #include <cmath>
 #include <type_traits>
@@ -521,7 +523,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
   const float* er = emb + (size_t)b * D;
   float nn = 0.f;
   for (int d = tid; d < D; d += 256) nn += er[d] * er[d];
-  const float nrm = fmaxf(sqrtf(block_sum(nn, sm)), 1e-12f);
+  const float raw = sqrtf(block_sum(nn, sm));
+  const float nrm = fmaxf(raw, 1e-12f);
   if constexpr (!WS) {
     if (dlogits) {
       for (int c = tid; c < C; c += 256) dl[c] = cs * dlogits[(size_t)b * C + c];
@@ -543,7 +546,9 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     de[d] = g;                       // d e-hat
     dotp += g * er[d];
   }
-  const float proj = block_sum(dotp, sm) / (nrm * nrm);   // (e-hat . d e-hat) / ||e||
+  // (e-hat . d e-hat) / ||e||; ||e|| < 1e-12: F.normalize's clamp has derivative 0 there, d e = d e-hat / 1e-12 (the rule of head_wgrad_kernel)
+  const float projn = block_sum(dotp, sm) / (nrm * nrm);
+  const float proj = (raw < 1e-12f) ? 0.0f : projn;      // (a NaN norm keeps the NaN projection)
   const float mu = mean[b], rs = rstd[b];
   const X* xr = x + (size_t)b * Tn * D;
   for (int d = tid; d < D; d += 256) {          // the pooled row the forward normalised (same summation order)

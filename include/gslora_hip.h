@@ -310,6 +310,14 @@ GSL_API int gsl_head_fwd(const void* x, int x_dtype, int T, const float* gamma, 
  * amax_ws [B], pass 2 picks the power of two S with S * max in [2^10, 2^11), stores dx / dxb multiplied by S and publishes
  * gscale[0..1] = {S, 1/S} on the device (no host sync; HIP-graph safe). Every kernel downstream is linear in the gradient; the
  * LoRA-gradient reductions take gscale and divide S out.
+ * The scale rule, exactly: max = m 2^ex with m in [0.5, 1) (frexp), S = 2^(E - ex), the exponent clamped to +-60 — a maximum that is a
+ * power of two lands on 2^(E-1). max = 0 (every gradient zero): S = 1. gscale[1] is 1 / S, exact.
+ * Non-finite gradients: an image whose gradient holds a NaN (a NaN or Inf row of dlogits: Inf - Inf in the sum over the classes) gets a
+ * non-finite dx and its maximum is PASSED OVER (fmaxf): S is the rule's value for the largest finite image maximum, every other image is
+ * S times its gradient, and gscale[0..1] stay finite powers of two. An image maximum of +Inf (no NaN in its row) gives S = 1. The
+ * non-finite image reaches the overflow guard below through the LayerNorm backwards that read its dx.
+ * Zero embeddings: F.normalize's clamp has derivative 0 below it, so an image with ||emb|| < 1e-12 (a constant row with beta = 0, or
+ * any embedding under the clamp) gets d emb = d e-hat / 1e-12 without the projection term, as autograd gives the reference.
  * Overflow guard (round 6; GradScaler semantics without a host sync). gscale is f32 [4] that PERSISTS across steps (zero it once):
  *   [2] = the largest |scaled gradient| the LayerNorm backwards of this backward saw (gsl_layernorm_bwd's gmax; reset to 0 here),
  *   [3] = the exponent E in use: S * max lands in [2^(E-1), 2^E).
@@ -335,7 +343,10 @@ GSL_API int gsl_head_bwd(const float* dlogits, const float* demb, const void* x,
  *                 cos - sin(pi - m)*m (easy_margin: cos); cos_m is not read, linear_head must be 0. The constants are computed
  *                 from the double m as the reference's math.* does, then rounded to float. The forward writes cos_y [B] = the
  *                 label column's cosine before the margin; the backward reads it (and label) to take the same branch and scales
- *                 dlogits[y] by d phi / d cos. One departure: 1 - cos^2 is clamped at 0 and the derivative divides by
+ *                 dlogits[y] by d phi / d cos. A label outside [0, C) (-1, C, a value beyond 32 bits: the comparison is 64-bit)
+ *                 names no class: no column takes the margin or the factor, and cos_y[b] is NOT written (nor read). logits = NULL:
+ *                 cos_y is not written at all. The branch is a strict `>`: cos = th (easy margin: cos = +-0) takes cos - mm (cos)
+ *                 in the forward and d phi = 1 in the backward. One departure: 1 - cos^2 is clamped at 0 and the derivative divides by
  *                 max(sine, 1e-6) (the reference gives NaN for |cos| > 1 and an infinite gradient at |cos| = 1).
  * Every other argument means what it means for gsl_head_fwd / gsl_head_bwd. */
 GSL_API int gsl_head_fwd_margin(const void* x, int x_dtype, int T, const float* gamma, const float* beta, float eps,
