@@ -43,7 +43,7 @@ extern "C" int gsl_patchify(const float* img, void* out, int B, int C, int H, in
 // nn.Unfold(k, stride, pad) -> [B*T, ldo]: row b*T is the zero cls slot, row b*T + 1 + t window t (row-major over Lh x Lw), column
 // j = c*k*k + kh*k + kw; out-of-image taps and the K padding j >= C*k*k are 0. Every element is written.
 // The column decode is the same for every row: one LDS table per workgroup, {c*H*W + kh*W + kw, kh << 16 | kw}; padding columns carry an
-// out-of-range kh, so they fail the bounds test like a padding tap. A workgroup takes UNF_ROWS consecutive rows (neighbouring windows of
+// out-of-range kw (65535: beyond every W the entry accepts, independent of H), so they fail the bounds test like a padding tap. A workgroup takes UNF_ROWS consecutive rows (neighbouring windows of
 // one image: the ~(k/stride)^2 re-reads of a pixel hit L2) and its lanes walk them as 8-column chunks, consecutive lanes on consecutive
 // chunks of a row: one 16-byte store per lane for 16-bit outputs, two for f32. The cls row gets an out-of-range h0 and comes out 0.
 constexpr int UNF_ROWS = 32;
@@ -89,7 +89,9 @@ __global__ void __launch_bounds__(256) unfold_patches_kernel(const float* __rest
       const int c = j / kk, r = j - c * kk, kh = r / k, kw = r - kh * k;
       unf_tab[j] = make_int2(c * H * W + kh * W + kw, (kh << 16) | kw);
     } else {
-      unf_tab[j] = make_int2(0, 0x7fff << 16);      // kh out of range: always 0
+      // kw = 0xffff: w = w0 + 65535 >= 65535 - pad > W for every accepted W < 32768 (pad < k <= 64), whatever H and h0 are. (kh = 0x7fff alone
+      // was in range again at H + pad >= 32768: row -pad of the image, read in front of it.) Always 0.
+      unf_tab[j] = make_int2(0, (0x7fff << 16) | 0xffff);
     }
   }
   const int nch = ldo >> 3, per = UNF_ROWS * nch;

@@ -1,7 +1,8 @@
 """Face verification, host side (no GPU): the restated pieces of util/verification.py against the real sklearn / scipy / reference
 results recorded in tests/golden/verification_small.npz (tools/make_golden_verification.py), and the C ABI of the three metric entry points.
 
-The kernels themselves run in tests/test_hip_verification.py. Here a numpy model of their integer arithmetic (contiguous folds, strict
+The kernels themselves run in tests/test_hip_verification.py. Here the numpy model of their integer arithmetic (oracle/eval_probes.py:
+counts_model, select_model — contiguous folds, strict
 (double)dist < thr, train counts = totals minus the fold's, first arg-max of the integer train numerator, f64 divisions on the integers)
 is held against the reference's outputs bit for bit: it pins the algorithm the kernels implement and guards the fixture."""
 import os
@@ -11,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.eval_probes import counts_model, select_model
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ["model", "p603_f10", "p50_f5", "nosame", "ties"]
 THRESHOLDS = np.arange(0, 4, 0.01)
@@ -19,38 +22,6 @@ THRESHOLDS = np.arange(0, 4, 0.01)
 @pytest.fixture(scope="module")
 def gold():
     return np.load(os.path.join(ROOT, "tests", "golden", "verification_small.npz"))
-
-
-def counts_model(dist32, issame, thresholds, F):
-    """gsl_verif_fold_counts in numpy: (counts [F, Tn, 2], fold_tot [F, 2])."""
-    from util import verification as V
-    d = dist32.astype(np.float32).astype(np.float64)
-    same = issame.astype(bool)
-    counts, tot = np.zeros((F, len(thresholds), 2), np.int64), np.zeros((F, 2), np.int64)
-    for f, (a, b) in enumerate(V.fold_bounds(len(d), F)):
-        acc = d[a:b, None] < np.asarray(thresholds)[None, :]
-        counts[f, :, 0] = (acc & same[a:b, None]).sum(0)
-        counts[f, :, 1] = (acc & ~same[a:b, None]).sum(0)
-        tot[f] = same[a:b].sum(), (~same[a:b]).sum()
-    return counts, tot
-
-
-def select_model(counts, tot, thresholds):
-    """gsl_verif_select in numpy: accuracy [F], best_thresholds [F], tpr [Tn], fpr [Tn]."""
-    F, Tn = counts.shape[:2]
-    acc, best = np.zeros(F), np.zeros(F)
-    all_c, all_d = counts.sum(0), tot[:, 1].sum()
-    for f in range(F):
-        tr = all_c - counts[f]
-        num = tr[:, 0] + (all_d - tot[f, 1]) - tr[:, 1]
-        bi = int(np.argmax(num))      # first maximum
-        best[f] = thresholds[bi]
-        acc[f] = float(counts[f, bi, 0] + tot[f, 1] - counts[f, bi, 1]) / float(tot[f].sum())
-    tpr, fpr = np.zeros(Tn), np.zeros(Tn)
-    for f in range(F):      # fold order, as np.mean(axis=0) adds the rows
-        tpr += 0.0 if tot[f, 0] == 0 else counts[f, :, 0].astype(np.float64) / float(tot[f, 0])
-        fpr += 0.0 if tot[f, 1] == 0 else counts[f, :, 1].astype(np.float64) / float(tot[f, 1])
-    return acc, best, tpr / F, fpr / F
 
 
 def test_fold_bounds_are_sklearns_kfold(gold):
