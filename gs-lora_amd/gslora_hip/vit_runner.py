@@ -9,6 +9,7 @@ This is the host-side "engine" behind vit_pytorch_face.ViT_face.forward: it owns
 Reference semantics: vit_pytorch_face/vit_face.py:523-548 (forward), autograd of the same.
 """
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -90,6 +91,10 @@ class BlockSpec:
 
 # head kinds that run the plain linear classifier of gsl_head_fwd / gsl_head_bwd (no normalisation, no margin)
 LINEAR_HEADS = ("linear", "softmax")
+# the kernels of gsl_gemm_nt_lora that hold the in-kernel LoRA form at few rows (ViTRunner.lora_in_kernel), and what the library's tile
+# rule answered per (rows, N, K, dtype): a launch-bound step asks once per shape, not once per site
+RING64_TILES = (L.TILE_RING64, L.TILE_RING64_WIDE, L.TILE_RING64_KSPLIT)
+_RING_LORA = {}
 
 
 class ModelSpec:
@@ -211,7 +216,6 @@ class _Pass:
         self.xdt = (torch.float16 if xf16 else torch.bfloat16) if xbf else torch.float32            # dtype of the residual stream
         self.epi_res = _res_epilogue(self.xdt)
         self.epi_patch = (L.EPI_PATCH_F16 if xf16 else L.EPI_PATCH_BF16) if xbf else L.EPI_PATCH
-
 
     def gemm(self, *a, **kw):
         """ops.gemm_nt in the pass's GEMM mode: every GEMM of the forward and the backward goes through here. (Attention, LayerNorm, head, losses,
@@ -377,11 +381,12 @@ class ViTRunner:
         return ent["out"]
 
     def qkv_lora_ops(self, i, ml, dtype):
-        """Operands of the three q / k / v adapters of one MergedLinear, as ONE LoRA K segment (r3 = 3r <= 64 live columns):
-          A_rows [64, dim]      rows g*r+j = A_g[j, :]                       (u = s * xn A_all^T)
-          Bblk  [3*inner, 64]   row g*inner+n, column g*r+j = B_g[n, j]      (qkv += u Bblk^T: block diagonal)
-          BblkT [64, 3*inner]                                                 (v = s * dqkv Bblk)
-          AT    [dim, 64]       column g*r+j = A_g[j, :]                      (dxn1 += v A_all)"""
+        """Operands of the three q / k / v adapters of one MergedLinear, as ONE LoRA K segment (r3 = 3r <= 64 live columns), under the
+        K-segment kinds of LORA_KINDS:
+          A_rows  [64, dim]      rows g*r+j = A_g[j, :]                       (u = s * xn A_all^T)
+          B_cols  [3*inner, 64]  row g*inner+n, column g*r+j = B_g[n, j]      (qkv += u Bblk^T: block diagonal)
+          BT_rows [64, 3*inner]                                                (v = s * dqkv Bblk)
+          AT_cols [dim, 64]      column g*r+j = A_g[j, :]                      (dxn1 += v A_all)"""
         r, ng = ml.r, len(ml.enable_lora)
         if ng * r > PADK:
             raise NotImplementedError("gs-lora_amd: 3 * lora_rank must not exceed 64 for --lora_pos Attention")
@@ -394,7 +399,7 @@ class ViTRunner:
             for g in range(ng):
                 bblk[g * inner:(g + 1) * inner, g * r:(g + 1) * r] = B[g * inner:(g + 1) * inner]
             cast = (lambda t: t.contiguous()) if dtype == torch.float32 else (lambda t: ops.cast(t.contiguous(), dtype))
-            return dict(A_rows=cast(a_rows), Bblk=cast(bblk), BblkT=cast(bblk.t()), AT=cast(a_rows.t()))
+            return dict(A_rows=cast(a_rows), B_cols=cast(bblk), BT_rows=cast(bblk.t()), AT_cols=cast(a_rows.t()))
         return self._cached(self._lcache, (f"qkvlora{i}", dtype), (ml.lora_A, ml.lora_B), build)
 
     def refresh_lora_packs(self, dtype):
@@ -429,20 +434,66 @@ class ViTRunner:
             z = self._wcache[("zeros", n, dev)] = torch.zeros(n, device=dev, dtype=torch.float32)
         return z
 
-    def lora_in_kernel(self, dtype, rows, N=None):
+    def lora_in_kernel(self, dtype, rows, N, K):
         """The bf16 wide GEMMs compute the LoRA down-projection inside the kernel (no extra pass over the activation): on the 256x256
         8-phase kernel from INK_MIN_ROWS rows on, and on the 64x64 ring kernel wherever gsl_gemm_nt_lora picks it (few rows: the
         launch-bound regime, where the separate skinny GEMM is a 6 - 12 us launch per adapted layer and direction). In between, the
-        N = 512 GEMMs would run the 8-phase kernel on a handful of workgroups and the two-launch K-segment form wins."""
+        N = 512 GEMMs would run the 8-phase kernel on a handful of workgroups and the two-launch K-segment form wins. Which kernel
+        gsl_gemm_nt_lora picks is the library's tile rule (csrc/gemm.hip), asked once per shape."""
         if dtype not in OP16 or self._rank > 16:
             return False
         if rows >= INK_MIN_ROWS:
             return True
-        if N is None or not INK_SMALL:
+        if not INK_SMALL:
             return False
-        t256 = ((rows + 255) // 256) * ((N + 255) // 256)
-        t128 = ((rows + 127) // 128) * ((N + 127) // 128)
-        return (rows < 1024 or t256 < 128) and t128 <= 256      # the tile rule of gsl_gemm_nt_lora (csrc/gemm.hip)
+        key = (rows, N, K, dtype)
+        if key not in _RING_LORA:
+            _RING_LORA[key] = ops.gemm_tile_choice(rows, N, K, dtype, in_kernel_lora=True) in RING64_TILES
+        return _RING_LORA[key]
+
+    # ------------------------------------------------------------------ the adapted linear layer
+    # out = epilogue(a W^T + s (a P^T) Q^T): PACK_GEOM kinds of (P, Q) by direction and form. Forward: P from lora_A, Q from lora_B; dX
+    # (a = dY, W = the transposed weight): P from lora_B, Q from lora_A. "kseg": a skinny GEMM writes u = s a P^T [rows, 64] and the
+    # wide GEMM takes (u, Q) as a second K segment; "ink": gsl_gemm_nt_lora forms u inside the wide GEMM (P [16, K], Q [N, 32]).
+    LORA_KINDS = {("fwd", "kseg"): ("A_rows", "B_cols"), ("fwd", "ink"): ("A_rows16", "B_cols32"),
+                  ("dx", "kseg"): ("BT_rows", "AT_cols"), ("dx", "ink"): ("BT_rows16", "AT_cols32")}
+
+    def ffn_packs(self, i, n, layer, dtype):
+        """kind -> the packed operand of the adapter of FFN layer n (1 / 2) of block i."""
+        return lambda kind: self.lora_pack(f"{kind[0]}{n}_{i}", layer.lora_A if kind[0] == "A" else layer.lora_B, kind, dtype)
+
+    def _lora_project(self, c, a, pack, direction, N, *, in_kernel_ok=True, u=None, compact=False):
+        """First half of one adapted linear layer: the form, the [rows, 64] down-projection u and, in the K-segment form, the skinny
+        GEMM that fills it. pack: kind -> operand (ffn_packs, the q / k / v adapters' table), None: no live adapter, a plain GEMM follows.
+        in_kernel_ok=False keeps the K-segment form whatever lora_in_kernel says; u: the projection from another producer
+        (gsl_layernorm_fwd_lora); compact: the skinny GEMM also writes u's first 16 columns as [rows, 16] (step.uc).
+        -> the step for _lora_finish; step.u is the projection for the stash and the reductions (in-kernel form: filled by _lora_finish)."""
+        st = SimpleNamespace(a=a, pack=pack, u=u, uc=None, ink=False, kinds=None)
+        if pack is None:
+            return st
+        rows, K = a.shape
+        st.ink = in_kernel_ok and u is None and self.lora_in_kernel(c.dt, rows, N, K)
+        st.kinds = self.LORA_KINDS[direction, "ink" if st.ink else "kseg"]
+        if u is None:
+            st.u = torch.empty(rows, PADK, device=c.dev, dtype=c.dt)
+            if not st.ink:
+                if compact:
+                    st.uc = torch.empty(rows, 16, device=c.dev, dtype=c.dt)
+                c.gemm(a, pack(st.kinds[0]), st.u, alpha=c.s_lora, out2=st.uc)
+        return st
+
+    def _lora_finish(self, c, st, w, out, kw, mulgrad=None):
+        """Second half: the wide GEMM into `out`; kw: its epilogue and the epilogue's operands (a dict, handed on once: this runs per adapted
+        layer of a launch-bound step). mulgrad (in-kernel form only): the operands of the gradient-fused epilogue of
+        gsl_gemm_nt_lora_mulgrad behind `out` (aux, U1, G1, g1s, Y2, G2, g2s, r). -> out"""
+        if st.pack is None:
+            return c.gemm(st.a, w, out, **kw)
+        if st.ink:
+            P, Q = st.pack(st.kinds[0]), st.pack(st.kinds[1])
+            if mulgrad is not None:
+                return ops.gemm_nt_lora_mulgrad(st.a, w, P, Q, c.s_lora, st.u, out, *mulgrad, **kw)
+            return ops.gemm_nt_lora(st.a, w, P, Q, c.s_lora, st.u, out, **kw)
+        return c.gemm(st.a, w, out, A2=st.u, W2=st.pack(st.kinds[1]), **kw)
 
     def ensure_bucket(self, spec=None):
         spec = spec or self.model.hip_spec()
@@ -558,23 +609,21 @@ class ViTRunner:
         fold = xn is None
         qsplit = tail and QSPLIT and not c.attn_site
         qkv = torch.empty(M, (2 if qsplit else 3) * inner, device=c.dev, dtype=dt)
-        uq, lora = None, {}
-        if c.attn_site and not blk.qkv_lora.merged:      # q / k / v adapters: one block-diagonal LoRA K segment
-            qo = self.qkv_lora_ops(i, blk.qkv_lora, dt)
-            uq = torch.empty(M, PADK, device=c.dev, dtype=dt)
-            c.gemm(xn, qo["A_rows"], uq, alpha=c.s_lora)
-            lora = dict(A2=uq, W2=qo["Bblk"])
+        a = x if fold else xn
+        # live q / k / v adapters: one block-diagonal LoRA K segment, always in that form (no fold while they are live: a is xn)
+        live = c.attn_site and not blk.qkv_lora.merged
+        st = self._lora_project(c, a, self.qkv_lora_ops(i, blk.qkv_lora, dt).__getitem__ if live else None, "fwd", 3 * inner, in_kernel_ok=False)
         # operand, weight, bias and epilogue: the stream itself with W' = W * gamma, d = W beta (+ bias) and the row statistics finishing
         # the normalisation in the epilogue (aux = rowsum(W')), or LayerNorm 1's output with the weight as it is
         if fold:
-            a, (w, cw, b), ln = x, self.w_ln(f"qkv{i}", blk.qkv_w, blk.ln1.weight, blk.ln1.bias, blk.qkv_b, dt), dict(pos=mean1, cls=rstd1)
+            (w, cw, b), ln = self.w_ln(f"qkv{i}", blk.qkv_w, blk.ln1.weight, blk.ln1.bias, blk.qkv_b, dt), dict(pos=mean1, cls=rstd1)
         else:
-            a, w, cw, b, ln = xn, self.w(f"qkv{i}", blk.qkv_w, dt), None, (None if blk.qkv_b is None else blk.qkv_b.detach()), {}
+            w, cw, b, ln = self.w(f"qkv{i}", blk.qkv_w, dt), None, (None if blk.qkv_b is None else blk.qkv_b.detach()), {}
         if not qsplit:
             hm = 1 if (QKV_HEAD_MAJOR and dt in OP16) else 0
             epi = (L.EPI_STORE_QKV_HM_LN if hm else L.EPI_STORE_LN) if fold else (L.EPI_STORE_QKV_HM if hm else L.EPI_STORE)
-            c.gemm(a, w, qkv, epilogue=epi, T=T, aux=cw, bias=b, **lora, **ln)
-            return qkv, None, uq, hm
+            self._lora_finish(c, st, w, qkv, dict(epilogue=epi, T=T, aux=cw, bias=b, **ln))
+            return qkv, None, st.u, hm
         # K and V for every token, Q for the cls rows only: rows inner .. 3*inner of the fused weight (and of W', c, d) are K | V
         rows = lambda t, s: None if t is None else t[s]
         kv, q = slice(inner, None), slice(None, inner)
@@ -602,62 +651,38 @@ class ViTRunner:
     def _fwd_ffn(self, c, i, blk, x1):
         """FFN sub-layer: x2 = x1 + drop(W2' drop(gelu(W1' LN2 x1))), W' = W + s B A while the FFN adapters are live.
         -> (x2, this sub-layer's part of the block's stash or None)"""
-        dt, D, r, s_lora, dev, save = c.dt, c.D, c.r, c.s_lora, c.dev, c.save
-        p_drop, seed, sflag = c.p_drop, c.seed, c.sflag
+        dt, D, r, dev, save = c.dt, c.D, c.r, c.dev, c.save
         n2, l1, l2 = blk.ln2, blk.l1, blk.l2
         Mr, mlp = x1.shape[0], l1.weight.shape[0]
         lora_on = r > 0 and not c.attn_site and not l1.merged
+        pk1, pk2 = (self.ffn_packs(i, 1, l1, dt), self.ffn_packs(i, 2, l2, dt)) if lora_on else (None, None)
         # bf16 stream: LayerNorm 2 also emits u1 = s * xn2 A1^T (the LoRA K segment of FFN1) instead of a skinny GEMM that re-reads xn2
         ln_u1 = LN_LORA and lora_on and r <= 16 and D in (512, 768) and x1.dtype == torch.bfloat16 and dt == torch.bfloat16      # (bf16 operands + bf16 stream only)
+        u1_ln = None
         if ln_u1:
             xn2, mean2, rstd2, u1_ln = ops.layernorm_fwd_lora(x1, D, Mr, D, n2.weight.detach(), n2.bias.detach(), c.eps,
-                                                               self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), s_lora)
+                                                               pk1(self.LORA_KINDS["fwd", "kseg"][0]), c.s_lora)
         else:
             xn2, mean2, rstd2 = ops.layernorm_fwd(x1, D, Mr, D, n2.weight.detach(), n2.bias.detach(), c.eps, dt)
         if lora_on and (abs(l1.scaling * r - 1.0) > 1e-9 or abs(l2.scaling * r - 1.0) > 1e-9):
             raise NotImplementedError("gs-lora_amd: the fused LoRA path uses scaling = 1 / r (lora_alpha = 1, the only value GS-LoRA "
                                       f"passes); got scaling {l1.scaling} / {l2.scaling} for r = {r}")
-        u1 = u2 = u1c = None
         h = torch.empty(Mr, mlp, device=dev, dtype=dt)
         gp8 = GP8 and dt in OP16 and save and mlp % 64 == 0
-        epi_gelu = L.EPI_BIAS_GELU_G8 if gp8 else L.EPI_BIAS_GELU
         gp = torch.empty(Mr, mlp, device=dev, dtype=torch.uint8 if gp8 else dt) if save else None
-        if lora_on:
-            if Mr < INK_MIN_ROWS and not ln_u1 and self.lora_in_kernel(dt, Mr, mlp):
-                # few rows: u1 = s * xn2 A1^T inside the FFN1 GEMM (64x64 ring kernel) instead of a skinny launch in front of it.
-                # (At full size the K-segment form below is as fast: the 8 N-tiles of a row panel would each recompute u1.)
-                u1 = torch.empty(Mr, PADK, device=dev, dtype=dt)
-                ops.gemm_nt_lora(xn2, self.w(f"w1_{i}", l1.weight, dt), self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows16", dt),
-                                 self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols32", dt), s_lora, u1, h, epilogue=epi_gelu,
-                                 bias=l1.bias.detach(), out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
-            else:
-                if ln_u1:
-                    u1 = u1_ln
-                else:
-                    u1 = torch.empty(Mr, PADK, device=dev, dtype=dt)
-                    # (16-bit modes: the GEMM also writes u1's first 16 columns as a compact [M, 16] tensor — the operand form the
-                    #  gradient-fused FFN2-dX epilogue reads 32 rows of with one contiguous 1 KB load; rank <= 16)
-                    u1c = torch.empty(Mr, 16, device=dev, dtype=dt) if (save and dt in OP16 and r <= 16 and Mr >= INK_MIN_ROWS) else None
-                    c.gemm(xn2, self.lora_pack(f"A1_{i}", l1.lora_A, "A_rows", dt), u1, alpha=s_lora, out2=u1c)
-                c.gemm(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, A2=u1,
-                            W2=self.lora_pack(f"B1_{i}", l1.lora_B, "B_cols", dt), bias=l1.bias.detach(), out2=gp,
-                            p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag, tag="ffn1")
-            u2 = torch.empty(Mr, PADK, device=dev, dtype=dt)
-            if not self.lora_in_kernel(dt, Mr, D):
-                c.gemm(h, self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows", dt), u2, alpha=s_lora)
-        else:
-            c.gemm(xn2, self.w(f"w1_{i}", l1.weight, dt), h, epilogue=epi_gelu, bias=l1.bias.detach(),
-                        out2=gp, p_drop=p_drop, seed=seed, site=(4 * i + 1) | sflag)
+        # FFN1. In-kernel only at few rows: at full size the K-segment form is as fast (the 8 N-tiles of a row panel would each recompute
+        # u1), and its skinny GEMM also writes u1's first 16 columns as a compact [M, 16] tensor — the operand form the gradient-fused
+        # FFN2-dX epilogue reads 32 rows of with one contiguous 1 KB load (16-bit modes, rank <= 16)
+        st1 = self._lora_project(c, xn2, pk1, "fwd", mlp, in_kernel_ok=Mr < INK_MIN_ROWS, u=u1_ln,
+                                 compact=save and dt in OP16 and r <= 16 and Mr >= INK_MIN_ROWS)
+        self._lora_finish(c, st1, self.w(f"w1_{i}", l1.weight, dt), h, dict(
+            epilogue=L.EPI_BIAS_GELU_G8 if gp8 else L.EPI_BIAS_GELU, bias=l1.bias.detach(), out2=gp, p_drop=c.p_drop, seed=c.seed,
+            site=(4 * i + 1) | c.sflag, tag="ffn1" if lora_on else None))
+        st2 = self._lora_project(c, h, pk2, "fwd", D)
         x2 = torch.empty(Mr, D, device=dev, dtype=c.xdt)
-        if lora_on and self.lora_in_kernel(dt, Mr, D):
-            ops.gemm_nt_lora(h, self.w(f"w2_{i}", l2.weight, dt), self.lora_pack(f"A2_{i}", l2.lora_A, "A_rows16", dt),
-                             self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols32", dt), s_lora, u2, x2, epilogue=c.epi_res,
-                             bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
-        else:
-            c.gemm(h, self.w(f"w2_{i}", l2.weight, dt), x2, epilogue=c.epi_res, A2=u2,
-                        W2=self.lora_pack(f"B2_{i}", l2.lora_B, "B_cols", dt) if lora_on else None,
-                        bias=l2.bias.detach(), res=x1, p_drop=p_drop, seed=seed, site=(4 * i + 2) | sflag)
-        return x2, (dict(mean2=mean2, rstd2=rstd2, xn2=xn2, u1=u1, u1c=u1c, h=h, gp=gp, u2=u2, lora_on=lora_on) if save else None)
+        self._lora_finish(c, st2, self.w(f"w2_{i}", l2.weight, dt), x2, dict(
+            epilogue=c.epi_res, bias=l2.bias.detach(), res=x1, p_drop=c.p_drop, seed=c.seed, site=(4 * i + 2) | c.sflag))
+        return x2, (dict(mean2=mean2, rstd2=rstd2, xn2=xn2, u1=st1.u, u1c=st1.uc, h=h, gp=gp, u2=st2.u, lora_on=lora_on) if save else None)
 
     def _fwd_head(self, c, x, label):
         """Final LayerNorm, pooling and the head of the model's kind. -> (logits, emb, what the head backward needs)"""
@@ -795,7 +820,7 @@ class ViTRunner:
     def _bwd_ffn_lora(self, c, i, blk, st, dyb, gather):
         """FFN sub-layer with live adapters: y = x1 + drop(W2' h + b2), h = drop(gelu(W1' xn2 + b1)). The four LoRA gradients, then
         -> dxn2 (None for block 0, where the chain ends)."""
-        dt, D, r, s_lora, dev, p_drop, gv = c.dt, c.D, c.r, c.s_lora, c.dev, c.p_drop, c.gv
+        dt, D, r, dev, gv = c.dt, c.D, c.r, c.dev, c.gv
         l1, l2 = blk.l1, blk.l2
         mlp = l1.weight.shape[0]
         if not st["lora_on"]:
@@ -807,49 +832,34 @@ class ViTRunner:
             xn2, h, gp, u1, u2 = st["xn2"], st["h"], st["gp"], st["u1"], st["u2"]
         u1c = None if gather else st.get("u1c")      # the compact [M, 16] form of u1 (16-bit modes, full-size blocks)
         Mrows = dyb.shape[0]
-        ink = self.lora_in_kernel(dt, Mrows, mlp)       # FFN2-dX (N = mlp)
-        ink1 = self.lora_in_kernel(dt, Mrows, D)        # FFN1-dX (N = dim)
-        epi_mul = L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL      # g' as the 8-bit code of the forward (decode scale from p_drop)
-        v2 = torch.empty(Mrows, PADK, device=dev, dtype=dt)
+        # FFN2-dX -> da = (dy W2' ) * g', with v2 = s*dy*B2 (g' possibly as the 8-bit code of the forward: decode scale from p_drop)
+        s2 = self._lora_project(c, dyb, self.ffn_packs(i, 2, l2, dt), "dx", mlp)
         da = torch.empty(Mrows, mlp, device=dev, dtype=dt)
-        fused_grads = ink and FUSE_LORA_GRAD and Mrows >= INK_MIN_ROWS      # the gradient-fused epilogue lives on the 8-phase kernel
+        w2t = self.wT(f"w2_{i}", l2.weight, dt)
+        fused_grads = s2.ink and FUSE_LORA_GRAD and Mrows >= INK_MIN_ROWS      # the gradient-fused epilogue lives on the 8-phase kernel
         if fused_grads:
-            # v2 = s*dy*B2 is produced inside the dX GEMM, and the two gradient reductions that contract over the rows of its
-            # [M, mlp] tiles (dB1 from the da it produces, dA2 from h and the v2 it holds) ride in its epilogue
-            ops.gemm_nt_lora_mulgrad(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
-                                     self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, gp,
-                                     (u1c if u1c is not None else u1), gv[id(l1.lora_B)], (r, 1), h, gv[id(l2.lora_A)], (1, mlp), r, tag="ffn2dx", p_drop=p_drop,
-                                     gscale=c.gscale)
-        elif ink:    # v2 = s*dy*B2 is produced inside the dX GEMM
-            ops.gemm_nt_lora(dyb, self.wT(f"w2_{i}", l2.weight, dt), self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows16", dt),
-                             self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols32", dt), s_lora, v2, da, epilogue=epi_mul, aux=gp, p_drop=p_drop)
+            # the two gradient reductions that contract over the rows of the [M, mlp] tiles (dB1 from the da the GEMM produces, dA2 from
+            # h and the v2 it holds) ride in its epilogue
+            self._lora_finish(c, s2, w2t, da, dict(tag="ffn2dx", p_drop=c.p_drop, gscale=c.gscale),
+                              mulgrad=(gp, u1c if u1c is not None else u1, gv[id(l1.lora_B)], (r, 1), h, gv[id(l2.lora_A)], (1, mlp), r))
         else:
-            c.gemm(dyb, self.lora_pack(f"B2_{i}", l2.lora_B, "BT_rows", dt), v2, alpha=s_lora)
-            c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=epi_mul, A2=v2,
-                        W2=self.lora_pack(f"A2_{i}", l2.lora_A, "AT_cols", dt), aux=gp, p_drop=p_drop)
+            self._lora_finish(c, s2, w2t, da, dict(epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp, p_drop=c.p_drop))
         self._lgrad(c, dyb, u2, gv[id(l2.lora_B)], r, 1, r)                        # dB2[c, j]
         if not fused_grads:
-            self._lgrad(c, h, v2, gv[id(l2.lora_A)], 1, mlp, r)                    # dA2[j, hid]
-        v1 = torch.empty(Mrows, PADK, device=dev, dtype=dt)
-        dxn2 = None
-        if ink1 and i > 0:   # v1 = s*da*B1 is produced inside the FFN1-dX GEMM
-            dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
-            ops.gemm_nt_lora(da, self.wT(f"w1_{i}", l1.weight, dt), self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows16", dt),
-                             self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols32", dt), s_lora, v1, dxn2)
-        else:
-            c.gemm(da, self.lora_pack(f"B1_{i}", l1.lora_B, "BT_rows", dt), v1, alpha=s_lora)
+            self._lgrad(c, h, s2.u, gv[id(l2.lora_A)], 1, mlp, r)                  # dA2[j, hid]
+        # FFN1-dX with v1 = s*da*B1. The in-kernel form makes v1 in the dX launch itself, so that launch goes in front of the reductions
+        # that read v1; in the K-segment form they (and the hook) run between the two halves. Block 0 needs v1 alone: K-segment form.
+        s1 = self._lora_project(c, da, self.ffn_packs(i, 1, l1, dt), "dx", D, in_kernel_ok=i > 0)
+        finish = lambda: self._lora_finish(c, s1, self.wT(f"w1_{i}", l1.weight, dt), torch.empty(Mrows, D, device=dev, dtype=dt), {})
+        dxn2 = finish() if s1.ink else None
         if not fused_grads:
             self._lgrad(c, da, u1, gv[id(l1.lora_B)], r, 1, r)                     # dB1[hid, j]
-        self._lgrad(c, xn2, v1, gv[id(l1.lora_A)], 1, D, r)                        # dA1[j, c]
+        self._lgrad(c, xn2, s1.u, gv[id(l1.lora_A)], 1, D, r)                      # dA1[j, c]
         self._grads_done(c, i)
         if i == 0:
             self._flush(c)
             return None
-        if dxn2 is None:
-            dxn2 = torch.empty(Mrows, D, device=dev, dtype=dt)
-            c.gemm(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2, A2=v1,
-                        W2=self.lora_pack(f"A1_{i}", l1.lora_A, "AT_cols", dt))
-        return dxn2
+        return dxn2 if s1.ink else finish()
 
     def _bwd_ffn_frozen(self, c, i, blk, st, dyb, gather):
         """FFN sub-layer without live adapters (attention site): dX only. -> dxn2"""
@@ -899,9 +909,8 @@ class ViTRunner:
         """QKV projection with the q / k / v adapters (attention site): their gradients, then -> dxn1 with the adapter segment (None for
         block 0, where the chain ends). Same kernels as the FFN-site path."""
         dt, D, r, ml = c.dt, c.D, c.r, blk.qkv_lora
-        qo = self.qkv_lora_ops(i, ml, dt)
-        v = torch.empty(c.M, PADK, device=c.dev, dtype=dt)
-        c.gemm(dqkv, qo["BblkT"], v, alpha=c.s_lora)                      # v[:, g*r+j] = s * dqkv_g . B_g[:, j]
+        sq = self._lora_project(c, dqkv, self.qkv_lora_ops(i, ml, dt).__getitem__, "dx", D, in_kernel_ok=False)
+        v = sq.u                                                                 # v[:, g*r+j] = s * dqkv_g . B_g[:, j]
         ng, inner = len(ml.enable_lora), c.H * 64
         gA, gB = c.gv[id(ml.lora_A)], c.gv[id(ml.lora_B)]
         for g in range(ng):
@@ -910,6 +919,4 @@ class ViTRunner:
         self._grads_done(c, i)
         if i == 0:
             return None
-        dxn1 = torch.empty(c.M, D, device=c.dev, dtype=dt)
-        c.gemm(dqkv, self.wT(f"qkv{i}", blk.qkv_w, dt), dxn1, A2=v, W2=qo["AT"])
-        return dxn1
+        return self._lora_finish(c, sq, self.wT(f"qkv{i}", blk.qkv_w, dt), torch.empty(c.M, D, device=c.dev, dtype=dt), {})

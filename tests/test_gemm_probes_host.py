@@ -230,3 +230,37 @@ def test_tile_choice_names_every_table_row_and_follows_the_documented_rule():
     lib = L.load()
     assert lib.gsl_gemm_tile_choice(0, 64, 64, L.BF16, 0, 0) == -1 and lib.gsl_gemm_tile_choice(64, 64, 64, L.F32, 0, 1) == -1
     assert lib.gsl_gemm_tile_choice(64, 64, 64, 7, 0, 0) == -1
+
+
+def test_runner_asks_the_library_which_rows_take_the_in_kernel_lora_form(monkeypatch):
+    """ViTRunner.lora_in_kernel asks gsl_gemm_tile_choice for the few-row case. The yardstick is the expression it held before, a
+    restatement of the tile rule with its own copies of the 256 and 128 tile sizes: same answer at every shape, dtype and rank, with the
+    few-row form on and off, and from the memo as from the first call."""
+    from gslora_hip import vit_runner as R
+
+    def old(runner, dtype, rows, N):
+        if dtype not in R.OP16 or runner._rank > 16:
+            return False
+        if rows >= R.INK_MIN_ROWS:
+            return True
+        if N is None or not R.INK_SMALL:
+            return False
+        t256 = ((rows + 255) // 256) * ((N + 255) // 256)
+        t128 = ((rows + 127) // 128) * ((N + 127) // 128)
+        return (rows < 1024 or t256 < 128) and t128 <= 256
+
+    runner = R.ViTRunner(None)
+    seen = set()
+    for ink_small in (True, False):
+        monkeypatch.setattr(R, "INK_SMALL", ink_small)
+        for rank in (8, 32):
+            runner._rank = rank
+            for dtype in (torch.bfloat16, torch.float16, torch.float32):
+                for rows in (1, 63, 64, 111, 1023, 1024, 4096, 8191, 8192, 33490):
+                    for N in (64, 128, 256, 512, 2048):
+                        for K in (128, 2048):      # (K picks among the three ring tiles only)
+                            for again in range(2):
+                                got = runner.lora_in_kernel(dtype, rows, N, K)
+                                assert got is old(runner, dtype, rows, N), (ink_small, rank, dtype, rows, N, K, again)
+                                seen.add(got)
+    assert seen == {True, False}
