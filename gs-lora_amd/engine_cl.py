@@ -5,7 +5,8 @@ libgslora_hip.so via gslora_hip.step.gs_lora_step. Differences that are delibera
   * one deferred host sync per display interval instead of >= 8 `.item()` per step (meter values
     are identical);
   * under torch.distributed (one process per GPU) the step is data-parallel (see gslora_hip/step.py);
-  * `train_one_epoch_regularzation` / `get_reg_loss` (EWC/MAS/L2 baselines) keep their names only;
+  * `get_reg_loss` (:435-460) is the quadratic regulariser on the HIP path (gslora_hip.step.ffn_reg_step is the step that uses it);
+    `train_one_epoch_regularzation` (the EWC/MAS/L2 epoch loop) keeps its name only;
   * `eval_data_per_class` is an addition: eval_data with the per-class table of the reference's test/test_own.py:99-144.
 """
 import os
@@ -276,8 +277,12 @@ def get_prototype_loss(output, labels, prototype_dict, distance="kl"):
     return proto_sum(output, labels, table) / output.shape[0]
 
 
-def get_reg_loss(*args, **kwargs):
-    raise NotImplementedError("EWC/MAS/L2 regularisation baselines are outside the GS-LoRA hot path")
+def get_reg_loss(model: torch.nn.Module, regularization_terms: dict, reg_lambda: float, device: torch.device):
+    """reg_lambda * sum over the terms of sum(importance[n] * (p - task_param[n]) ** 2) over the trainable parameters (reference
+    engine_cl.py:435-460), on the HIP path: one autograd node over gst_reg_quad_fwd / gst_reg_quad_bwd. A 0-dim zero when the terms are None.
+    The step that uses it is gslora_hip.step.ffn_reg_step; the epoch loop around it (train_one_epoch_regularzation) is not provided."""
+    from gslora_hip.step import reg_loss
+    return reg_loss(model, regularization_terms, reg_lambda, device)
 
 
 def train_one_epoch_regularzation(*args, **kwargs):

@@ -23,6 +23,11 @@ HEADERS = ["gsl_common.h", "gsl_h16.h", "exports.map", "gelu_g8_table.inc"]
 DEV_ONLY = ["gemm_dev_a.inc", "gemm_dev_b.inc", "gemm_dev_c.inc", "gemm_dev_launch.inc", "gemm_w4.inc", "gemm_o4.inc", "attention_dev_launch.inc"]
 OUT = os.path.join(HERE, "libgslora_hip.so")
 OUT_DEV = os.path.join(HERE, "libgslora_hip_dev.so")
+# the second product library (include/gslora_train.h, prefix gst_): the weight-gradient GEMM and the quadratic regulariser of the FFN-training
+# step. One translation unit, its own version script; built by build() with the first, opened only by a process that trains FFN weights.
+TRAIN_SOURCES = ["train.hip"]
+TRAIN_HEADERS = ["gsl_common.h", "exports_train.map"]
+OUT_TRAIN = os.path.join(HERE, "libgslora_train.so")
 
 
 def needs_build(dev=False):
@@ -35,10 +40,43 @@ def needs_build(dev=False):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def needs_build_train():
+    if not os.path.exists(OUT_TRAIN):
+        return True
+    t = os.path.getmtime(OUT_TRAIN)
+    inc = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+    deps = [os.path.join(CSRC, s) for s in TRAIN_SOURCES + TRAIN_HEADERS] + [os.path.join(inc, h) for h in ("gslora_hip.h", "gslora_train.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_train(force=False, verbose=True):
+    """libgslora_train.so: same flags as the product library, linked against csrc/exports_train.map."""
+    if not force and not needs_build_train():
+        return OUT_TRAIN
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objdir = os.path.join(HERE, "build", "train")
+    os.makedirs(objdir, exist_ok=True)
+    objs = []
+    for src in TRAIN_SOURCES:
+        obj = os.path.join(objdir, src.replace(".hip", ".o"))
+        objs.append(obj)
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-c", os.path.join(CSRC, src), "-o", obj]
+        if verbose:
+            print("[gslora_hip.build]", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports_train.map"), "-o", OUT_TRAIN] + objs
+    if verbose:
+        print("[gslora_hip.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return OUT_TRAIN
+
+
 def build(force=False, verbose=True, dev=False, defines=(), out=None, tag=None):
     """defines / out / tag: an A/B build of the product sources with extra -D flags into another file (tools/probes/, never loaded by
-    default: `GSLORA_HIP_LIB=<out> python bench.py`)."""
+    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so."""
     variant = out is not None
+    if not variant and not dev:
+        build_train(force=force, verbose=verbose)
     out = out or (OUT_DEV if dev else OUT)
     if not variant and not force and not needs_build(dev):
         return out

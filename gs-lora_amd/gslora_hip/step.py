@@ -234,6 +234,96 @@ def _head_trains(net):
     return bool(heads) and any(p.requires_grad for n, p in net.named_parameters() if n in heads)
 
 
+def _ffn_trains(net):
+    """An FFN weight or bias requires a gradient (HIP models only: names containing net.trainable_ffn, the reference's --only_ffn rule)."""
+    if not getattr(net, "trainable_ffn", ""):
+        return False
+    # (asked once per step by GraphedStep: the FFN modules' own four tensors, not a walk over every named parameter)
+    return any(p.requires_grad for _, ff in net.transformer.layers for lin in (ff.fn.fn.net[0], ff.fn.fn.net[3]) for p in (lin.weight, lin.bias))
+
+
+_FFN_ONE_PROCESS = ("trainable FFN weights (fn.fn.net, the --only_ffn baselines) are served by one process through ffn_reg_step: their "
+                    "gradients are not reduced across ranks and their step is not captured")
+
+
+class _RegQuad(torch.autograd.Function):
+    """reg_lambda * sum over terms and tensors of sum(importance * (p - task_param) ** 2) (reference engine_cl.py:449-459) as ONE autograd
+    node over gst_reg_quad_fwd / gst_reg_quad_bwd. entries: (p, task_param, importance or None) per term and trainable tensor."""
+
+    @staticmethod
+    def forward(ctx, entries, reg_lambda, *params):
+        from . import _lib_train as LT
+        dev = params[0].device
+        out = torch.zeros((), device=dev, dtype=torch.float32)
+        ws = torch.empty(max(LT.load().gst_reg_quad_ws_elems(p.numel()) for p in params), device=dev, dtype=torch.float32)
+        for k, (p, p0, om) in enumerate(entries):
+            LT.reg_quad_fwd(p.detach(), p0, om, out, accumulate=k > 0, ws=ws)
+        ctx.entries, ctx.reg_lambda, ctx.ids = entries, float(reg_lambda), [id(p) for p in params]
+        return out * float(reg_lambda)
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import _lib_train as LT
+        coef = (gout.detach().float() * ctx.reg_lambda).reshape(1).contiguous()      # a device float: upstream gradient times lambda
+        grads = {}
+        for p, p0, om in ctx.entries:
+            g = grads.get(id(p))
+            if g is None:
+                g = grads[id(p)] = torch.zeros(p.shape, device=p.device, dtype=torch.float32)
+            LT.reg_quad_bwd(p.detach(), p0, om, coef, g)
+        return (None, None) + tuple(grads.get(i) if need else None for i, need in zip(ctx.ids, ctx.needs_input_grad[2:]))
+
+
+def reg_loss(model, regularization_terms, reg_lambda, device):
+    """engine_cl.get_reg_loss (reference engine_cl.py:435-460): reg_lambda * sum_terms sum_{trainable p} sum(importance[n] * (p -
+    task_param[n]) ** 2), a 0-dim f32 tensor; a 0-dim zero when the terms are None. importance[n] may be None for the identity (L2)."""
+    zero = torch.tensor(0.0, device=device)
+    if regularization_terms is None:
+        return zero
+    net = model.module if isinstance(model, nn.DataParallel) else model
+    named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
+    entries = []
+    for term in regularization_terms.values():
+        imp, ref = term["importance"], term["task_param"]
+        for n, p in named:
+            om, p0 = imp[n], ref[n]
+            if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
+                raise RuntimeError(f"gs-lora_amd get_reg_loss: parameter {n!r} must be a contiguous f32 tensor on the GPU (no CPU fallback)")
+            if p0.shape != p.shape or (om is not None and om.shape != p.shape):
+                raise ValueError(f"get_reg_loss: importance / task_param of {n!r} do not have the parameter's shape")
+            entries.append((p, p0.detach().to(device=p.device, dtype=torch.float32).contiguous(),
+                            None if om is None else om.detach().to(device=p.device, dtype=torch.float32).contiguous()))
+    if not entries:
+        return zero
+    return _RegQuad.apply(entries, reg_lambda, *[p for _, p in named])
+
+
+def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, reg_lambda=0.0):
+    """One step of the regularised baselines on trainable FFN weights — the loop body of the reference's engine_cl.py:490-512: forward, mean
+    cross-entropy (and top-1), get_reg_loss, zero_grad, backward, optimizer.step(). The trainable parameters are whatever requires a gradient
+    under the reference's --only_ffn rule (train/train_own_forget_cl.py:432-439: names containing "fn.fn.net", and the `loss` head).
+    Returns a DEVICE tensor [loss_ce, loss_reg, loss_total, prec1 %] (no host sync). Single process, eager."""
+    if _world() > 1:
+        raise RuntimeError(f"gs-lora_amd: ffn_reg_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    _check_not_replicated(model)
+    net = model.module if isinstance(model, nn.DataParallel) else model
+    logits, _ = model(_model_input(net, x), y)
+    n = float(x.size(0))
+    if _plain_ce(criterion):
+        ce_sum, hits = losses.ce_sum_top1(logits, y)
+        loss_ce = ce_sum / n
+    else:
+        loss_ce = criterion(logits, y)
+        hits = losses.ce_sum_top1(logits.detach(), y)[1]
+    loss_reg = reg_loss(model, regularization_terms, reg_lambda, logits.device)
+    total = loss_reg + loss_ce
+    optimizer.zero_grad()
+    total.backward()
+    _arm_overflow_guard(net, optimizer)      # fp16: the FFN gradients came out of a loss-scaled backward
+    optimizer.step()
+    return torch.stack((loss_ce.detach(), loss_reg.detach(), total.detach(), hits * (100.0 / n)))
+
+
 def head_probe_step(model, optimizer, criterion, x, y):
     """One step of the linear probe — the loop body of the reference's train/backbone_forget_main.py:657-670: forward, mean cross-entropy,
     top-1, backward, optimizer.step(). The trainable parameters are whatever requires a gradient; with the head alone (the reference's rule,
@@ -257,8 +347,8 @@ def head_probe_step(model, optimizer, criterion, x, y):
     optimizer.zero_grad()
     loss.backward()
     bucket = net.runner().bucket if hasattr(net, "runner") else None
-    if bucket is not None and any(p.requires_grad for p in bucket.params):
-        _arm_overflow_guard(net, optimizer)      # LoRA trains too: its fp16 backward ran on loss-scaled gradients
+    if (bucket is not None and any(p.requires_grad for p in bucket.params)) or _ffn_trains(net):
+        _arm_overflow_guard(net, optimizer)      # LoRA (or the FFN weights) train too: their fp16 backward ran on loss-scaled gradients
     elif hasattr(optimizer, "overflow_guard"):
         optimizer.overflow_guard = None          # head alone: f32 arithmetic, no loss scale, nothing to guard
     optimizer.step()
@@ -280,6 +370,8 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
     _check_not_replicated(model)
     net = model.module if isinstance(model, nn.DataParallel) else model
     world = _world()
+    if _dp_active() and _ffn_trains(net):      # (before any launch)
+        raise RuntimeError(f"gs-lora_amd: the data-parallel gs_lora_step all-reduces the flat LoRA gradient bucket only; {_FFN_ONE_PROCESS}")
     if _dp_active() and _head_trains(net):      # (before any launch)
         raise RuntimeError("gs-lora_amd: the data-parallel gs_lora_step all-reduces the flat LoRA gradient bucket only; a trainable classifier "
                            "head (loss.weight / loss.bias) is served by one process (gs_lora_step eager, or head_probe_step)")
@@ -472,6 +564,8 @@ class GraphedStep:
         return gs_lora_step(self.model, self.optimizer, self.criterion, x_r, y_r, x_f, y_f, **kw)
 
     def __call__(self, x_r, y_r, x_f, y_f, **kw):
+        if _ffn_trains(self.net):
+            raise RuntimeError(f"gs-lora_amd: GraphedStep captures the LoRA-only step; {_FFN_ONE_PROCESS}")
         if _head_trains(self.net):      # (any other trainable frozen tensor is refused, with its own reason, by the model's forward)
             raise RuntimeError("gs-lora_amd: GraphedStep captures the LoRA-only step; a trainable classifier head (loss.weight / loss.bias) runs "
                                "through the eager gs_lora_step (cfg HIP_GRAPH=False) or head_probe_step")

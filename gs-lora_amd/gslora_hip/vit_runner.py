@@ -200,10 +200,11 @@ class _Pass:
     """What every step of one pass reads, computed once by the forward; the backward of the same pass goes on with it (`saved["ctx"]`)
     and adds its own state: the loss scale and its overflow guard, the gradient views, the deferred LoRA-gradient reductions."""
     __slots__ = ("sp", "dt", "xdt", "epi_res", "epi_patch", "B", "T", "D", "H", "M", "dev", "seed", "sflag", "p_drop", "p_emb", "r",
-                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending", "f32_mode")
+                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending", "f32_mode", "ffn_train", "wg_ws", "wgrads")
 
     def __init__(self, sp, dt, B, dev, training, seed, sflag, save, f32_mode=None):
         self.sp, self.dt, self.dev, self.seed, self.sflag, self.save = sp, dt, dev, seed, sflag, save
+        self.ffn_train = False      # the FFN weights train (save="ffn"): the backward forms their gradients with gst_wgrad, see ViTRunner.backward
         self.f32_mode = f32_mode if dt == torch.float32 else None      # "x3" (the 'fp32x3' mode): every GEMM of the pass multiplies on the bf16 matrix cores
         self.B, self.T, self.D, self.H, self.M = B, sp.num_tokens, sp.dim, sp.heads, B * sp.num_tokens
         self.p_drop = sp.dropout_p if training else 0.0
@@ -515,8 +516,10 @@ class ViTRunner:
         """img: [B, C, H, W], or a tuple of such batches that are processed as ONE batch (gs_lora_step hands over the remain and the
         forget batch this way: each is patchified into its row range of the token matrix, no concatenated image copy is made)."""
         head_only = save == "head"      # only the head's parameters train: nothing of the blocks is kept (see head_param_grads)
-        save = save is True
+        ffn_train = save == "ffn"       # the FFN weights (and possibly the head) train, no LoRA in the model: everything is kept
+        save = save is True or ffn_train
         c, parts, u8tab, label = self._fwd_prepare(img, label, save)
+        c.ffn_train = ffn_train
         sp = c.sp
         x = self._fwd_patch(c, parts, u8tab)
         stash = []
@@ -732,11 +735,15 @@ class ViTRunner:
         every block's attention needs its dqkv, and the chain stops after the LoRA gradients of block 0's projection."""
         c = saved["ctx"]
         sp, bucket = c.sp, self.bucket
-        if bucket is None:
+        if c.ffn_train:      # third configuration (no LoRA in the model): see _bwd_ffn_train. -> {id(parameter): its gradient}
+            bucket, c.wgrads, c.wg_ws = None, {}, self._wgrad_workspace(c, sp)
+        elif bucket is None:
             return
-        bucket.attach_grads()
+        else:
+            bucket.attach_grads()
         dx, dxb = self._bwd_head(c, saved, dlogits, demb)
-        c.gv = {id(p): g for p, g in zip(bucket.params, bucket.grad_views)}
+        if bucket is not None:
+            c.gv = {id(p): g for p, g in zip(bucket.params, bucket.grad_views)}
         c.pending = []      # deferred LoRA-gradient reductions (launch-bound regime): (Y, U, G, gsn, gsj, r, accumulate), operands kept alive
         nl = len(saved["layers"])
         for i in reversed(range(nl)):
@@ -748,9 +755,10 @@ class ViTRunner:
             # tail: the forward of this block already ran on the cls rows, every saved tensor behind the attention is [B, .]; otherwise
             # dx / dxb arrive compact ([B, D]) from the head backward and the cls rows of the dense saved tensors are gathered
             gather = sparse and not st["tail"]
-            dxn2 = (self._bwd_ffn_frozen if c.attn_site else self._bwd_ffn_lora)(c, i, blk, st, dxb, gather)
+            ffn_bwd = self._bwd_ffn_train if c.ffn_train else (self._bwd_ffn_frozen if c.attn_site else self._bwd_ffn_lora)
+            dxn2 = ffn_bwd(c, i, blk, st, dxb, gather)
             if dxn2 is None:
-                break   # FFN site: nothing below the layer-0 FFN input is trainable
+                break   # FFN site / trainable FFN weights: nothing below the layer-0 FFN input is trainable
             dx1, dx1b = self._bwd_ln2(c, i, blk, st, dxn2, dx, gather)
             del dxn2
             # ---- attention sub-layer: x1 = x + drop(Wo o + bo) -------------------------------------
@@ -770,6 +778,8 @@ class ViTRunner:
                                         p_drop=c.p_drop, seed=c.seed, site=(4 * (i - 1) + 2) | c.sflag,
                                         dres_cls_T=c.T if sparse else 0, gmax=c.gmax)      # after the cls-row-only block dx1 is compact [B, D]
             saved["layers"][i] = None   # free this layer's activations
+        if c.ffn_train:
+            return c.wgrads
         if not c.attn_site and not torch.cuda.is_current_stream_capturing():
             self.build_pack_tables(c.dt)    # every pack of the step is registered now: the next forward refreshes them in one launch
 
@@ -872,6 +882,40 @@ class ViTRunner:
         c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
                     p_drop=c.p_drop)
         dxn2 = torch.empty(dyb.shape[0], c.D, device=c.dev, dtype=dt)
+        c.gemm(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
+        return dxn2
+
+    def _wgrad_workspace(self, c, sp):
+        """One f32 workspace for every gst_wgrad of a backward pass: the largest gst_wgrad_ws_elems of its shapes (both FFN products, on all
+        M rows and on the B cls rows of the last block under pool='cls')."""
+        from . import _lib_train as LT
+        mlp = sp.blocks[0].l1.weight.shape[0]
+        rows = {c.M, c.B} if sp.pool == "cls" else {c.M}
+        n = max(LT.wgrad_ws_elems(m, a, b, c.dt) for m in rows for a, b in ((c.D, mlp), (mlp, c.D)))
+        return torch.empty(n, device=c.dev, dtype=torch.float32)
+
+    def _bwd_ffn_train(self, c, i, blk, st, dyb, gather):
+        """FFN sub-layer whose two linears train (no adapters): FFN2-dX as _bwd_ffn_frozen forms it, then the weight and bias gradients
+        dW2 = dyb^T h, db2 = colsum(dyb), dW1 = da^T xn2, db1 = colsum(da) (gst_wgrad, fresh f32 buffers in c.wgrads; fp16: the loss
+        scale is divided out), then FFN1-dX -> dxn2 (None for block 0, where the chain ends)."""
+        from . import _lib_train as LT
+        dt, D, l1, l2 = c.dt, c.D, blk.l1, blk.l2
+        mlp = l1.weight.shape[0]
+        if gather:
+            xn2, h, gp = _cls_rows(c, st["xn2"], D), _cls_rows(c, st["h"], mlp), _gp_rows(c, st["gp"], mlp)
+        else:
+            xn2, h, gp = st["xn2"], st["h"], st["gp"]
+        da = torch.empty(dyb.shape[0], mlp, device=c.dev, dtype=dt)
+        c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
+                    p_drop=c.p_drop)
+        for layer, Y, X in ((l2, dyb, h), (l1, da, xn2)):
+            dW = torch.empty(layer.weight.shape, device=c.dev, dtype=torch.float32)
+            db = torch.empty(layer.bias.shape, device=c.dev, dtype=torch.float32)
+            LT.wgrad(Y, X, dW, db, ws=c.wg_ws, gscale=c.gscale)
+            c.wgrads[id(layer.weight)], c.wgrads[id(layer.bias)] = dW, db
+        if i == 0:
+            return None
+        dxn2 = torch.empty(dyb.shape[0], D, device=c.dev, dtype=dt)
         c.gemm(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
         return dxn2
 

@@ -185,12 +185,15 @@ class _ViTFaceFn(torch.autograd.Function):
     bucket whose views are the parameters' .grad (same observable result as autograd accumulation, no per-tensor copies); the head's are
     freshly written buffers (gsl_head_wgrad) that autograd accumulates into .grad.
     mode True: the whole backward chain runs (LoRA, plus the head's one launch when it trains). mode "head" (no trainable LoRA parameter):
-    the forward keeps nothing of the blocks and the backward is that one launch."""
+    the forward keeps nothing of the blocks and the backward is that one launch. mode "ffn" (a model without LoRA whose FFN linears train,
+    the reference's --only_ffn): the parameters behind the head's are the FFN weights and biases, the backward chain forms their gradients
+    with gst_wgrad into fresh buffers that autograd accumulates into .grad, like the head's."""
 
     @staticmethod
     def forward(ctx, runner, img, label, mode, n_head, *params):
         logits, emb, saved = runner.forward(img, label, save=mode)
         ctx.runner, ctx.saved, ctx.mode, ctx.n_head, ctx.n = runner, saved, mode, n_head, len(params)
+        ctx.ffn_ids = [id(p) for p in params[n_head:]] if mode == "ffn" else None
         if logits is None:
             return emb
         return logits, emb
@@ -206,10 +209,14 @@ class _ViTFaceFn(torch.autograd.Function):
         head_grads = (None,) * ctx.n_head
         if ctx.n_head:      # d loss / d (loss.weight, loss.bias): demb (the prototype term) reaches the head's parameters through nothing
             head_grads = ctx.runner.head_param_grads(ctx.saved, dlogits, ctx.needs_input_grad[5:5 + ctx.n_head])
+        rest = (None,) * (ctx.n - ctx.n_head)
         if ctx.mode is True:
             ctx.runner.backward(ctx.saved, dlogits, demb)
+        elif ctx.mode == "ffn":
+            wg = ctx.runner.backward(ctx.saved, dlogits, demb)
+            rest = tuple(wg[i] if need else None for i, need in zip(ctx.ffn_ids, ctx.needs_input_grad[5 + ctx.n_head:]))
         ctx.saved = None
-        return (None,) * 5 + tuple(head_grads) + (None,) * (ctx.n - ctx.n_head)
+        return (None,) * 5 + tuple(head_grads) + rest
 
 
 # the speed mode a model starts in (GSLORA_DTYPE overrides): IEEE fp16 operands since round 5 — same kernels, bytes and MFMA rate as bf16,
@@ -281,6 +288,9 @@ class HipModelMixin:
     # names of the non-LoRA parameters that may train on the HIP path: the classifier head of ViT_face / ViTs_face (the linear probe of
     # train/backbone_forget_main.py:596-600, the baselines' --ffn_open), whose gradient is gsl_head_wgrad
     trainable_head = ()
+    # name fragment of the backbone weights that may train: the two FFN linears of every block, weight and bias — the reference's --only_ffn
+    # rule (train/train_own_forget_cl.py:432-439) — in a model built WITHOUT LoRA (lora_rank = 0); their gradients are gst_wgrad's
+    trainable_ffn = ""
     _frozen_note = ""
 
     def _hip_call(self, img, label):
@@ -288,17 +298,28 @@ class HipModelMixin:
         spec = self.hip_spec()
         lora_params = [p for blk in spec.blocks for p in blk.lora_params()] if spec.lora_rank > 0 else []
         grad_on = torch.is_grad_enabled()
-        head_params = []
+        head_params, ffn_params = [], []
         if grad_on:
             for n, p in self.named_parameters():
                 if not p.requires_grad or "lora_" in n:
                     continue
+                if self.trainable_ffn and self.trainable_ffn in n:
+                    if spec.lora_rank > 0:
+                        raise RuntimeError(f"gs-lora_amd {type(self).__name__}: parameter {n!r} requires a gradient, but this model holds LoRA adapters "
+                                           f"(lora_rank = {spec.lora_rank}): the FFN weights train only in a model built with lora_rank = 0 (the "
+                                           "reference's --only_ffn baselines); LoRA and FFN weights training together is not implemented")
+                    ffn_params.append(p)
+                    continue
                 if n not in self.trainable_head:
                     raise RuntimeError(f"gs-lora_amd {type(self).__name__}: parameter {n!r} requires a gradient, but the HIP path trains the LoRA "
                                        f"parameters{' and the classifier head (loss.weight, loss.bias)' if self.trainable_head else ''} only"
+                                       f"{' (and, in a model built with lora_rank = 0, the FFN linears: names containing fn.fn.net)' if self.trainable_ffn else ''}"
                                        f"{self._frozen_note}: call loralib.mark_only_lora_as_trainable(model) first, set requires_grad by name "
                                        "as train/backbone_forget_main.py:596-600 does, or run under torch.no_grad()")
                 head_params.append(p)
+        if ffn_params:      # the third backward configuration (ViTRunner.backward): needs logits or an embedding gradient like the LoRA one
+            out = _ViTFaceFn.apply(runner, img, label, "ffn", len(head_params), *head_params, *ffn_params)
+            return out if isinstance(out, tuple) else (None, out)
         lora_live = grad_on and any(p.requires_grad for p in lora_params)
         if lora_live or (head_params and label is not None):
             # (without a label there are no logits: the head's parameters take no part in the forward)
@@ -310,6 +331,7 @@ class HipModelMixin:
 
 class ViT_face(HipModelMixin, nn.Module):
     trainable_head = ("loss.weight", "loss.bias")
+    trainable_ffn = "fn.fn.net"
 
     def __init__(self, *, loss_type, GPU_ID, num_class, image_size, patch_size, dim, depth, heads, mlp_dim, pool="cls",
                  channels=3, dim_head=64, dropout=0.0, emb_dropout=0.0, lora_rank=8, lora_pos: str = "FFN"):

@@ -19,6 +19,7 @@ from .vit_face import DEFAULT_DTYPE, MIN_NUM_PATCHES, _HEADS, HipModelMixin, Tra
 
 class ViTs_face(HipModelMixin, nn.Module):
     trainable_head = ViT_face.trainable_head      # the same heads, the same gradient kernel
+    trainable_ffn = ViT_face.trainable_ffn        # ... and the same FFN linears under the same names
 
     def __init__(self, *, loss_type, GPU_ID, num_class, image_size, patch_size, ac_patch_size, pad, dim, depth, heads, mlp_dim,
                  pool="cls", channels=3, dim_head=64, dropout=0.0, emb_dropout=0.0, lora_rank=8):
