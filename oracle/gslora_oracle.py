@@ -26,8 +26,9 @@ COS_M = 0.35   # vit_face.py:158 CosFace m
 LN_EPS = 1e-5  # nn.LayerNorm default (vit_face.py:319, :499)
 
 
-def to_torch(state_np, requires_grad_lora=False):
-    st = {k: torch.tensor(v, dtype=torch.float32) for k, v in state_np.items()}
+def to_torch(state_np, requires_grad_lora=False, dtype=torch.float32):
+    """dtype: torch.float64 restates the same network in double precision (the reference of the large-row gradient tests)."""
+    st = {k: torch.tensor(v, dtype=dtype) for k, v in state_np.items()}
     if requires_grad_lora:
         for k in st:
             if "lora_" in k:
@@ -63,17 +64,18 @@ def merged_delta(A, B, r):
     return torch.bmm(B.view(ng, -1, r), A.view(ng, r, -1)).reshape(B.shape[0], A.shape[1])
 
 
-def vit_forward(st, img, label, cfg, merged=False, dropout_masks=None, dropout_p=0.0):
+def vit_forward(st, img, label, cfg, merged=False, dropout_masks=None, dropout_p=0.0, dtype=torch.float32):
     """ViT_face.forward (vit_face.py:523-548) with Transformer (:442-446), Attention
     (:358-379, scale = dim**-0.5 :346), FeedForward (:329-335, exact-erf GELU) and
     CosFace (:171-208). Dropout is the identity for parity runs (p = 0 / eval mode); dropout_p > 0 applies torch's own Bernoulli
     dropout at the reference's 19 sites (emb_dropout :537, to_out :353-356, FeedForward :329-335) — used only by bench.py's CPU
-    baseline, which times the step "as the reference trains" (dropout 0.1).
+    baseline, which times the step "as the reference trains" (dropout 0.1). dtype: what the image is cast to (the reference's
+    inputs.float()); torch.float64 with a to_torch(..., dtype=torch.float64) state runs the whole forward in double precision.
     Returns (logits|None, emb)."""
     dp = (lambda t: F.dropout(t, dropout_p, True)) if dropout_p > 0 else (lambda t: t)
     p, d, hds, r = cfg["patch_size"], cfg["dim"], cfg["heads"], cfg["lora_rank"]
     attn_lora = cfg.get("lora_pos", "FFN") == "Attention"
-    x = patchify(img.float(), p)
+    x = patchify(img.to(dtype), p)
     x = F.linear(x, st["patch_to_embedding.weight"], st["patch_to_embedding.bias"])
     b, n, _ = x.shape
     x = torch.cat((st["cls_token"].expand(b, -1, -1), x), dim=1)

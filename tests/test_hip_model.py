@@ -306,39 +306,12 @@ def test_dropout_grads_match_autograd_with_same_masks():
     seed = (r.drop_seed << 20) + 42
     (lo.square().mean() + em.sum()).backward()
     got = lora_grads(m)
-    # oracle with identical masks
-    B, T, D, mlp = 3, m.num_tokens, cfg["dim"], cfg["mlp_dim"]
+    # oracle with identical masks: the mask-injected forward of tests/large_row_reference.py (which knows the sites, and that the last
+    # block's counters index a compact [B, width] tensor: it runs on the cls rows only under pool='cls')
+    import large_row_reference as LR
     keep = lambda n, site: ops.dropout_mask(n, p, seed, site, "cuda").cpu().float() / (1 - p)
-
-    def keep_rows(i, width, site):
-        """Mask of a [B, T, width] activation behind the attention of block i. The last block runs on the cls rows only (pool='cls':
-        nothing else is consumed), so its dropout counters index a compact [B, width] tensor; the other rows never reach the output."""
-        if i < cfg["depth"] - 1:
-            return keep(B * T * width, site).reshape(B, T, width)
-        full = torch.ones(B, T, width)
-        full[:, 0] = keep(B * width, site).reshape(B, width)
-        return full
     st = O.to_torch(st_np, requires_grad_lora=True)
-    import torch.nn.functional as F
-    x = O.patchify(xr.cpu(), cfg["patch_size"])
-    x = F.linear(x, st["patch_to_embedding.weight"], st["patch_to_embedding.bias"])
-    x = torch.cat((st["cls_token"].expand(B, -1, -1), x), 1) + st["pos_embedding"][:, :T]
-    x = x * keep(B * T * D, 1_000_000).reshape(B, T, D)
-    rr = cfg["lora_rank"]
-    for i in range(cfg["depth"]):
-        a, f = f"transformer.layers.{i}.0.fn", f"transformer.layers.{i}.1.fn"
-        xn = F.layer_norm(x, (D,), st[f"{a}.norm.weight"], st[f"{a}.norm.bias"], 1e-5)
-        q, k, v = [t.reshape(B, T, cfg["heads"], 64).permute(0, 2, 1, 3) for t in F.linear(xn, st[f"{a}.fn.to_qkv.weight"]).chunk(3, -1)]
-        att = (torch.einsum("bhid,bhjd->bhij", q, k) * D ** -0.5).softmax(-1)
-        o = torch.einsum("bhij,bhjd->bhid", att, v).permute(0, 2, 1, 3).reshape(B, T, -1)
-        x = F.linear(o, st[f"{a}.fn.to_out.0.weight"], st[f"{a}.fn.to_out.0.bias"]) * keep_rows(i, D, 4 * i) + x
-        xn = F.layer_norm(x, (D,), st[f"{f}.norm.weight"], st[f"{f}.norm.bias"], 1e-5)
-        h = O.lora_linear(xn, st[f"{f}.fn.net.0.weight"], st[f"{f}.fn.net.0.bias"], st[f"{f}.fn.net.0.lora_A"], st[f"{f}.fn.net.0.lora_B"], rr, False)
-        h = F.gelu(h) * keep_rows(i, mlp, 4 * i + 1)
-        y = O.lora_linear(h, st[f"{f}.fn.net.3.weight"], st[f"{f}.fn.net.3.bias"], st[f"{f}.fn.net.3.lora_A"], st[f"{f}.fn.net.3.lora_B"], rr, False)
-        x = y * keep_rows(i, D, 4 * i + 2) + x
-    emb = F.layer_norm(x[:, 0], (D,), st["mlp_head.0.weight"], st["mlp_head.0.bias"], 1e-5)
-    logits = O.cosface(emb, st["loss.weight"], yr.cpu())
+    logits, emb, _ = LR.forward(st, xr.cpu(), yr.cpu(), cfg, keep=keep, dtype=torch.float32)
     assert (lo.detach().cpu() - logits.detach()).abs().max() < 1e-4
     names = [k for k in st if "lora_" in k]
     gr = torch.autograd.grad(logits.square().mean() + emb.sum(), [st[k] for k in names])
