@@ -28,6 +28,11 @@ OUT_DEV = os.path.join(HERE, "libgslora_hip_dev.so")
 TRAIN_SOURCES = ["train.hip"]
 TRAIN_HEADERS = ["gsl_common.h", "exports_train.map"]
 OUT_TRAIN = os.path.join(HERE, "libgslora_train.so")
+# the third product library (include/gslora_reg.h, prefix gsr_): importance accumulation, MAS's objective and the batched quadratic regulariser
+# of the L2 / EWC / MAS baselines. Made the way the second one is; opened only by a process that runs those baselines.
+REG_SOURCES = ["reg.hip"]
+REG_HEADERS = ["gsl_common.h", "exports_reg.map"]
+OUT_REG = os.path.join(HERE, "libgslora_reg.so")
 
 
 def needs_build(dev=False):
@@ -40,43 +45,64 @@ def needs_build(dev=False):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def needs_build_train():
-    if not os.path.exists(OUT_TRAIN):
+def _needs_build_side(out, sources, headers, header):
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT_TRAIN)
+    t = os.path.getmtime(out)
     inc = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
-    deps = [os.path.join(CSRC, s) for s in TRAIN_SOURCES + TRAIN_HEADERS] + [os.path.join(inc, h) for h in ("gslora_hip.h", "gslora_train.h")]
+    deps = [os.path.join(CSRC, s) for s in sources + headers] + [os.path.join(inc, h) for h in ("gslora_hip.h", header)]
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def needs_build_train():
+    return _needs_build_side(OUT_TRAIN, TRAIN_SOURCES, TRAIN_HEADERS, "gslora_train.h")
+
+
+def needs_build_reg():
+    return _needs_build_side(OUT_REG, REG_SOURCES, REG_HEADERS, "gslora_reg.h")
 
 
 def build_train(force=False, verbose=True):
     """libgslora_train.so: same flags as the product library, linked against csrc/exports_train.map."""
     if not force and not needs_build_train():
         return OUT_TRAIN
+    return _build_side(OUT_TRAIN, TRAIN_SOURCES, "exports_train.map", "train", verbose)
+
+
+def build_reg(force=False, verbose=True):
+    """libgslora_reg.so: same flags as the product library, linked against csrc/exports_reg.map."""
+    if not force and not needs_build_reg():
+        return OUT_REG
+    return _build_side(OUT_REG, REG_SOURCES, "exports_reg.map", "reg", verbose)
+
+
+def _build_side(out, sources, version_script, tag, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objdir = os.path.join(HERE, "build", "train")
+    objdir = os.path.join(HERE, "build", tag)
     os.makedirs(objdir, exist_ok=True)
     objs = []
-    for src in TRAIN_SOURCES:
+    for src in sources:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(obj)
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print("[gslora_hip.build]", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports_train.map"), "-o", OUT_TRAIN] + objs
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, version_script), "-o", out] + objs
     if verbose:
         print("[gslora_hip.build]", " ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    return OUT_TRAIN
+    return out
 
 
 def build(force=False, verbose=True, dev=False, defines=(), out=None, tag=None):
     """defines / out / tag: an A/B build of the product sources with extra -D flags into another file (tools/probes/, never loaded by
-    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so."""
+    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so and
+    libgslora_reg.so."""
     variant = out is not None
     if not variant and not dev:
         build_train(force=force, verbose=verbose)
+        build_reg(force=force, verbose=verbose)
     out = out or (OUT_DEV if dev else OUT)
     if not variant and not force and not needs_build(dev):
         return out

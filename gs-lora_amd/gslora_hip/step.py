@@ -302,6 +302,8 @@ def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, r
     """One step of the regularised baselines on trainable FFN weights — the loop body of the reference's engine_cl.py:490-512: forward, mean
     cross-entropy (and top-1), get_reg_loss, zero_grad, backward, optimizer.step(). The trainable parameters are whatever requires a gradient
     under the reference's --only_ffn rule (train/train_own_forget_cl.py:432-439: names containing "fn.fn.net", and the `loss` head).
+    regularization_terms: the reference's dict (get_reg_loss: two launches forward and one backward per term and tensor), None, or a
+    gslora_hip.reg.RegTerms prepared from such a dict (two launches forward and one backward in all, the same bits).
     Returns a DEVICE tensor [loss_ce, loss_reg, loss_total, prec1 %] (no host sync). Single process, eager."""
     if _world() > 1:
         raise RuntimeError(f"gs-lora_amd: ffn_reg_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
@@ -315,7 +317,11 @@ def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, r
     else:
         loss_ce = criterion(logits, y)
         hits = losses.ce_sum_top1(logits.detach(), y)[1]
-    loss_reg = reg_loss(model, regularization_terms, reg_lambda, logits.device)
+    if hasattr(regularization_terms, "loss") and not isinstance(regularization_terms, dict):
+        # a gslora_hip.reg.RegTerms: the same value and gradients from the batched kernels (its own reg_lambda; the argument is not read)
+        loss_reg = regularization_terms.loss(logits.device)
+    else:
+        loss_reg = reg_loss(model, regularization_terms, reg_lambda, logits.device)
     total = loss_reg + loss_ce
     optimizer.zero_grad()
     total.backward()
