@@ -33,6 +33,11 @@ OUT_TRAIN = os.path.join(HERE, "libgslora_train.so")
 REG_SOURCES = ["reg.hip"]
 REG_HEADERS = ["gsl_common.h", "exports_reg.map"]
 OUT_REG = os.path.join(HERE, "libgslora_reg.so")
+# the fourth product library (include/gslora_kd.h, prefix gsk_): the distillation + cross-entropy row loss and the batched parameter distance
+# of the SCRUB baseline. Made the way the third one is; opened only by a process that runs a SCRUB step.
+KD_SOURCES = ["kd.hip"]
+KD_HEADERS = ["gsl_common.h", "exports_kd.map"]
+OUT_KD = os.path.join(HERE, "libgslora_kd.so")
 
 
 def needs_build(dev=False):
@@ -62,6 +67,10 @@ def needs_build_reg():
     return _needs_build_side(OUT_REG, REG_SOURCES, REG_HEADERS, "gslora_reg.h")
 
 
+def needs_build_kd():
+    return _needs_build_side(OUT_KD, KD_SOURCES, KD_HEADERS, "gslora_kd.h")
+
+
 def build_train(force=False, verbose=True):
     """libgslora_train.so: same flags as the product library, linked against csrc/exports_train.map."""
     if not force and not needs_build_train():
@@ -74,6 +83,13 @@ def build_reg(force=False, verbose=True):
     if not force and not needs_build_reg():
         return OUT_REG
     return _build_side(OUT_REG, REG_SOURCES, "exports_reg.map", "reg", verbose)
+
+
+def build_kd(force=False, verbose=True):
+    """libgslora_kd.so: same flags as the product library, linked against csrc/exports_kd.map."""
+    if not force and not needs_build_kd():
+        return OUT_KD
+    return _build_side(OUT_KD, KD_SOURCES, "exports_kd.map", "kd", verbose)
 
 
 def _build_side(out, sources, version_script, tag, verbose):
@@ -97,12 +113,13 @@ def _build_side(out, sources, version_script, tag, verbose):
 
 def build(force=False, verbose=True, dev=False, defines=(), out=None, tag=None):
     """defines / out / tag: an A/B build of the product sources with extra -D flags into another file (tools/probes/, never loaded by
-    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so and
-    libgslora_reg.so."""
+    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so,
+    libgslora_reg.so and libgslora_kd.so."""
     variant = out is not None
     if not variant and not dev:
         build_train(force=force, verbose=verbose)
         build_reg(force=force, verbose=verbose)
+        build_kd(force=force, verbose=verbose)
     out = out or (OUT_DEV if dev else OUT)
     if not variant and not force and not needs_build(dev):
         return out

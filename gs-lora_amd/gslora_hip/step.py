@@ -330,6 +330,54 @@ def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, r
     return torch.stack((loss_ce.detach(), loss_reg.detach(), total.detach(), hits * (100.0 / n)))
 
 
+def scrub_step(student, teacher, optimizer, criterion, x, y, *, maximize, kd_T, sgda_gamma, sgda_alpha, dist=None):
+    """One iteration of either loop of the reference's baselines/SCRUBtrain.py on trainable FFN weights: the student's forward in its
+    current mode, the teacher's under torch.no_grad(), the distillation KL between the two (util/sgda_utils.py, DistillKL(kd_T)) and
+
+      maximize       loss = -kd + dist.loss()                                       (the max steps over the forget loader)
+      not maximize   loss = sgda_gamma * CE + sgda_alpha * kd + dist.loss()         (the min steps over the remain loader)
+
+    then zero_grad, one backward, optimizer.step(). The KL, the cross-entropy, their weighted sum and the gradient of that sum are
+    gslora_hip.kd.kd_ce (two launches forward, one backward); dist: a gslora_hip.kd.ParamDist over (student, its averaged copy) or None
+    (param_dist of the reference; with the default smoothing 0 it launches nothing). A criterion that is not plain nn.CrossEntropyLoss
+    keeps its semantics: CE comes from the criterion and kd_ce runs with c_ce = 0. One backward per optimizer step: the overflow guard the
+    optimizer reads is this backward's. Returns a DEVICE tensor [kd, ce, total] (ce is 0 on a max step; no host sync).
+    Single process, eager: a process group and GraphedStep are refused, as ffn_reg_step refuses them."""
+    if _world() > 1:
+        raise RuntimeError(f"gs-lora_amd: scrub_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    if isinstance(student, GraphedStep) or isinstance(optimizer, GraphedStep):
+        raise RuntimeError(f"gs-lora_amd: scrub_step is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+    _check_not_replicated(student)
+    net = student.module if isinstance(student, nn.DataParallel) else student
+    tnet = teacher.module if isinstance(teacher, nn.DataParallel) else teacher
+    if not getattr(net, "trainable_ffn", ""):
+        raise RuntimeError(f"gs-lora_amd: scrub_step trains the FFN linears of a ViT_face / ViTs_face built with lora_rank = 0 (the reference's "
+                           f"--only_ffn rule); {type(net).__name__} has no FFN weights that train on the HIP path")
+    if getattr(net, "lora_rank", 0) > 0:
+        raise RuntimeError(f"gs-lora_amd: scrub_step trains the FFN linears of a model built with lora_rank = 0 (the reference's --only_ffn rule); "
+                           f"this {type(net).__name__} holds LoRA adapters (lora_rank = {net.lora_rank})")
+    from . import kd as kdm
+    xin = _model_input(net, x)
+    logits, _ = student(xin, y)
+    with torch.no_grad():
+        t_logits, _ = teacher(_model_input(tnet, x), y)
+    if maximize:
+        kd, ce, total = kdm.kd_ce(logits, t_logits, None, kd_T, -1.0, 0.0)
+    elif _plain_ce(criterion):
+        kd, ce, total = kdm.kd_ce(logits, t_logits, y, kd_T, sgda_alpha, sgda_gamma)
+    else:      # exotic criterion: keep its semantics
+        kd, _, part = kdm.kd_ce(logits, t_logits, None, kd_T, sgda_alpha, 0.0)
+        ce = criterion(logits, y)
+        total = sgda_gamma * ce + part
+    if dist is not None and dist.p != 0.0:      # (smoothing 0, the reference's default: the term and its gradient are 0 — not one launch)
+        total = total + dist.loss()
+    optimizer.zero_grad()
+    total.backward()
+    _arm_overflow_guard(net, optimizer)      # fp16: the FFN gradients came out of a loss-scaled backward
+    optimizer.step()
+    return torch.stack((kd.detach(), ce.detach(), total.detach()))
+
+
 def head_probe_step(model, optimizer, criterion, x, y):
     """One step of the linear probe — the loop body of the reference's train/backbone_forget_main.py:657-670: forward, mean cross-entropy,
     top-1, backward, optimizer.step(). The trainable parameters are whatever requires a gradient; with the head alone (the reference's rule,
