@@ -38,6 +38,11 @@ OUT_REG = os.path.join(HERE, "libgslora_reg.so")
 KD_SOURCES = ["kd.hip"]
 KD_HEADERS = ["gsl_common.h", "exports_kd.map"]
 OUT_KD = os.path.join(HERE, "libgslora_kd.so")
+# the fifth product library (include/gslora_fd.h, prefix gsf_): the student-teacher row distance of the DER / DER++ and FDR baselines. Made the
+# way the fourth one is; opened only by a process that takes a DER or FDR step.
+FD_SOURCES = ["fd.hip"]
+FD_HEADERS = ["gsl_common.h", "exports_fd.map"]
+OUT_FD = os.path.join(HERE, "libgslora_fd.so")
 
 
 def needs_build(dev=False):
@@ -71,6 +76,10 @@ def needs_build_kd():
     return _needs_build_side(OUT_KD, KD_SOURCES, KD_HEADERS, "gslora_kd.h")
 
 
+def needs_build_fd():
+    return _needs_build_side(OUT_FD, FD_SOURCES, FD_HEADERS, "gslora_fd.h")
+
+
 def build_train(force=False, verbose=True):
     """libgslora_train.so: same flags as the product library, linked against csrc/exports_train.map."""
     if not force and not needs_build_train():
@@ -90,6 +99,13 @@ def build_kd(force=False, verbose=True):
     if not force and not needs_build_kd():
         return OUT_KD
     return _build_side(OUT_KD, KD_SOURCES, "exports_kd.map", "kd", verbose)
+
+
+def build_fd(force=False, verbose=True):
+    """libgslora_fd.so: same flags as the product library, linked against csrc/exports_fd.map."""
+    if not force and not needs_build_fd():
+        return OUT_FD
+    return _build_side(OUT_FD, FD_SOURCES, "exports_fd.map", "fd", verbose)
 
 
 def _build_side(out, sources, version_script, tag, verbose):
@@ -114,12 +130,13 @@ def _build_side(out, sources, version_script, tag, verbose):
 def build(force=False, verbose=True, dev=False, defines=(), out=None, tag=None):
     """defines / out / tag: an A/B build of the product sources with extra -D flags into another file (tools/probes/, never loaded by
     default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so,
-    libgslora_reg.so and libgslora_kd.so."""
+    libgslora_reg.so, libgslora_kd.so and libgslora_fd.so."""
     variant = out is not None
     if not variant and not dev:
         build_train(force=force, verbose=verbose)
         build_reg(force=force, verbose=verbose)
         build_kd(force=force, verbose=verbose)
+        build_fd(force=force, verbose=verbose)
     out = out or (OUT_DEV if dev else OUT)
     if not variant and not force and not needs_build(dev):
         return out

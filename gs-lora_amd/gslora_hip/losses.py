@@ -72,6 +72,46 @@ def ce_sum_top1_split(logits, labels, nr):
     return _RowSumSplit.apply(logits, labels, None, int(nr), ops.ce_fwd, ops.ce_bwd, (1, 3), "rf")
 
 
+class _CeSegments(torch.autograd.Function):
+    """ce_sum_top1 of several consecutive row segments of ONE logit tensor (gslora_hip.step.distill_step runs the forget batch, the remain
+    batch and DER++'s second remain batch as one forward). sizes: the segments' row counts, in order, covering the tensor. Outputs: (CE sum,
+    top-1 hits) per segment, in order. Backward writes every segment's rows of a single gradient buffer, as _RowSumSplit does for two."""
+
+    @staticmethod
+    def forward(ctx, x, labels, sizes):
+        x = x.contiguous().float()
+        labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+        ctx.save_for_backward(x, labels)
+        ctx.ranges, r0 = [], 0
+        for n in sizes:
+            ctx.ranges.append(slice(r0, r0 + n))
+            r0 += n
+        res = tuple(v for sl in ctx.ranges for v in ops.ce_fwd(x[sl], labels[sl]))
+        ctx.mark_non_differentiable(*res[1::2])
+        return res
+
+    @staticmethod
+    def backward(ctx, *gs):
+        x, labels = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        for k, sl in enumerate(ctx.ranges):
+            g = gs[2 * k]
+            if g is None:
+                dx[sl].zero_()
+            else:
+                ops.ce_bwd(x[sl], labels[sl], g.reshape(1).float().contiguous(), 1.0, dx[sl], False)
+        return dx, None, None
+
+
+def ce_sum_top1_segments(logits, labels, sizes):
+    """-> (CE sum, top-1 hits) of each of the consecutive row segments of `sizes` rows: 2 * len(sizes) 0-dim f32 device tensors. A segment
+    whose sum is not used gets a zero gradient."""
+    sizes = tuple(int(n) for n in sizes)
+    if not sizes or min(sizes) < 1 or sum(sizes) != logits.shape[0]:
+        raise ValueError(f"ce_sum_top1_segments: segments of {sizes} rows do not cover the {logits.shape[0]} rows of the logits")
+    return _CeSegments.apply(logits, labels, sizes)
+
+
 def proto_kl_sum(emb, labels, table):
     return _RowSum.apply(emb, labels, table, ops.proto_kl_fwd, ops.proto_kl_bwd, ())[0]
 

@@ -378,6 +378,97 @@ def scrub_step(student, teacher, optimizer, criterion, x, y, *, maximize, kd_T, 
     return torch.stack((kd.detach(), ce.detach(), total.detach()))
 
 
+DISTILL_METHODS = ("lwf", "der", "fdr")
+
+
+def distill_step(student, teacher, optimizer, criterion, x_f, y_f, x_r, y_r, *, method, lam, lam_aux=0.0, x_n=None, y_n=None):
+    """One iteration of the reference's baselines/Lwftrain.py, DERtrain.py or FDRtrain.py on trainable FFN weights. x_f, y_f: the forget
+    batch; x_r, y_r: the current remain batch; s: the student, t: the frozen teacher:
+
+      "lwf"   loss = CE(s(x_f), y_f) + lam * KD + lam_aux * CE(s(x_r), y_r)                      (Lwftrain.py:69-89)
+      "der"   loss = CE(s(x_f), y_f) + lam * ||emb_s(x_r) - emb_t(x_r)||_F^2                     (DERtrain.py:61-92)
+              with x_n, y_n (a second remain batch: DER++)  + lam_aux * CE(s(x_n), y_n)
+      "fdr"   loss = CE(s(x_f), y_f) + lam * mean_b ||logits_s(x_r)_b - logits_t(x_r)_b||_2      (FDRtrain.py:59-74)
+
+    LwF's KD is the reference's L_old_kd_loss AS IT SHIPS: it takes torch.log of a log_softmax (<= 0) and sets every NaN to 0, so for finite
+    logits of at least two classes its value is exactly 0.0 and its gradient exactly zero. The reference's
+    behaviour is reproduced, not the paper's: KD is reported as an exact 0, the teacher is NOT run, lam multiplies nothing; a model of fewer
+    than two classes is refused (the reference's value is NaN there).
+
+    The student runs ONE forward over the tuple (x_f, x_r[, x_n]); the teacher runs one forward on x_r under torch.no_grad() — without
+    labels for "der" (the embedding alone), with y_r for "fdr". The CE terms are the row-segment kernels over the fused logits
+    (losses.ce_sum_top1_split, losses.ce_sum_top1_segments), the distance is gslora_hip.fd.row_dist over the remain rows. A criterion that
+    is not plain nn.CrossEntropyLoss keeps its semantics through torch on the segments. Then zero_grad, one backward, optimizer.step().
+    Returns a DEVICE tensor [ce_f, reg, ce_aux, total] (no host sync): reg is the DER / FDR distance, an exact 0 for "lwf"; ce_aux is CE_r
+    for "lwf", CE_n for DER++, 0 otherwise. Single process, eager: a process group and GraphedStep are refused, as scrub_step refuses them."""
+    if _world() > 1:
+        raise RuntimeError(f"gs-lora_amd: distill_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    if isinstance(student, GraphedStep) or isinstance(optimizer, GraphedStep):
+        raise RuntimeError(f"gs-lora_amd: distill_step is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+    if method not in DISTILL_METHODS:
+        raise ValueError(f"distill_step: method must be one of {DISTILL_METHODS}, got {method!r}")
+    if (x_n is None) != (y_n is None) or (x_n is not None and method != "der"):
+        raise ValueError("distill_step: x_n and y_n (the second remain batch of DER++) are given together, and only with method 'der'")
+    _check_not_replicated(student)
+    net = student.module if isinstance(student, nn.DataParallel) else student
+    tnet = teacher.module if isinstance(teacher, nn.DataParallel) else teacher
+    if not getattr(net, "trainable_ffn", ""):
+        raise RuntimeError(f"gs-lora_amd: distill_step trains the FFN linears of a ViT_face / ViTs_face built with lora_rank = 0 (the reference's "
+                           f"--only_ffn rule); {type(net).__name__} has no FFN weights that train on the HIP path")
+    if getattr(net, "lora_rank", 0) > 0:
+        raise RuntimeError(f"gs-lora_amd: distill_step trains the FFN linears of a model built with lora_rank = 0 (the reference's --only_ffn rule); "
+                           f"this {type(net).__name__} holds LoRA adapters (lora_rank = {net.lora_rank})")
+    parts = [(x_f, y_f), (x_r, y_r)] + ([(x_n, y_n)] if x_n is not None else [])
+    sizes = [x.size(0) for x, _ in parts]
+    nf, nr = sizes[0], sizes[1]
+    xs = tuple(_model_input(net, x) for x, _ in parts)
+    if not (getattr(net, "accepts_batch_tuple", False) and all(x.shape[1:] == xs[0].shape[1:] and x.dtype == xs[0].dtype for x in xs)):
+        xs = torch.cat([x.float() for x in xs], 0)
+    y_all = torch.cat([y for _, y in parts], 0)
+    logits, emb = student(xs, y_all)
+    if method == "lwf" and logits.shape[1] < 2:
+        raise ValueError(f"distill_step: method 'lwf' needs num_class >= 2 (the reference's L_old_kd_loss is NaN for one class), got {logits.shape[1]}")
+    zero = torch.zeros((), device=logits.device, dtype=torch.float32)
+    plain = _plain_ce(criterion)
+    ce_n = None
+    if plain and len(parts) == 2:
+        ce_f_sum, _, ce_r_sum, _ = losses.ce_sum_top1_split(logits, y_all, nf)      # (the range in front is the forget batch here)
+        ce_f, ce_r = ce_f_sum / float(nf), ce_r_sum / float(nr)
+    elif plain:
+        ce_f_sum, _, _, _, ce_n_sum, _ = losses.ce_sum_top1_segments(logits, y_all, sizes)
+        ce_f, ce_r, ce_n = ce_f_sum / float(nf), None, ce_n_sum / float(sizes[2])
+    else:      # exotic criterion: keep its semantics
+        ce_f = criterion(logits[:nf], y_f)
+        ce_r = criterion(logits[nf:nf + nr], y_r) if method == "lwf" else None
+        if x_n is not None:
+            ce_n = criterion(logits[nf + nr:], y_n)
+    if method == "lwf":
+        reg, ce_aux = zero, ce_r
+        total = ce_f + lam_aux * ce_r
+    else:
+        from . import fd
+        with torch.no_grad():
+            if method == "der":
+                t_out = teacher(_model_input(tnet, x_r))
+                s_out = emb
+            else:
+                t_out, _ = teacher(_model_input(tnet, x_r), y_r)
+                s_out = logits
+        if s_out.dtype != torch.float32:
+            s_out = s_out.float()
+        reg, part = fd.row_dist(s_out, nf, nr, t_out.float(), "sq" if method == "der" else "rownorm", lam)
+        total = ce_f + part
+        ce_aux = zero
+        if ce_n is not None:
+            ce_aux = ce_n
+            total = total + lam_aux * ce_n
+    optimizer.zero_grad()
+    total.backward()
+    _arm_overflow_guard(net, optimizer)      # fp16: the FFN gradients came out of a loss-scaled backward
+    optimizer.step()
+    return torch.stack((ce_f.detach(), reg.detach(), ce_aux.detach(), total.detach()))
+
+
 def head_probe_step(model, optimizer, criterion, x, y):
     """One step of the linear probe — the loop body of the reference's train/backbone_forget_main.py:657-670: forward, mean cross-entropy,
     top-1, backward, optimizer.step(). The trainable parameters are whatever requires a gradient; with the head alone (the reference's rule,
