@@ -43,6 +43,11 @@ OUT_KD = os.path.join(HERE, "libgslora_kd.so")
 FD_SOURCES = ["fd.hip"]
 FD_HEADERS = ["gsl_common.h", "exports_fd.map"]
 OUT_FD = os.path.join(HERE, "libgslora_fd.so")
+# the sixth product library (include/gslora_at.h, prefix gsa_): the attention-transfer term of the LIRF baseline on the stream between the two
+# half networks. Made the way the fifth one is; opened only by a process that takes a LIRF step.
+AT_SOURCES = ["at.hip"]
+AT_HEADERS = ["gsl_common.h", "exports_at.map"]
+OUT_AT = os.path.join(HERE, "libgslora_at.so")
 
 
 def needs_build(dev=False):
@@ -80,6 +85,10 @@ def needs_build_fd():
     return _needs_build_side(OUT_FD, FD_SOURCES, FD_HEADERS, "gslora_fd.h")
 
 
+def needs_build_at():
+    return _needs_build_side(OUT_AT, AT_SOURCES, AT_HEADERS, "gslora_at.h")
+
+
 def build_train(force=False, verbose=True):
     """libgslora_train.so: same flags as the product library, linked against csrc/exports_train.map."""
     if not force and not needs_build_train():
@@ -108,6 +117,13 @@ def build_fd(force=False, verbose=True):
     return _build_side(OUT_FD, FD_SOURCES, "exports_fd.map", "fd", verbose)
 
 
+def build_at(force=False, verbose=True):
+    """libgslora_at.so: same flags as the product library, linked against csrc/exports_at.map."""
+    if not force and not needs_build_at():
+        return OUT_AT
+    return _build_side(OUT_AT, AT_SOURCES, "exports_at.map", "at", verbose)
+
+
 def _build_side(out, sources, version_script, tag, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build", tag)
@@ -130,13 +146,14 @@ def _build_side(out, sources, version_script, tag, verbose):
 def build(force=False, verbose=True, dev=False, defines=(), out=None, tag=None):
     """defines / out / tag: an A/B build of the product sources with extra -D flags into another file (tools/probes/, never loaded by
     default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so,
-    libgslora_reg.so, libgslora_kd.so and libgslora_fd.so."""
+    libgslora_reg.so, libgslora_kd.so, libgslora_fd.so and libgslora_at.so."""
     variant = out is not None
     if not variant and not dev:
         build_train(force=force, verbose=verbose)
         build_reg(force=force, verbose=verbose)
         build_kd(force=force, verbose=verbose)
         build_fd(force=force, verbose=verbose)
+        build_at(force=force, verbose=verbose)
     out = out or (OUT_DEV if dev else OUT)
     if not variant and not force and not needs_build(dev):
         return out

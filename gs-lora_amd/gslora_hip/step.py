@@ -469,6 +469,90 @@ def distill_step(student, teacher, optimizer, criterion, x_f, y_f, x_r, y_r, *, 
     return torch.stack((ce_f.detach(), reg.detach(), ce_aux.detach(), total.detach()))
 
 
+LIRF_AT_WEIGHT, LIRF_KP_WEIGHT, LIRF_PT_RE_WEIGHT, LIRF_REPLAY_WEIGHT = -300.0, 10.0, 0.05, 5.0      # baselines/LIRFtrain.py:147-153
+
+
+def lirf_step(student_low, deposit_low, teacher_low, teacher_up, optimizer, criterion, x_f, y_f, x_r, y_r, *, split, T, alpha,
+              _at_weight=LIRF_AT_WEIGHT):
+    """One iteration of the reference's baselines/LIRFtrain.py (:104-164) on trainable FFN weights. s: student_low, d: deposit_low,
+    t: teacher_low (ViT_face_low), U: teacher_up (ViT_face_up: frozen, shared); x_f, y_f: the forget batch; x_r, y_r: the remain batch;
+    a = alpha:
+
+      S = U(s(x_f), y_f)    Dp = U(d(x_f), y_f)    Tt = U(t(x_f), y_f)
+      CE     = (1 - a) * criterion(S, y_f)
+      AT     = at_loss(s(x_f), t(x_f))                                                            (gslora_hip.at, on the [B, T, D] mid stream)
+      KP     = a * T^2 * KL_batchmean(log_softmax(S[:, split:] / T), softmax(Tt[:, split:] / T))
+      PT_RE  = a * T^2 * KL_batchmean(log_softmax(Dp[:, :split] / T), softmax(Tt[:, :split] / T)) + (1 - a) * CE(Dp, y_f)
+      REPLAY = criterion(U(s(x_r), y_r), y_r)
+      total  = CE - 300 * AT + 10 * KP + 0.05 * PT_RE + 5 * REPLAY
+
+    The student and U run as ONE pass over the tuple (x_f, x_r) with one backward (vit_pytorch_face.vit_face.low_up_forward): the
+    gradient of AT enters at the boundary between the halves, and the overflow guard the optimizer reads is that one backward's. CE and
+    REPLAY are losses.ce_sum_top1_split over the fused logits, the two KL terms gslora_hip.kd.kd_ce on column ranges of the logits. A
+    criterion that is not plain nn.CrossEntropyLoss keeps its semantics through torch on the row ranges.
+
+    Two documented differences from the reference. Trainable set: the FFN linears of student_low (names containing fn.fn.net, the
+    reference's --only_ffn rule, models built with lora_rank = 0) — the reference's LIRF branch leaves all of student_low trainable, and
+    full-weight training is not on the HIP path. Deposit: the optimizer holds student_low alone and U is frozen, so PT_RE has no path to
+    an updated weight; here d runs under torch.no_grad(), PT_RE is a reported value and deposit_low receives no .grad (in the reference
+    its .grad accumulates and nothing reads it).
+
+    Returns a DEVICE tensor [CE, AT, KP, PT_RE, total, REPLAY], the order of the reference's meters (no host sync). Single process,
+    eager: a process group, GraphedStep, nn.DataParallel over several devices and a student that holds LoRA are refused."""
+    if _world() > 1:
+        raise RuntimeError(f"gs-lora_amd: lirf_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    if isinstance(student_low, GraphedStep) or isinstance(optimizer, GraphedStep):
+        raise RuntimeError(f"gs-lora_amd: lirf_step is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+    nets = []
+    for m in (student_low, deposit_low, teacher_low, teacher_up):
+        _check_not_replicated(m)
+        nets.append(m.module if isinstance(m, nn.DataParallel) else m)
+    s, d, t, U = nets
+    from vit_pytorch_face.vit_face import ViT_face_low, ViT_face_up, low_up_forward, low_up_pair
+    for m, cls, what in ((s, ViT_face_low, "student_low"), (d, ViT_face_low, "deposit_low"), (t, ViT_face_low, "teacher_low"),
+                         (U, ViT_face_up, "teacher_up")):
+        if not isinstance(m, cls):
+            raise RuntimeError(f"gs-lora_amd: lirf_step runs the ViT_face family's half networks; {what} must be a {cls.__name__}, got "
+                               f"{type(m).__name__}")
+    if s.lora_rank > 0:
+        raise RuntimeError(f"gs-lora_amd: lirf_step trains the FFN linears of a model built with lora_rank = 0 (the reference's --only_ffn rule); "
+                           f"this {type(s).__name__} holds LoRA adapters (lora_rank = {s.lora_rank})")
+    num_class = U.loss.weight.shape[0]
+    split = int(split)
+    if not 0 < split < num_class:
+        raise ValueError(f"lirf_step: split (cfg['PER_FORGET_CLS']) must cut the {num_class} classes in two non-empty ranges, got {split}")
+    from . import kd as kdm
+    nf, nr = x_f.size(0), x_r.size(0)
+    xf_in = _model_input(s, x_f)
+    with torch.no_grad():
+        mid_t = t(_model_input(t, x_f))
+        Tt, _ = U(mid_t, y_f)
+        Dp, _ = U(d(_model_input(d, x_f)), y_f)
+        Tt, Dp = Tt.float(), Dp.float()
+        kd_d = kdm.kd_ce(Dp[:, :split], Tt[:, :split], None, T, 1.0, 0.0)[0]
+        pt_re = alpha * kd_d + (1.0 - alpha) * (losses.ce_sum_top1(Dp, y_f)[0] / float(nf))
+    xs = (xf_in, _model_input(s, x_r))
+    if not all(x.shape[1:] == xs[0].shape[1:] and x.dtype == xs[0].dtype for x in xs):
+        xs = torch.cat([x.float() for x in xs], 0)
+    y_all = torch.cat((y_f, y_r), 0)
+    logits, _, at_value = low_up_forward(s, U, xs, y_all, at_images=nf, at_teacher=mid_t)
+    if _plain_ce(criterion):
+        ce_f_sum, _, ce_r_sum, _ = losses.ce_sum_top1_split(logits, y_all, nf)      # (the range in front is the forget batch here)
+        ce_f, replay = ce_f_sum / float(nf), ce_r_sum / float(nr)
+    else:      # exotic criterion: keep its semantics
+        ce_f, replay = criterion(logits[:nf], y_f), criterion(logits[nf:], y_r)
+    ce = (1.0 - alpha) * ce_f
+    # kd_ce's kd is KL * T^2 / B: KP = alpha * kd, and its part of the total, 10 * KP, is formed on the device with the gradient
+    kd_s, _, kp_part = kdm.kd_ce(logits[:nf, split:], Tt[:, split:], None, T, LIRF_KP_WEIGHT * alpha, 0.0)
+    total = ce + float(_at_weight) * at_value + kp_part + LIRF_PT_RE_WEIGHT * pt_re + LIRF_REPLAY_WEIGHT * replay
+    optimizer.zero_grad()
+    total.backward()
+    if hasattr(optimizer, "overflow_guard"):      # fp16: the FFN gradients came out of the pair's loss-scaled backward
+        optimizer.overflow_guard = low_up_pair(s, U).runner().overflow_guard()
+    optimizer.step()
+    return torch.stack((ce.detach(), at_value.detach(), alpha * kd_s.detach(), pt_re, total.detach(), replay.detach()))
+
+
 def head_probe_step(model, optimizer, criterion, x, y):
     """One step of the linear probe — the loop body of the reference's train/backbone_forget_main.py:657-670: forward, mean cross-entropy,
     top-1, backward, optimizer.step(). The trainable parameters are whatever requires a gradient; with the head alone (the reference's rule,

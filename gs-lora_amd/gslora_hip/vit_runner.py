@@ -108,10 +108,16 @@ class ModelSpec:
                     LN eps 1e-6, scale head_dim^-0.5, nn.Linear head with bias, the label argument is ignored.
       ViTs_face     (vit_pytorch_face/vits_face.py, reference vits_face.py:414-509): ViT_face with an overlapping patch stage —
                     nn.Unfold(patch_kernel, patch_stride, patch_pad) windows (gsl_unfold_patches) into the same Linear embedding, whose
-                    weight is zero-padded along K to a multiple of 64; num_tokens = 1 + the number of windows."""
+                    weight is zero-padded along K to a multiple of 64; num_tokens = 1 + the number of windows.
+      ViT_face_low / ViT_face_up (vit_pytorch_face/vit_face.py, reference :551-781), the two halves of a ViT_face for the LIRF baseline:
+                    the lower half ends in the stream (stream_out: no final LayerNorm, no head), the upper half starts from one
+                    (stream_in: no patch stage; block0 = the network-wide index of its first block, which the dropout sites keep). A
+                    training pass runs both as ONE spec — patch stage and lower blocks of the student, upper blocks and head of the
+                    upper module — with boundary = the index of the first upper block, whose saved input is the mid stream."""
     __slots__ = ("patch_size", "num_tokens", "dim", "heads", "attn_scale", "ln_eps", "dropout_p", "emb_dropout_p", "lora_rank",
                  "patch_w", "patch_is_conv", "patch_b", "cls", "pos", "blocks", "final_ln", "head_kind", "head_w", "head_b",
-                 "cos_s", "cos_m", "easy_margin", "lora_site", "pool", "patch_kernel", "patch_stride", "patch_pad", "image_size")
+                 "cos_s", "cos_m", "easy_margin", "lora_site", "pool", "patch_kernel", "patch_stride", "patch_pad", "image_size",
+                 "block0", "stream_in", "stream_out", "boundary", "dropout_p_up")
 
     def __init__(self, **kw):
         kw.setdefault("easy_margin", False)    # ArcFace only
@@ -121,6 +127,11 @@ class ModelSpec:
         kw.setdefault("image_size", None)      # (checked against the input on the unfold path)
         kw.setdefault("lora_site", "ffn")      # "ffn" (GS-LoRA) or "attention" (--lora_pos Attention ablation)
         kw.setdefault("pool", "cls")           # "cls" (token 0) or "mean" (mean over the tokens, vit_face.py:540)
+        kw.setdefault("block0", 0)             # network-wide index of blocks[0] (ViT_face_up: depth // 2)
+        kw.setdefault("stream_in", False)      # the input is the [B, T, D] stream in front of blocks[0], not images
+        kw.setdefault("stream_out", False)     # the output is the stream behind the last block: no final LayerNorm, no head
+        kw.setdefault("boundary", None)        # a lower + upper pair: index of the first upper block
+        kw.setdefault("dropout_p_up", None)    # .. and the dropout rate in force in the upper blocks (the upper module's own mode decides it)
         for k in self.__slots__:
             setattr(self, k, kw[k])
 
@@ -200,7 +211,7 @@ class _Pass:
     """What every step of one pass reads, computed once by the forward; the backward of the same pass goes on with it (`saved["ctx"]`)
     and adds its own state: the loss scale and its overflow guard, the gradient views, the deferred LoRA-gradient reductions."""
     __slots__ = ("sp", "dt", "xdt", "epi_res", "epi_patch", "B", "T", "D", "H", "M", "dev", "seed", "sflag", "p_drop", "p_emb", "r",
-                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending", "f32_mode", "ffn_train", "wg_ws", "wgrads")
+                 "attn_site", "s_lora", "eps", "save", "gscale", "gmax", "gv", "pending", "f32_mode", "ffn_train", "wg_ws", "wgrads", "p_up", "kb")
 
     def __init__(self, sp, dt, B, dev, training, seed, sflag, save, f32_mode=None):
         self.sp, self.dt, self.dev, self.seed, self.sflag, self.save = sp, dt, dev, seed, sflag, save
@@ -209,6 +220,7 @@ class _Pass:
         self.B, self.T, self.D, self.H, self.M = B, sp.num_tokens, sp.dim, sp.heads, B * sp.num_tokens
         self.p_drop = sp.dropout_p if training else 0.0
         self.p_emb = sp.emb_dropout_p if training else 0.0
+        self.p_up, self.kb = sp.dropout_p_up, sp.boundary      # a lower + upper pair: blocks kb .. drop at the upper module's rate, see pd()
         self.r, self.eps = sp.lora_rank, sp.ln_eps
         self.attn_site = self.r > 0 and sp.lora_site == "attention"
         self.s_lora = (1.0 / self.r) if self.r > 0 else 0.0
@@ -218,10 +230,18 @@ class _Pass:
         self.epi_res = _res_epilogue(self.xdt)
         self.epi_patch = (L.EPI_PATCH_F16 if xf16 else L.EPI_PATCH_BF16) if xbf else L.EPI_PATCH
 
+    def pd(self, i):
+        """The dropout rate of block i's three sites."""
+        return self.p_drop if (self.p_up is None or i < self.kb) else self.p_up
+
     def gemm(self, *a, **kw):
         """ops.gemm_nt in the pass's GEMM mode: every GEMM of the forward and the backward goes through here. (Attention, LayerNorm, head, losses,
         LoRA-gradient reductions and AdamW have no such mode: in 'fp32x3' they are the f32 kernels of 'fp32'.)"""
         return ops.gemm_nt(*a, f32_mode=self.f32_mode, **kw)
+
+
+def _ffn_requires_grad(blk):
+    return any(p.requires_grad for lin in (blk.l1, blk.l2) for p in (lin.weight, lin.bias))
 
 
 def _cls_rows(c, t, w):
@@ -521,10 +541,11 @@ class ViTRunner:
         c, parts, u8tab, label = self._fwd_prepare(img, label, save)
         c.ffn_train = ffn_train
         sp = c.sp
-        x = self._fwd_patch(c, parts, u8tab)
+        x = self._fwd_stream_in(c, parts[0]) if sp.stream_in else self._fwd_patch(c, parts, u8tab)
         stash = []
         for i, blk in enumerate(sp.blocks):
-            tail = TAIL_CLS and i == len(sp.blocks) - 1 and sp.pool == "cls"
+            # (a lower half hands every token on: its last block is never the cls-row-only one)
+            tail = TAIL_CLS and i == len(sp.blocks) - 1 and sp.pool == "cls" and not sp.stream_out
             xn, mean1, rstd1 = self._fwd_ln1(c, blk, x)
             qkv, q_cls, uq, hm = self._fwd_qkv(c, i, blk, x, xn, mean1, rstd1, tail)
             xn_keep = xn if (c.attn_site and save) else None
@@ -535,6 +556,11 @@ class ViTRunner:
                 st.update(x=x, mean1=mean1, rstd1=rstd1, qkv=qkv, qkv_hm=hm, o=o, lse=lse, x1=x1, xn=xn_keep, uq=uq, tail=tail, q_cls=q_cls)
                 stash.append(st)
             x = x2
+        if sp.stream_out:
+            if save or head_only:
+                raise RuntimeError(f"{type(self.model).__name__}: a lower half network keeps nothing for a backward of its own; a training pass "
+                                   "runs it together with the upper half (gslora_hip.step.lirf_step)")
+            return None, x.view(c.B, c.T, c.D), None
         logits, emb, head = self._fwd_head(c, x, label)
         if head_only:
             return logits, emb, dict(ctx=c, emb=emb, label=label, cos_y=head["cos_y"])
@@ -544,6 +570,8 @@ class ViTRunner:
         """Input validation, the uint8 / float decision with its value table, the dropout seed and the LoRA state of this pass.
         -> (pass context, image batches, value table or None, label as the head wants it)"""
         m = self.model
+        if getattr(m, "stream_in", False):      # ViT_face_up
+            return self._fwd_prepare_stream(img, label, save)
         raw = list(img) if isinstance(img, (tuple, list)) else [img]
         # uint8 batches of a model that was told how to normalise them (set_input_norm) stay bytes up to the patch gather, which looks
         # ToTensor() + Normalize() up in a [C, 256] table; any other input is a value cast, as the reference's inputs.float()
@@ -576,6 +604,30 @@ class ViTRunner:
         if c.r > 0 and not c.attn_site:
             self.refresh_lora_packs(c.dt)
         return c, parts, u8tab, label
+
+    def _fwd_prepare_stream(self, x, label, save):
+        """_fwd_prepare of an upper half network: the input is the [B, T, D] stream of the lower half."""
+        m = self.model
+        sp = m.hip_spec()
+        if not (torch.is_tensor(x) and x.dim() == 3 and tuple(x.shape[1:]) == (sp.num_tokens, sp.dim)
+                and x.dtype in (torch.float32, torch.float16, torch.bfloat16)):
+            raise ValueError(f"{type(m).__name__}: the input is the lower half's stream [B, {sp.num_tokens}, {sp.dim}] (f32 or a 16-bit stream), got "
+                             f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(m).__name__} (gs-lora_amd): the model runs only on a ROCm GPU through libgslora_hip.so; "
+                               "there is no CPU fallback. Move the model and inputs to 'cuda'.")
+        L.load()
+        if label is not None:
+            label = label.to(device=x.device, dtype=torch.int64).contiguous()
+        self.drop_calls += 1
+        seed, sflag = (self.drop_seed << 20) + self.drop_calls, 0
+        c = _Pass(sp, m.compute_dtype, x.shape[0], x.device, m.training, seed, sflag, save, getattr(m, "gemm_mode", None))
+        self.ensure_bucket(sp)
+        return c, [x], None, label
+
+    def _fwd_stream_in(self, c, x):
+        """The stream an upper half starts from, [M, D] in the pass's stream dtype (a copy only where the dtype or the layout differs)."""
+        return x.detach().to(c.xdt).contiguous().view(c.M, c.D)
 
     def _fwd_patch(self, c, parts, u8tab):
         """Patch stage: the patch gather (tiles, or ViTs_face's overlapping windows) and the embedding GEMM whose epilogue adds bias and
@@ -648,7 +700,7 @@ class ViTRunner:
             xres = x
         x1 = torch.empty(xres.shape[0], D, device=c.dev, dtype=c.xdt)
         c.gemm(o, self.w(f"wo{i}", blk.out.weight, c.dt), x1, epilogue=c.epi_res,
-                    bias=blk.out.bias.detach(), res=xres, p_drop=c.p_drop, seed=c.seed, site=(4 * i) | c.sflag)
+                    bias=blk.out.bias.detach(), res=xres, p_drop=c.pd(i), seed=c.seed, site=(4 * (i + c.sp.block0)) | c.sflag)
         return o, lse, x1
 
     def _fwd_ffn(self, c, i, blk, x1):
@@ -679,12 +731,12 @@ class ViTRunner:
         st1 = self._lora_project(c, xn2, pk1, "fwd", mlp, in_kernel_ok=Mr < INK_MIN_ROWS, u=u1_ln,
                                  compact=save and dt in OP16 and r <= 16 and Mr >= INK_MIN_ROWS)
         self._lora_finish(c, st1, self.w(f"w1_{i}", l1.weight, dt), h, dict(
-            epilogue=L.EPI_BIAS_GELU_G8 if gp8 else L.EPI_BIAS_GELU, bias=l1.bias.detach(), out2=gp, p_drop=c.p_drop, seed=c.seed,
-            site=(4 * i + 1) | c.sflag, tag="ffn1" if lora_on else None))
+            epilogue=L.EPI_BIAS_GELU_G8 if gp8 else L.EPI_BIAS_GELU, bias=l1.bias.detach(), out2=gp, p_drop=c.pd(i), seed=c.seed,
+            site=(4 * (i + c.sp.block0) + 1) | c.sflag, tag="ffn1" if lora_on else None))
         st2 = self._lora_project(c, h, pk2, "fwd", D)
         x2 = torch.empty(Mr, D, device=dev, dtype=c.xdt)
         self._lora_finish(c, st2, self.w(f"w2_{i}", l2.weight, dt), x2, dict(
-            epilogue=c.epi_res, bias=l2.bias.detach(), res=x1, p_drop=c.p_drop, seed=c.seed, site=(4 * i + 2) | c.sflag))
+            epilogue=c.epi_res, bias=l2.bias.detach(), res=x1, p_drop=c.pd(i), seed=c.seed, site=(4 * (i + c.sp.block0) + 2) | c.sflag))
         return x2, (dict(mean2=mean2, rstd2=rstd2, xn2=xn2, u1=st1.u, u1c=st1.uc, h=h, gp=gp, u2=st2.u, lora_on=lora_on) if save else None)
 
     def _fwd_head(self, c, x, label):
@@ -728,11 +780,13 @@ class ViTRunner:
         by_param = {id(sp.head_w): dW, id(sp.head_b): db}
         return tuple(by_param[id(p)] if w else None for p, w in zip(params, want))
 
-    def backward(self, saved, dlogits, demb):
+    def backward(self, saved, dlogits, demb, at=None):
         """Accumulates d(loss)/d(LoRA) into the flat gradient bucket (views are the params' .grad). One chain for both LoRA sites: with
         the adapters on the FFN it stops after the LoRA gradients of block 0's FFN; with the adapters on the QKV projection
         (--lora_pos Attention; reference vit_face.py:349-355 with loralib.MergedLinear) the FFN is a plain frozen sub-layer (dX only),
-        every block's attention needs its dqkv, and the chain stops after the LoRA gradients of block 0's projection."""
+        every block's attention needs its dqkv, and the chain stops after the LoRA gradients of block 0's projection.
+        at = (G, coef) (a lower + upper pair, sp.boundary = k): the attention-transfer term's gradient coef * G[b, d] * x[b, t, d] enters
+        at the boundary, see _inject_at."""
         c = saved["ctx"]
         sp, bucket = c.sp, self.bucket
         if c.ffn_train:      # third configuration (no LoRA in the model): see _bwd_ffn_train. -> {id(parameter): its gradient}
@@ -755,7 +809,9 @@ class ViTRunner:
             # tail: the forward of this block already ran on the cls rows, every saved tensor behind the attention is [B, .]; otherwise
             # dx / dxb arrive compact ([B, D]) from the head backward and the cls rows of the dense saved tensors are gathered
             gather = sparse and not st["tail"]
-            ffn_bwd = self._bwd_ffn_train if c.ffn_train else (self._bwd_ffn_frozen if c.attn_site else self._bwd_ffn_lora)
+            # trainable FFN weights: a block whose FFN tensors all stay frozen (the upper half of a lower + upper pair) takes the dX-only form
+            ffn_bwd = ((self._bwd_ffn_train if _ffn_requires_grad(blk) else self._bwd_ffn_frozen) if c.ffn_train
+                       else (self._bwd_ffn_frozen if c.attn_site else self._bwd_ffn_lora))
             dxn2 = ffn_bwd(c, i, blk, st, dxb, gather)
             if dxn2 is None:
                 break   # FFN site / trainable FFN weights: nothing below the layer-0 FFN input is trainable
@@ -774,14 +830,42 @@ class ViTRunner:
             else:
                 dxn1 = self._bwd_qkv_frozen(c, i, blk, st, d_o, sparse)
                 del d_o, dx1b
+            cls_T = c.T if sparse else 0      # after the cls-row-only block dx1 is compact [B, D]
+            if at is not None and i == sp.boundary:
+                dx1, cls_T = self._inject_at(c, st["x"], dx1, cls_T, at), 0
             dx, dxb = ops.layernorm_bwd(dxn1, st["x"], c.D, blk.ln1.weight.detach(), st["mean1"], st["rstd1"], dx1,
-                                        p_drop=c.p_drop, seed=c.seed, site=(4 * (i - 1) + 2) | c.sflag,
-                                        dres_cls_T=c.T if sparse else 0, gmax=c.gmax)      # after the cls-row-only block dx1 is compact [B, D]
+                                        p_drop=c.pd(i - 1), seed=c.seed, site=(4 * (i - 1) + 2) | c.sflag,
+                                        dres_cls_T=cls_T, gmax=c.gmax)
             saved["layers"][i] = None   # free this layer's activations
         if c.ffn_train:
             return c.wgrads
         if not c.attn_site and not torch.cuda.is_current_stream_capturing():
             self.build_pack_tables(c.dt)    # every pack of the step is registered now: the next forward refreshes them in one launch
+
+    def _inject_at(self, c, x, dx1, cls_T, at):
+        """The boundary of a lower + upper pair, block k = sp.boundary. x (block k's saved input) IS the student's mid stream, and through
+        the residual x1 = x + attn(LN1 x) the stream gradient dx1 reaches it unchanged: the attention-transfer term's gradient
+        coef * S * G[b, d] * x[b, t, d] (gsa_at_bwd; S: the loss scale of an fp16 pass, else 1) is added IN PLACE to dx1 on the forget rows
+        BEFORE LayerNorm 1's backward reads it as its residual input. That one kernel then writes dx = dx1 + LN1'(dxn1) and its
+        operand-format copy dxb (with block k-1's FFN2 dropout mask) from the same sum, and raises the overflow guard to the largest |dx|
+        it stores: both forms are consistent and the guard sees the gradient with the injected term. dx1's other reader (the out-proj dX
+        GEMM, through dx1b) has run by now. When block k is the cls-row-only last block (an upper half of one block) dx1 is compact
+        [B, D]: it is spread to the dense [M, D] rows first. -> the dense dx1"""
+        from . import at as AT
+        G, coef = at
+        if cls_T:
+            dense = torch.zeros(c.M, c.D, device=c.dev, dtype=dx1.dtype)
+            dense.view(c.B, c.T, c.D)[:, 0] = dx1
+            dx1 = dense
+        one = c.gscale[0:1] if c.gscale is not None else self._ones(c.dev)
+        AT.at_inject(dx1, x, G, coef, one, T=c.T)
+        return dx1
+
+    def _ones(self, dev):
+        o = self._wcache.get(("zeros", "one", dev))      # (kept by invalidate_operand_caches like the zero vectors)
+        if o is None:
+            o = self._wcache[("zeros", "one", dev)] = torch.ones(1, device=dev, dtype=torch.float32)
+        return o
 
     def _bwd_head(self, c, saved, dlogits, demb):
         """Head backward with the loss-scale / overflow-guard state of the pass. -> (dx, dxb): the stream gradient entering the last block,
@@ -805,7 +889,7 @@ class ViTRunner:
             margin = dict(head_kind="arcface", m=sp.cos_m, easy_margin=sp.easy_margin, cos_y=saved["cos_y"], label=saved["label"])
         return (ops.head_bwd_margin if margin else ops.head_bwd)(
             dlogits, demb, saved["x_last"], c.B, saved["Th"], c.D, sp.final_ln.weight.detach(), saved["meanh"], saved["rstdh"],
-            saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=c.p_drop, seed=c.seed,
+            saved["emb"], saved["Wn"], 1.0 if linear_head else sp.cos_s, dt, p_drop=c.pd(len(saved["layers"]) - 1), seed=c.seed,
             site=(4 * (len(saved["layers"]) - 1) + 2) | c.sflag, linear=linear_head, pool_mean=(sp.pool == "mean"),
             stream_dtype=dt if (dt in OP16 and GRAD_STREAM_BF16) else torch.float32,
             compact=(sp.pool == "cls"), gscale=c.gscale, target_exp=GRAD_TARGET_EXP, **margin)
@@ -872,15 +956,19 @@ class ViTRunner:
         return dxn2 if s1.ink else finish()
 
     def _bwd_ffn_frozen(self, c, i, blk, st, dyb, gather):
-        """FFN sub-layer without live adapters (attention site): dX only. -> dxn2"""
+        """FFN sub-layer without live adapters (attention site), or a frozen one among trainable FFN weights: dX only. -> dxn2 (None for
+        block 0 of a pass that trains FFN weights, where the chain ends)."""
         dt, l1, l2 = c.dt, blk.l1, blk.l2
-        if st["uq"] is None:
+        if c.ffn_train:
+            if i == 0:
+                return None
+        elif st["uq"] is None:
             raise RuntimeError("backward with merged LoRA weights is undefined (model.train() un-merges)")
         mlp = l1.weight.shape[0]
         gp = _gp_rows(c, st["gp"], mlp) if gather else st["gp"]
         da = torch.empty(dyb.shape[0], mlp, device=c.dev, dtype=dt)
         c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
-                    p_drop=c.p_drop)
+                    p_drop=c.pd(i))
         dxn2 = torch.empty(dyb.shape[0], c.D, device=c.dev, dtype=dt)
         c.gemm(da, self.wT(f"w1_{i}", l1.weight, dt), dxn2)
         return dxn2
@@ -907,7 +995,7 @@ class ViTRunner:
             xn2, h, gp = st["xn2"], st["h"], st["gp"]
         da = torch.empty(dyb.shape[0], mlp, device=c.dev, dtype=dt)
         c.gemm(dyb, self.wT(f"w2_{i}", l2.weight, dt), da, epilogue=L.EPI_MUL_G8 if gp.dtype == torch.uint8 else L.EPI_MUL, aux=gp,
-                    p_drop=c.p_drop)
+                    p_drop=c.pd(i))
         for layer, Y, X in ((l2, dyb, h), (l1, da, xn2)):
             dW = torch.empty(layer.weight.shape, device=c.dev, dtype=torch.float32)
             db = torch.empty(layer.bias.shape, device=c.dev, dtype=torch.float32)
@@ -921,7 +1009,7 @@ class ViTRunner:
 
     def _bwd_ln2(self, c, i, blk, st, dxn2, dx, gather):
         """LayerNorm 2 backward -> (dx1, dx1b): the stream gradient at x1 and its operand-format copy with the out-proj dropout mask."""
-        gamma, kw = blk.ln2.weight.detach(), dict(p_drop=c.p_drop, seed=c.seed, site=(4 * i) | c.sflag, gmax=c.gmax)
+        gamma, kw = blk.ln2.weight.detach(), dict(p_drop=c.pd(i), seed=c.seed, site=(4 * i) | c.sflag, gmax=c.gmax)
         if gather:   # compact in, compact out: the cls rows of x1 are T*D apart, the dropout counters are those of the dense tensor
             return ops.layernorm_bwd(dxn2, st["x1"], c.T * c.D, gamma, _cls_rows(c, st["mean2"].view(-1, 1), 1).view(-1),
                                      _cls_rows(c, st["rstd2"].view(-1, 1), 1).view(-1), dx, drop_row_stride=c.T * c.D, **kw)

@@ -13,6 +13,7 @@ There is no CPU fallback: calling the model on CPU tensors raises.
 """
 import math
 import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -332,6 +333,8 @@ class HipModelMixin:
 class ViT_face(HipModelMixin, nn.Module):
     trainable_head = ("loss.weight", "loss.bias")
     trainable_ffn = "fn.fn.net"
+    _transformer_up = False                              # Transformer(up=...): True in ViT_face_up
+    _transformer_depth = staticmethod(lambda depth: depth)      # blocks the module owns: depth // 2 in ViT_face_low
 
     def __init__(self, *, loss_type, GPU_ID, num_class, image_size, patch_size, dim, depth, heads, mlp_dim, pool="cls",
                  channels=3, dim_head=64, dropout=0.0, emb_dropout=0.0, lora_rank=8, lora_pos: str = "FFN"):
@@ -352,7 +355,8 @@ class ViT_face(HipModelMixin, nn.Module):
         self.patch_to_embedding = nn.Linear(patch_dim, dim)
         self.cls_token = nn.Parameter(torch.randn(1, 1, dim))
         self.dropout = nn.Dropout(emb_dropout)
-        self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout, lora_rank, lora_pos=lora_pos)
+        self.transformer = Transformer(dim, self._transformer_depth(depth), heads, dim_head, mlp_dim, dropout, lora_rank, up=self._transformer_up,
+                                       lora_pos=lora_pos)
         self.pool = pool
         self.to_latent = nn.Identity()
         self.mlp_head = nn.Sequential(nn.LayerNorm(dim))
@@ -416,16 +420,229 @@ class ViT_face(HipModelMixin, nn.Module):
         return emb if label is None else (logits, emb)
 
 
-def _not_in_scope(name, why):
-    class _Stub(nn.Module):
-        def __init__(self, *a, **k):
-            raise NotImplementedError(f"{name} is outside the GS-LoRA hot path covered by gs-lora_amd ({why})")
-    _Stub.__name__ = name
-    return _Stub
+_REQUIRED = object()      # default of the keywords the reference's half-network constructors require, see _check_required
+_HALF_REQUIRED = ("loss_type", "GPU_ID", "num_class", "image_size", "patch_size", "dim", "depth", "heads", "mlp_dim")
+# low -> {id(up): _LowUpPair}, up -> the pairs it serves: invalidate_operand_caches() of either half reaches the pair's runner. Weak keys: a
+# pair lives as long as its student.
+_PAIRS_OF_LOW = weakref.WeakKeyDictionary()
+_PAIRS_OF_UP = weakref.WeakKeyDictionary()
+_LIRF_HINT = ("the halves run standalone under torch.no_grad() only (evaluation, the teacher, the deposit network); a training pass runs "
+              "both halves as one, through gslora_hip.step.lirf_step")
 
 
-ViT_face_low = _not_in_scope("ViT_face_low", "LIRF baseline half-network, reference vit_face.py:551-781")
-ViT_face_up = _not_in_scope("ViT_face_up", "LIRF baseline half-network, reference vit_face.py:551-781")
+def _check_required(cls, given):
+    """The reference's ViT_face_low / ViT_face_up constructors have nine required keyword arguments. Here they carry a sentinel default
+    and are checked by hand, so that a call without them raises NotImplementedError — what the placeholder classes these replace raised
+    for any call, and what callers that probe for the LIRF baseline (and tests/test_host_logic.py) still expect of `ViT_face_low()`."""
+    missing = [k for k in _HALF_REQUIRED if given[k] is _REQUIRED]
+    if missing:
+        raise NotImplementedError(f"{cls.__name__} needs the keyword arguments of the reference's constructor (vit_face.py:551-781): missing "
+                                  f"{', '.join(missing)}")
+
+
+class _HalfMixin:
+    """What ViT_face_low and ViT_face_up share: the refusals of a standalone call and the reach of invalidate_operand_caches()."""
+
+    def _standalone(self, mask):
+        if mask is not None:
+            raise NotImplementedError("attention masks are never passed by the GS-LoRA engines")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError(f"gs-lora_amd {type(self).__name__}: called with gradients enabled and trainable parameters; {_LIRF_HINT}")
+
+    def invalidate_operand_caches(self):
+        super().invalidate_operand_caches()
+        pairs = (_PAIRS_OF_LOW.get(self) or {}).values() if isinstance(self, ViT_face_low) else list(_PAIRS_OF_UP.get(self) or ())
+        for pair in pairs:
+            pair.invalidate_operand_caches()
+
+
+class ViT_face_low(_HalfMixin, ViT_face):
+    """The lower half of a ViT_face for the LIRF baseline (reference vit_face.py:551-666): the patch stage and blocks 0 .. depth // 2 - 1;
+    forward(img) -> the stream [B, T, D] in the stream dtype of the compute mode (f32 in the fp32 modes). Parameter names are the
+    reference's: `transformer.layers.{0 .. depth // 2 - 1}` plus, unused, the final LayerNorm `mlp_head` and the head `loss`, so
+    load_state_dict(full_checkpoint, strict=False) fills it and reports the upper blocks alone as unexpected. img may be a tuple of
+    batches or uint8 (set_input_norm), as for ViT_face."""
+
+    _transformer_depth = staticmethod(lambda depth: depth // 2)
+
+    def __init__(self, *, loss_type=_REQUIRED, GPU_ID=_REQUIRED, num_class=_REQUIRED, image_size=_REQUIRED, patch_size=_REQUIRED,
+                 dim=_REQUIRED, depth=_REQUIRED, heads=_REQUIRED, mlp_dim=_REQUIRED, pool="cls", channels=3, dim_head=64, dropout=0.0,
+                 emb_dropout=0.0, lora_rank=8, lora_pos: str = "FFN"):
+        _check_required(type(self), locals())
+        if depth < 2:
+            raise NotImplementedError("gs-lora_amd ViT_face_low / ViT_face_up: depth must be at least 2 (depth // 2 lower blocks)")
+        super().__init__(loss_type=loss_type, GPU_ID=GPU_ID, num_class=num_class, image_size=image_size, patch_size=patch_size, dim=dim,
+                         depth=depth, heads=heads, mlp_dim=mlp_dim, pool=pool, channels=channels, dim_head=dim_head, dropout=dropout,
+                         emb_dropout=emb_dropout, lora_rank=lora_rank, lora_pos=lora_pos)
+        self.split = depth // 2
+
+    def hip_spec(self):
+        sp = super().hip_spec()
+        sp.final_ln, sp.head_w, sp.head_b, sp.stream_out = None, None, None, True
+        return sp
+
+    def forward(self, img, label=None, mask=None):
+        """:return: the stream behind block depth // 2 - 1, [B, T, D] — as the reference (:638-665); label is not used."""
+        self._standalone(mask)
+        return self.runner().forward(img, None, save=False)[1]
+
+
+class ViT_face_up(_HalfMixin, ViT_face):
+    """The upper half of a ViT_face for the LIRF baseline (reference vit_face.py:668-781): blocks depth // 2 .. depth - 1 of a full-depth
+    Transformer(up=True), then pooling, the final LayerNorm and the head; forward(x, label) -> (logits, emb), or emb without a label, from
+    the lower half's stream x [B, T, D] (f32 or the stream dtype of the compute mode). It owns, unused, the patch embedding, cls_token,
+    pos_embedding and the lower blocks, as the reference does: load_state_dict(full_checkpoint, strict=False) reports nothing unexpected.
+    The dropout sites keep the network-wide block indices."""
+
+    _transformer_up = True
+    stream_in = True
+
+    def __init__(self, *, loss_type=_REQUIRED, GPU_ID=_REQUIRED, num_class=_REQUIRED, image_size=_REQUIRED, patch_size=_REQUIRED,
+                 dim=_REQUIRED, depth=_REQUIRED, heads=_REQUIRED, mlp_dim=_REQUIRED, pool="cls", channels=3, dim_head=64, dropout=0.0,
+                 emb_dropout=0.0, lora_rank=8, lora_pos: str = "FFN"):
+        _check_required(type(self), locals())
+        if depth < 2:
+            raise NotImplementedError("gs-lora_amd ViT_face_low / ViT_face_up: depth must be at least 2 (depth // 2 lower blocks)")
+        super().__init__(loss_type=loss_type, GPU_ID=GPU_ID, num_class=num_class, image_size=image_size, patch_size=patch_size, dim=dim,
+                         depth=depth, heads=heads, mlp_dim=mlp_dim, pool=pool, channels=channels, dim_head=dim_head, dropout=dropout,
+                         emb_dropout=emb_dropout, lora_rank=lora_rank, lora_pos=lora_pos)
+        self.split = depth // 2
+
+    def hip_spec(self):
+        sp = super().hip_spec()
+        sp.blocks, sp.block0, sp.stream_in = sp.blocks[self.split:], self.split, True
+        return sp
+
+    def forward(self, x, label=None, mask=None):
+        """:return: (logits, emb) if label is given else emb — as the reference (:755-781)."""
+        self._standalone(mask)
+        logits, emb, _ = self.runner().forward(x, label, save=False)
+        return emb if label is None else (logits, emb)
+
+
+class _LowUpPair:
+    """A student ViT_face_low and a ViT_face_up as ONE model in front of a ViTRunner of its own: the patch stage and blocks [0, k) are the
+    student's, blocks [k, depth), the final LayerNorm and the head the upper module's. The runner's operand caches are keyed per site and
+    tagged with their parameters' (data_ptr, _version), so they serve the two modules' tensors like one model's."""
+    accepts_batch_tuple = True
+
+    def __init__(self, low, up):
+        for a in ("dim", "depth", "heads", "mlp_dim", "num_tokens", "patch_size", "attn_scale"):
+            if getattr(low, a) != getattr(up, a):
+                raise ValueError(f"ViT_face_low / ViT_face_up: the halves differ in {a} ({getattr(low, a)} against {getattr(up, a)})")
+        self._low, self.up = weakref.ref(low), up
+        self._runner = None
+
+    @property
+    def low(self):
+        low = self._low()
+        if low is None:
+            raise RuntimeError("ViT_face_low / ViT_face_up: the student's lower half no longer exists")
+        return low
+
+    def runner(self):
+        if self._runner is None:
+            self._runner = ViTRunner(self)
+        return self._runner
+
+    def invalidate_operand_caches(self):
+        if self._runner is not None:
+            self._runner.invalidate_operand_caches()
+
+    # ---- what ViTRunner reads of its model
+    compute_dtype = property(lambda self: self.low.compute_dtype)
+    gemm_mode = property(lambda self: self.low.gemm_mode)
+    input_norm = property(lambda self: self.low.input_norm)
+    training = property(lambda self: self.low.training)
+
+    def check_modes(self):
+        low, up = self.low, self.up
+        if low.compute_mode != up.compute_mode:
+            raise RuntimeError(f"ViT_face_low / ViT_face_up: one pass runs in one compute mode; the student's half is in {low.compute_mode!r}, "
+                               f"the upper half in {up.compute_mode!r} (set_compute_dtype)")
+
+    def hip_spec(self):
+        low, up = self.low, self.up
+        sp, su = ViT_face.hip_spec(low), ViT_face.hip_spec(up)
+        k = low.split
+        su.blocks = sp.blocks + su.blocks[k:]
+        su.boundary = k
+        su.patch_w, su.patch_b, su.cls, su.pos = sp.patch_w, sp.patch_b, sp.cls, sp.pos
+        # dropout: the lower blocks and the embedding follow the student's rate and mode (the pass's), the upper blocks the upper module's
+        # own — the reference's loop trains student_low.train() under teacher_up.eval()
+        su.dropout_p, su.emb_dropout_p = sp.dropout_p, sp.emb_dropout_p
+        su.dropout_p_up = up.dropout_p if up.training else 0.0
+        return su
+
+
+def low_up_pair(low, up):
+    """The pair object (and through it the runner) that serves this student and this upper half; made once per couple."""
+    pairs = _PAIRS_OF_LOW.setdefault(low, {})
+    pair = pairs.get(id(up))
+    if pair is None or pair.up is not up:
+        pair = pairs[id(up)] = _LowUpPair(low, up)
+        _PAIRS_OF_UP.setdefault(up, weakref.WeakSet()).add(pair)
+    return pair
+
+
+class _LowUpFn(torch.autograd.Function):
+    """One autograd node for up(low(img), label) with the attention-transfer term of the mid stream as a third output. The parameters
+    handed over are the student's trainable FFN tensors; their gradients come from ViTRunner.backward (gst_wgrad), where the gradient of
+    the third output enters at the boundary between the halves."""
+
+    @staticmethod
+    def forward(ctx, runner, img, label, at_images, at_teacher, *params):
+        from gslora_hip import at as AT
+        logits, emb, saved = runner.forward(img, label, save="ffn")
+        c = saved["ctx"]
+        G = None
+        if at_teacher is not None:
+            mid = saved["layers"][c.sp.boundary]["x"]      # block k's saved input IS the student's mid stream: no copy
+            at_value, G = AT.at_loss_value_and_table(mid, at_images, c.T, at_teacher.to(mid.dtype))
+        else:
+            at_value = torch.zeros((), device=c.dev, dtype=torch.float32)
+        ctx.runner, ctx.saved, ctx.G, ctx.ids = runner, saved, G, [id(p) for p in params]
+        return logits, emb, at_value
+
+    @staticmethod
+    def backward(ctx, dlogits, demb, dat):
+        if ctx.saved is None:
+            raise RuntimeError("ViT_face_low / ViT_face_up backward called twice (activations are released after the first pass)")
+        at = None
+        if ctx.G is not None and dat is not None:
+            at = (ctx.G, dat.detach().float().reshape(1).contiguous())      # a device float: the upstream gradient times the term's weight
+        wg = ctx.runner.backward(ctx.saved, dlogits, demb, at=at)
+        ctx.saved = ctx.G = None
+        return (None,) * 5 + tuple(wg.get(i) if need else None for i, need in zip(ctx.ids, ctx.needs_input_grad[5:]))
+
+
+def low_up_forward(low, up, img, label, at_images=0, at_teacher=None):
+    """up(low(img), label) as one pass with a backward: -> (logits, emb, at_value). img: a batch or a tuple of batches; at_teacher: the
+    teacher's mid stream [at_images, T, D] for the first at_images images, or None (at_value is then a constant 0). The trainable set is
+    the reference's --only_ffn rule on the student's half (names containing fn.fn.net) in models built with lora_rank = 0; every
+    parameter of the upper half is frozen. Used by gslora_hip.step.lirf_step."""
+    for m in (low, up):
+        if m.lora_rank > 0:
+            raise RuntimeError(f"gs-lora_amd {type(m).__name__}: a training pass over both halves trains the FFN linears of models built with "
+                               f"lora_rank = 0 (the reference's --only_ffn rule); this {type(m).__name__} holds LoRA adapters (lora_rank = "
+                               f"{m.lora_rank})")
+    params = []
+    for n, p in low.named_parameters():
+        if p.requires_grad:
+            if low.trainable_ffn not in n:
+                raise RuntimeError(f"gs-lora_amd ViT_face_low: parameter {n!r} requires a gradient, but the HIP path trains the FFN linears "
+                                   "(names containing fn.fn.net) of the student's half only; set requires_grad by that rule first")
+            params.append(p)
+    frozen = [n for n, p in up.named_parameters() if p.requires_grad]
+    if frozen:
+        raise RuntimeError(f"gs-lora_amd ViT_face_up: parameter {frozen[0]!r} requires a gradient, but the upper half is the frozen, shared "
+                           "network of the LIRF step")
+    if not params or not torch.is_grad_enabled():
+        raise RuntimeError(f"gs-lora_amd ViT_face_low: a pass over both halves is a training pass (trainable FFN weights, gradients enabled); "
+                           f"{_LIRF_HINT}")
+    pair = low_up_pair(low, up)
+    pair.check_modes()
+    return _LowUpFn.apply(pair.runner(), img, label, int(at_images), at_teacher, *params)
 
 
 def __getattr__(name):      # vit_face.ViTs_face keeps resolving: the overlapping-patch model lives in vits_face.py (as in the reference)
