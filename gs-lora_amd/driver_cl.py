@@ -34,6 +34,7 @@ from torch.utils.data import DataLoader, TensorDataset  # noqa: E402
 
 import engine_cl  # noqa: E402
 import loralib as lora  # noqa: E402
+from driver_common import geometry, task_classes  # noqa: E402
 from gslora_hip.optim import create_optimizer, create_scheduler  # noqa: E402
 from util.cal_norm import get_norm_of_lora  # noqa: E402
 from util.utils import AverageMeter, calculate_prototypes, count_trainable_parameters, perform_val, reinitialize_lora_parameters  # noqa: E402
@@ -263,8 +264,7 @@ def main(argv=None):
     args = get_args(argv)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
-    geo = (dict(image_size=48, patch_size=8, dim=128, depth=3, heads=2, mlp_dim=256) if args.small else
-           dict(image_size=112, patch_size=8, dim=512, depth=6, heads=8, mlp_dim=2048))
+    geo = geometry(args.small)
     out = args.outdir or tempfile.mkdtemp(prefix="gslora_cl_")
     order = list(range(args.num_class))                       # reference :198-204
     random.seed(args.seed)
@@ -282,12 +282,9 @@ def main(argv=None):
         model.set_input_norm("totensor")
     x_all, y_all = synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed, u8=args.u8_input)
     x_te, y_te = synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1, u8=args.u8_input)
-    num_first = args.num_class - args.per_forget_cls           # classes not yet forgotten after task 0
 
     def task_data(task_i, model):
-        en1 = num_first - task_i * args.per_forget_cls        # :539-545  (st1 = 0, st2 = en1)
-        en2 = en1 + args.per_forget_cls
-        remain_cls, forget_cls = order[:en1], order[en1:en2]
+        remain_cls, forget_cls = task_classes(order, args.num_class, args.per_forget_cls, task_i)      # :539-545
         gen = torch.Generator().manual_seed(args.seed + task_i)
         mk = lambda ds, bs, sh: DataLoader(ds, batch_size=bs, shuffle=sh, generator=gen if sh else None, drop_last=False)
         tr_f, tr_r = subset(x_all, y_all, forget_cls), subset(x_all, y_all, remain_cls)

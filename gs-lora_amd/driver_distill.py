@@ -19,24 +19,20 @@ weight stays frozen (DESIGN.md sections 9 and 9n). LwF's distillation term is th
 (baselines/Lwftrain.py), so an LwF run never runs its teacher.
 """
 import argparse
-import copy
-import json
 import os
-import random
 import sys
-import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import torch  # noqa: E402
-from torch.utils.data import DataLoader  # noqa: E402
 
 import engine_cl  # noqa: E402
-from driver_reg import mark_only_ffn_as_trainable  # noqa: E402
+from driver_common import (add_common_args, append_record, build_ffn_model, eval_cfg, eval_task, frozen_copy, geometry, meter_averages,  # noqa: E402
+                           outdir, synthetic_task_data)
 from gslora_hip.optim import create_optimizer  # noqa: E402
-from util.utils import AverageMeter, count_trainable_parameters  # noqa: E402
+from util.utils import AverageMeter  # noqa: E402
 
 NO_GPU = "gs-lora_amd driver_distill: no ROCm GPU is visible; the distillation baselines run on the HIP path, which has no CPU fallback"
 METHODS = ("lwf", "der", "derpp", "fdr")
@@ -57,38 +53,14 @@ def get_args(argv=None):
     p.add_argument("--DER_plus_lambda", default=0.1, type=float, help="lambda for DER_plus")
     p.add_argument("--FDR_lambda", default=0.1, type=float, help="lambda for FDR")
     p.add_argument("--epochs", default=1, type=int, help="epochs over the forget loader per task")
-    p.add_argument("--ffn_open", default=False, action="store_true", help="train the `loss` head too (train_own_forget_cl.py:426)")
-    p.add_argument("--only_ffn", default=True, action="store_true",
-                   help="always on: the FFN linears (names containing fn.fn.net) are the backbone weights that train on the HIP path")
-    p.add_argument("--num_class", type=int, default=100)
-    p.add_argument("--num_tasks", type=int, default=4)
-    p.add_argument("--per_forget_cls", type=int, default=20)
-    p.add_argument("--batch_size", type=int, default=48)
-    p.add_argument("--samples_per_class", type=int, default=8)
-    p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--weight_decay", type=float, default=0.05)
-    p.add_argument("--opt", default="adamw")
-    p.add_argument("--opt_eps", type=float, default=1e-8)
-    p.add_argument("--opt_betas", default=None)
-    p.add_argument("--dropout", type=float, default=0.1)
-    p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 | fp32 | fp32x3")
-    p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
-    p.add_argument("-n", "--net", default="VIT", choices=["VIT", "VITs"])
-    p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"])
-    p.add_argument("--outdir", default=None)
-    p.add_argument("--seed", type=int, default=1337)
+    add_common_args(p)
     args = p.parse_args(argv)
     if args.method == "lwf" and args.num_class < 2:
         p.error("--method lwf needs --num_class >= 2: the reference's L_old_kd_loss is NaN for one class")
     return args
 
 
-def make_teacher(model, dev):
-    """:440-443"""
-    teacher = copy.deepcopy(model).to(dev).eval()
-    for p in teacher.parameters():
-        p.requires_grad_(False)
-    return teacher
+make_teacher = frozen_copy      # :440-443
 
 
 def one_epoch(args, common, m):
@@ -111,15 +83,15 @@ def run_tasks(model, args, task_data, dev, out):
     """task_data(task_i) -> dict(loader_f, loader_r: the task's forget and remain training loaders, te_f, te_r: test loaders, info).
     -> report"""
     criterion = torch.nn.CrossEntropyLoss()
-    cfg = {"DATA_ROOT": "./data/synthetic/", "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net}
+    cfg = eval_cfg(out, args.net)
+    evaluate = lambda loader, tag: engine_cl.eval_data(model, loader, dev, tag)
     report = []
     path = os.path.join(out, "distill_report.jsonl")
     for task_i in range(args.num_tasks):
         td = task_data(task_i)
         teacher = make_teacher(model, dev)
         optimizer = create_optimizer(args, model)
-        forget_before = engine_cl.eval_data(model, td["te_f"], dev, f"forget-{task_i}-before")
-        remain_before = engine_cl.eval_data(model, td["te_r"], dev, f"remain-{task_i}-before")
+        forget_before, remain_before = eval_task(evaluate, td, task_i, "before")
         model.train()
         batch, best_h = 0, 0.0
         m = {k: AverageMeter() for k in METERS[args.method]}
@@ -129,60 +101,25 @@ def run_tasks(model, args, task_data, dev, out):
                           criterion=criterion, optimizer=optimizer, device=dev, epoch=epoch, batch=batch, task_i=task_i,
                           testloader_forget=td["te_f"], testloader_remain=td["te_r"], highest_H_mean=best_h, forget_acc_before=forget_before, cfg=cfg)
             batch, best_h = one_epoch(args, common, m)
-            epochs.append({k: (v.avg if v.count else None) for k, v in m.items()})
-        forget_after = engine_cl.eval_data(model, td["te_f"], dev, f"forget-{task_i}-after")
-        remain_after = engine_cl.eval_data(model, td["te_r"], dev, f"remain-{task_i}-after")
+            epochs.append(meter_averages(m))
+        forget_after, remain_after = eval_task(evaluate, td, task_i, "after")
         model.train()
         rec = dict(task=task_i, method=args.method, steps=batch, epochs=epochs, forget_before=forget_before, forget_after=forget_after,
                    remain_before=remain_before, remain_after=remain_after, **td.get("info", {}))
-        report.append(rec)
-        with open(path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        print(f"[task {task_i}] {args.method} steps={batch} forget {forget_before:.1f}->{forget_after:.1f}  remain {remain_before:.1f}->{remain_after:.1f}")
+        append_record(path, report, rec, f"{args.method} steps={batch}")
     return report
 
 
 def main(argv=None):
-    import driver_cl
-    from vit_pytorch_face import ViT_face, ViTs_face
     args = get_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError(NO_GPU)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
-    geo = (dict(image_size=48, patch_size=8, dim=128, depth=3, heads=2, mlp_dim=256) if args.small else
-           dict(image_size=112, patch_size=8, dim=512, depth=6, heads=8, mlp_dim=2048))
-    out = args.outdir or tempfile.mkdtemp(prefix="gslora_distill_")
-    os.makedirs(out, exist_ok=True)
-    kw = dict(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout, lora_rank=0, **geo)
-    model = ViTs_face(ac_patch_size=12, pad=4, **kw) if args.net == "VITs" else ViT_face(**kw)
-    names = mark_only_ffn_as_trainable(model, args.ffn_open)
-    print("trainable parameters:", count_trainable_parameters(model), f"({len(names)} tensors)")
-    model = model.to(dev).set_compute_dtype(args.dtype)
-    order = list(range(args.num_class))
-    random.seed(args.seed)
-    random.shuffle(order)
-    x_all, y_all = driver_cl.synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed)
-    x_te, y_te = driver_cl.synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1)
-    x_all, y_all, x_te, y_te = x_all.to(dev), y_all.to(dev), x_te.to(dev), y_te.to(dev)      # device-resident: the loaders index on the GPU
-    num_first = args.num_class - args.per_forget_cls
-
-    def subset(x, y, classes):
-        m = torch.isin(y, torch.tensor(classes, device=y.device))
-        return torch.utils.data.TensorDataset(x[m], y[m])
-
-    def task_data(task_i):
-        en1 = num_first - task_i * args.per_forget_cls
-        en2 = en1 + args.per_forget_cls
-        remain_cls, forget_cls = order[:en1], order[en1:en2]
-        gen = torch.Generator().manual_seed(args.seed + task_i)
-        mk = lambda ds, bs, sh: DataLoader(ds, batch_size=bs, shuffle=sh, generator=gen if sh else None, drop_last=False)
-        return dict(loader_f=mk(subset(x_all, y_all, forget_cls), args.batch_size, True),
-                    loader_r=mk(subset(x_all, y_all, remain_cls), args.batch_size, True),
-                    te_f=mk(subset(x_te, y_te, forget_cls), 5 * args.batch_size, False),
-                    te_r=mk(subset(x_te, y_te, remain_cls), 5 * args.batch_size, False), info=dict(forget_cls=forget_cls))
-
-    report = run_tasks(model, args, task_data, dev, out)
+    geo = geometry(args.small)
+    out = outdir(args, "gslora_distill_")
+    model = build_ffn_model(args, geo, dev)
+    report = run_tasks(model, args, synthetic_task_data(args, geo["image_size"], dev), dev, out)
     return report, out, model
 
 

@@ -17,19 +17,17 @@ reference's --only_ffn rule is ALWAYS applied to student_low: the two FFN linear
 (the reference's LIRF branch leaves all of student_low trainable; full-weight training is not on the HIP path: DESIGN.md section 9o).
 """
 import argparse
-import json
 import os
-import random
 import sys
-import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import torch  # noqa: E402
-from torch.utils.data import DataLoader  # noqa: E402
 
+from driver_common import (add_common_args, append_record, eval_cfg, eval_task, geometry, mark_only_ffn_as_trainable, meter_averages,  # noqa: E402
+                           model_keywords, outdir, synthetic_task_data)
 from gslora_hip.optim import create_optimizer  # noqa: E402
 from util.utils import AverageMeter, count_trainable_parameters  # noqa: E402
 
@@ -46,22 +44,7 @@ def get_args(argv=None):
     p.add_argument("--LIRF_alpha", default=0.1, type=float, help="lambda for LIRF")
     p.add_argument("--epochs", default=1, type=int, help="epochs over the forget loader per task")
     p.add_argument("--vit_depth", type=int, default=None, help="transformer depth (default 6, 3 with --small); the halves split at depth // 2")
-    p.add_argument("--num_class", type=int, default=100)
-    p.add_argument("--num_tasks", type=int, default=4)
-    p.add_argument("--per_forget_cls", type=int, default=20)
-    p.add_argument("--batch_size", type=int, default=48)
-    p.add_argument("--samples_per_class", type=int, default=8)
-    p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--weight_decay", type=float, default=0.05)
-    p.add_argument("--opt", default="adamw")
-    p.add_argument("--opt_eps", type=float, default=1e-8)
-    p.add_argument("--opt_betas", default=None)
-    p.add_argument("--dropout", type=float, default=0.1)
-    p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 | fp32 | fp32x3")
-    p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
-    p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"])
-    p.add_argument("--outdir", default=None)
-    p.add_argument("--seed", type=int, default=1337)
+    add_common_args(p, net=False, ffn=False)
     args = p.parse_args(argv)
     if not 0 < args.per_forget_cls < args.num_class:
         p.error("--per_forget_cls is the column at which LIRF cuts the logits: it must lie inside (0, num_class)")
@@ -72,9 +55,7 @@ def get_args(argv=None):
 
 def mark_student(student_low):
     """The reference's --only_ffn rule on the student's half: names containing fn.fn.net train. -> their names"""
-    for n, p in student_low.named_parameters():
-        p.requires_grad = "fn.fn.net" in n
-    return [n for n, p in student_low.named_parameters() if p.requires_grad]
+    return mark_only_ffn_as_trainable(student_low)
 
 
 def make_halves(kw, state, dev, dtype):
@@ -98,8 +79,7 @@ def run_tasks(kw, state, args, task_data, dev, out):
     """task_data(task_i) -> dict(loader_f, loader_r, te_f, te_r, info). state: the full ViT_face checkpoint. -> (report, the last student)"""
     from baselines.LIRFtrain import eval_data_LIRF, train_one_epoch_LIRF
     criterion = torch.nn.CrossEntropyLoss()
-    cfg = {"DATA_ROOT": "./data/synthetic/", "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": "VIT", "PER_FORGET_CLS": args.per_forget_cls,
-           "LIRF_T": args.LIRF_T, "LIRF_alpha": args.LIRF_alpha}
+    cfg = {**eval_cfg(out, "VIT"), "PER_FORGET_CLS": args.per_forget_cls, "LIRF_T": args.LIRF_T, "LIRF_alpha": args.LIRF_alpha}
     report, nets = [], None
     path = os.path.join(out, "lirf_report.jsonl")
     for task_i in range(args.num_tasks):
@@ -109,8 +89,8 @@ def run_tasks(kw, state, args, task_data, dev, out):
         names = mark_student(student)
         print("trainable parameters:", count_trainable_parameters(student), f"({len(names)} tensors)")
         optimizer = create_optimizer(args, student)
-        forget_before = eval_data_LIRF(student, up, td["te_f"], dev, f"forget-{task_i}-before")
-        remain_before = eval_data_LIRF(student, up, td["te_r"], dev, f"remain-{task_i}-before")
+        evaluate = lambda loader, tag: eval_data_LIRF(student, up, loader, dev, tag)
+        forget_before, remain_before = eval_task(evaluate, td, task_i, "before")
         batch, best_h = 0, 0.0
         m = {k: AverageMeter() for k in METERS}
         epochs = []
@@ -120,61 +100,29 @@ def run_tasks(kw, state, args, task_data, dev, out):
                                         best_h, cfg)
             batch, best_h = out_[0], out_[1]
             m = dict(zip(METERS, out_[2:]))
-            epochs.append({k: (v.avg if v.count else None) for k, v in m.items()})
-        forget_after = eval_data_LIRF(student, up, td["te_f"], dev, f"forget-{task_i}-after")
-        remain_after = eval_data_LIRF(student, up, td["te_r"], dev, f"remain-{task_i}-after")
+            epochs.append(meter_averages(m))
+        forget_after, remain_after = eval_task(evaluate, td, task_i, "after")
         student.train()
         rec = dict(task=task_i, method="lirf", steps=batch, epochs=epochs, forget_before=forget_before, forget_after=forget_after,
                    remain_before=remain_before, remain_after=remain_after, best_H_mean=best_h, **td.get("info", {}))
-        report.append(rec)
-        with open(path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        print(f"[task {task_i}] lirf steps={batch} forget {forget_before:.1f}->{forget_after:.1f}  remain {remain_before:.1f}->{remain_after:.1f}")
+        append_record(path, report, rec, f"lirf steps={batch}")
         # the next task starts from this task's student: its lower blocks replace the checkpoint's
         state = {**state, **{k: v.detach().clone() for k, v in student.state_dict().items() if k.startswith("transformer.layers.")}}
     return report, nets
 
 
 def main(argv=None):
-    import driver_cl
     from vit_pytorch_face import ViT_face
     args = get_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError(NO_GPU)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
-    geo = (dict(image_size=48, patch_size=8, dim=128, depth=3, heads=2, mlp_dim=256) if args.small else
-           dict(image_size=112, patch_size=8, dim=512, depth=6, heads=8, mlp_dim=2048))
-    if args.vit_depth is not None:
-        geo["depth"] = args.vit_depth
-    out = args.outdir or tempfile.mkdtemp(prefix="gslora_lirf_")
-    os.makedirs(out, exist_ok=True)
-    kw = dict(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout, lora_rank=0, **geo)
+    geo = geometry(args.small, args.vit_depth)
+    out = outdir(args, "gslora_lirf_")
+    kw = model_keywords(args, geo)
     state = {k: v.detach().clone() for k, v in ViT_face(**kw).state_dict().items()}      # stands for the pretrained checkpoint
-    order = list(range(args.num_class))
-    random.seed(args.seed)
-    random.shuffle(order)
-    x_all, y_all = driver_cl.synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed)
-    x_te, y_te = driver_cl.synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1)
-    x_all, y_all, x_te, y_te = x_all.to(dev), y_all.to(dev), x_te.to(dev), y_te.to(dev)      # device-resident: the loaders index on the GPU
-    num_first = args.num_class - args.per_forget_cls
-
-    def subset(x, y, classes):
-        m = torch.isin(y, torch.tensor(classes, device=y.device))
-        return torch.utils.data.TensorDataset(x[m], y[m])
-
-    def task_data(task_i):
-        en1 = num_first - task_i * args.per_forget_cls
-        en2 = en1 + args.per_forget_cls
-        remain_cls, forget_cls = order[:en1], order[en1:en2]
-        gen = torch.Generator().manual_seed(args.seed + task_i)
-        mk = lambda ds, bs, sh: DataLoader(ds, batch_size=bs, shuffle=sh, generator=gen if sh else None, drop_last=False)
-        return dict(loader_f=mk(subset(x_all, y_all, forget_cls), args.batch_size, True),
-                    loader_r=mk(subset(x_all, y_all, remain_cls), args.batch_size, True),
-                    te_f=mk(subset(x_te, y_te, forget_cls), 5 * args.batch_size, False),
-                    te_r=mk(subset(x_te, y_te, remain_cls), 5 * args.batch_size, False), info=dict(forget_cls=forget_cls))
-
-    report, nets = run_tasks(kw, state, args, task_data, dev, out)
+    report, nets = run_tasks(kw, state, args, synthetic_task_data(args, geo["image_size"], dev), dev, out)
     return report, out, nets
 
 

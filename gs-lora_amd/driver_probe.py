@@ -96,12 +96,12 @@ def main(argv=None):
     import random
 
     import driver_cl
+    from driver_common import geometry, task_classes
     from vit_pytorch_face import ViT_face, ViTs_face
     args = driver_cl.get_args(argv)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
-    geo = (dict(image_size=48, patch_size=8, dim=128, depth=3, heads=2, mlp_dim=256) if args.small else
-           dict(image_size=112, patch_size=8, dim=512, depth=6, heads=8, mlp_dim=2048))
+    geo = geometry(args.small)
     kw = dict(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout, lora_rank=args.lora_rank, **geo)
     model = (ViTs_face(ac_patch_size=12, pad=4, **kw) if args.net == "VITs" else ViT_face(**kw)).to(dev).set_compute_dtype(args.dtype)
     if args.u8_input:
@@ -109,10 +109,10 @@ def main(argv=None):
     order = list(range(args.num_class))
     random.seed(args.seed)
     random.shuffle(order)
-    en1 = args.num_class - args.per_forget_cls
+    remain_cls, forget_cls = task_classes(order, args.num_class, args.per_forget_cls, 0)
     x_tr, y_tr = driver_cl.synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed, u8=args.u8_input)
     x_te, y_te = driver_cl.synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1, u8=args.u8_input)
-    loaders = probe_loaders(x_tr, y_tr, x_te, y_te, order[en1:], order[:en1], args.batch_size, args.seed)
+    loaders = probe_loaders(x_tr, y_tr, x_te, y_te, forget_cls, remain_cls, args.batch_size, args.seed)
     return run_probe(model, args, loaders, dev), model
 
 

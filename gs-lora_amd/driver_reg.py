@@ -19,23 +19,21 @@ the `loss` head trains with --ffn_open (:426), every other backbone weight stays
 section 9).
 """
 import argparse
-import json
 import os
-import random
 import sys
-import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import torch  # noqa: E402
-from torch.utils.data import DataLoader  # noqa: E402
 
 import engine_cl  # noqa: E402
 import engine_reg  # noqa: E402
+from driver_common import (add_common_args, append_record, build_ffn_model, eval_cfg, eval_task, geometry, mark_only_ffn_as_trainable,  # noqa: E402, F401
+                           meter_averages, outdir, synthetic_task_data)
 from gslora_hip.optim import create_optimizer, create_scheduler  # noqa: E402
-from util.utils import AverageMeter, count_trainable_parameters  # noqa: E402
+from util.utils import AverageMeter  # noqa: E402
 
 NO_GPU = "gs-lora_amd driver_reg: no ROCm GPU is visible; the regularisation baselines run on the HIP path, which has no CPU fallback"
 
@@ -53,43 +51,14 @@ def get_args(argv=None):
     p.add_argument("--ewc_lambda", type=float, default=0.1)
     p.add_argument("--mas_lambda", type=float, default=0.1)
     p.add_argument("--online", default=False, action="store_true", help="keep ONE term and accumulate its importance across tasks")
-    p.add_argument("--ffn_open", default=False, action="store_true", help="train the `loss` head too (train_own_forget_cl.py:426)")
-    p.add_argument("--only_ffn", default=True, action="store_true",
-                   help="always on: the FFN linears (names containing fn.fn.net) are the backbone weights that train on the HIP path")
-    p.add_argument("--num_class", type=int, default=100)
-    p.add_argument("--num_tasks", type=int, default=4)
-    p.add_argument("--per_forget_cls", type=int, default=20)
     p.add_argument("--epochs", type=int, default=2)
-    p.add_argument("--batch_size", type=int, default=48)
-    p.add_argument("--samples_per_class", type=int, default=8)
-    p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--min_lr", type=float, default=1e-5)
-    p.add_argument("--weight_decay", type=float, default=0.05)
-    p.add_argument("--opt", default="adamw")
-    p.add_argument("--opt_eps", type=float, default=1e-8)
-    p.add_argument("--opt_betas", default=None)
     p.add_argument("--sched", default="cosine")
     p.add_argument("--warmup_epochs", type=int, default=0)
     p.add_argument("--warmup_lr", type=float, default=1e-6)
     p.add_argument("--cooldown_epochs", type=int, default=10)
-    p.add_argument("--dropout", type=float, default=0.1)
-    p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 | fp32 | fp32x3")
-    p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
-    p.add_argument("-n", "--net", default="VIT", choices=["VIT", "VITs"])
-    p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"])
-    p.add_argument("--outdir", default=None)
-    p.add_argument("--seed", type=int, default=1337)
+    add_common_args(p)
     return p.parse_args(argv)
-
-
-def mark_only_ffn_as_trainable(model, ffn_open=False):
-    """train_own_forget_cl.py:425-439: requires_grad = "fn.fn.net" in name, or ("loss" in name and --ffn_open). -> the names that train"""
-    names = []
-    for name, param in model.named_parameters():
-        param.requires_grad = "fn.fn.net" in name or (ffn_open and "loss" in name)
-        if param.requires_grad:
-            names.append(name)
-    return names
 
 
 def kind_of(args):
@@ -107,7 +76,8 @@ def run_tasks(model, args, task_data, dev, out):
     from gslora_hip import reg
     kind, reg_lambda = kind_of(args)
     criterion = torch.nn.CrossEntropyLoss()
-    cfg = {"DATA_ROOT": "./data/synthetic/", "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net}
+    cfg = eval_cfg(out, args.net)
+    evaluate = lambda loader, tag: engine_cl.eval_data(model, loader, dev, tag)
     terms, report = {}, []
     model.train()                                                                    # :1412
     path = os.path.join(out, "reg_report.jsonl")
@@ -121,8 +91,7 @@ def run_tasks(model, args, task_data, dev, out):
             terms[0] = {"importance": importance, "task_param": task_param}
         optimizer = create_optimizer(args, model)
         scheduler, _ = create_scheduler(args, optimizer)
-        forget_before = engine_cl.eval_data(model, td["te_f"], dev, f"forget-{task_i}-before")
-        remain_before = engine_cl.eval_data(model, td["te_r"], dev, f"remain-{task_i}-before")
+        forget_before, remain_before = eval_task(evaluate, td, task_i, "before")
         model.train()
         batch, best_h = 0, 0.0
         m = dict(losses_CE=AverageMeter(), losses_regularization=AverageMeter(), losses_total=AverageMeter())
@@ -133,7 +102,7 @@ def run_tasks(model, args, task_data, dev, out):
                 model=model, criterion=criterion, data_loader_cl_forget=td["loader_f"], optimizer=optimizer, device=dev, epoch=epoch,
                 batch=batch, reg_lambda=reg_lambda, regularization_terms=terms, task_i=task_i, testloader_forget=td["te_f"],
                 testloader_remain=td["te_r"], highest_H_mean=best_h, forget_acc_before=forget_before, cfg=cfg, **m)
-            epochs.append({k: (v.avg if v.count else None) for k, v in m.items()})
+            epochs.append(meter_averages(m))
         task_param = backup(model)                                                   # :1629-1633
         if task_i < args.num_tasks - 1:                                              # :1637-1690: the NEXT task's remain set
             nxt = task_data(task_i + 1)
@@ -142,62 +111,27 @@ def run_tasks(model, args, task_data, dev, out):
                                                   prior=terms[0]["importance"] if online and kind != "l2" else None)
             skipped += importance.skipped
             terms[0 if online else task_i + 1] = {"importance": importance, "task_param": task_param}
-        forget_after = engine_cl.eval_data(model, td["te_f"], dev, f"forget-{task_i}-after")
-        remain_after = engine_cl.eval_data(model, td["te_r"], dev, f"remain-{task_i}-after")
+        forget_after, remain_after = eval_task(evaluate, td, task_i, "after")
         model.train()
         last = terms[max(terms)]["importance"]
         rec = dict(task=task_i, kind=kind, reg_lambda=reg_lambda, online=bool(args.online), steps=batch, n_terms=len(terms), epochs=epochs,
                    importance_sum=float(sum(v.double().sum() for v in last.values())), skipped_importance_batches=skipped,
                    forget_before=forget_before, forget_after=forget_after, remain_before=remain_before, remain_after=remain_after,
                    **td.get("info", {}))
-        report.append(rec)
-        with open(path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        print(f"[task {task_i}] {kind} lambda={reg_lambda} terms={len(terms)} steps={batch} "
-              f"forget {forget_before:.1f}->{forget_after:.1f}  remain {remain_before:.1f}->{remain_after:.1f}")
+        append_record(path, report, rec, f"{kind} lambda={reg_lambda} terms={len(terms)} steps={batch}")
     return report, terms
 
 
 def main(argv=None):
-    import driver_cl
-    from vit_pytorch_face import ViT_face, ViTs_face
     args = get_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError(NO_GPU)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
-    geo = (dict(image_size=48, patch_size=8, dim=128, depth=3, heads=2, mlp_dim=256) if args.small else
-           dict(image_size=112, patch_size=8, dim=512, depth=6, heads=8, mlp_dim=2048))
-    out = args.outdir or tempfile.mkdtemp(prefix="gslora_reg_")
-    os.makedirs(out, exist_ok=True)
-    kw = dict(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout, lora_rank=0, **geo)
-    model = ViTs_face(ac_patch_size=12, pad=4, **kw) if args.net == "VITs" else ViT_face(**kw)
-    names = mark_only_ffn_as_trainable(model, args.ffn_open)
-    print("trainable parameters:", count_trainable_parameters(model), f"({len(names)} tensors)")
-    model = model.to(dev).set_compute_dtype(args.dtype)
-    order = list(range(args.num_class))
-    random.seed(args.seed)
-    random.shuffle(order)
-    x_all, y_all = driver_cl.synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed)
-    x_te, y_te = driver_cl.synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1)
-    x_all, y_all, x_te, y_te = x_all.to(dev), y_all.to(dev), x_te.to(dev), y_te.to(dev)      # device-resident: the loaders index on the GPU
-    num_first = args.num_class - args.per_forget_cls
-
-    def subset(x, y, classes):
-        m = torch.isin(y, torch.tensor(classes, device=y.device))
-        return torch.utils.data.TensorDataset(x[m], y[m])
-
-    def task_data(task_i):
-        en1 = num_first - task_i * args.per_forget_cls        # :1639-1643 (st1 = 0, st2 = en1)
-        en2 = en1 + args.per_forget_cls
-        remain_cls, forget_cls = order[:en1], order[en1:en2]
-        gen = torch.Generator().manual_seed(args.seed + task_i)
-        mk = lambda ds, bs, sh: DataLoader(ds, batch_size=bs, shuffle=sh, generator=gen if sh else None, drop_last=False)
-        return dict(loader_f=mk(subset(x_all, y_all, forget_cls), args.batch_size, True),
-                    loader_imp=mk(subset(x_all, y_all, remain_cls), args.batch_size, True),
-                    te_f=mk(subset(x_te, y_te, forget_cls), 5 * args.batch_size, False),
-                    te_r=mk(subset(x_te, y_te, remain_cls), 5 * args.batch_size, False), info=dict(forget_cls=forget_cls))
-
+    geo = geometry(args.small)
+    out = outdir(args, "gslora_reg_")
+    model = build_ffn_model(args, geo, dev)
+    task_data = synthetic_task_data(args, geo["image_size"], dev, remain_key="loader_imp")      # (the split of :1639-1643)
     report, terms = run_tasks(model, args, task_data, dev, out)
     return report, out, (model, terms)
 

@@ -18,24 +18,20 @@ The optimizer is create_optimizer's FusedAdamW: with the reference's default --o
 rmsp, :860-879) matches, so the timm AdamW built before stays. Those three values are refused with that explanation.
 """
 import argparse
-import copy
-import json
 import os
-import random
 import sys
-import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 import torch  # noqa: E402
-from torch.utils.data import DataLoader  # noqa: E402
 
 import engine_cl  # noqa: E402
-from driver_reg import mark_only_ffn_as_trainable  # noqa: E402
+from driver_common import (add_common_args, append_record, build_ffn_model, eval_cfg, eval_task, frozen_copy, geometry, meter_averages,  # noqa: E402
+                           outdir, synthetic_task_data)
 from gslora_hip.optim import create_optimizer  # noqa: E402
-from util.utils import AverageMeter, count_trainable_parameters  # noqa: E402
+from util.utils import AverageMeter  # noqa: E402
 
 NO_GPU = "gs-lora_amd driver_scrub: no ROCm GPU is visible; the SCRUB baseline runs on the HIP path, which has no CPU fallback"
 SCRUB_OPTS = ("sgd", "adam", "rmsp")
@@ -54,26 +50,7 @@ def get_args(argv=None):
     p.add_argument("--SCRUB_superepoch", default=10, type=int, help="superepochs per task")
     p.add_argument("--kd_T", default=2.0, type=float, help="distillation temperature")
     p.add_argument("--scrub_decay_epoch", default=100, type=int, help="inner epoch behind which the rate decays")
-    p.add_argument("--ffn_open", default=False, action="store_true", help="train the `loss` head too (train_own_forget_cl.py:426)")
-    p.add_argument("--only_ffn", default=True, action="store_true",
-                   help="always on: the FFN linears (names containing fn.fn.net) are the backbone weights that train on the HIP path")
-    p.add_argument("--num_class", type=int, default=100)
-    p.add_argument("--num_tasks", type=int, default=4)
-    p.add_argument("--per_forget_cls", type=int, default=20)
-    p.add_argument("--batch_size", type=int, default=48)
-    p.add_argument("--samples_per_class", type=int, default=8)
-    p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--weight_decay", type=float, default=0.05)
-    p.add_argument("--opt", default="adamw")
-    p.add_argument("--opt_eps", type=float, default=1e-8)
-    p.add_argument("--opt_betas", default=None)
-    p.add_argument("--dropout", type=float, default=0.1)
-    p.add_argument("--dtype", default=os.environ.get("GSLORA_DTYPE", "fp16"), help="fp16 | bf16 | fp32 | fp32x3")
-    p.add_argument("--small", action="store_true", help="shrunken model (48 px, dim 128, depth 3) for tests")
-    p.add_argument("-n", "--net", default="VIT", choices=["VIT", "VITs"])
-    p.add_argument("--head", default="CosFace", choices=["CosFace", "ArcFace", "Softmax"])
-    p.add_argument("--outdir", default=None)
-    p.add_argument("--seed", type=int, default=1337)
+    add_common_args(p)
     args = p.parse_args(argv)
     if args.opt.lower() in SCRUB_OPTS:
         p.error(f"--opt {args.opt}: the reference builds torch's SGD / Adam / RMSprop for SCRUB only under --opt sgd | adam | rmsp; with its "
@@ -84,18 +61,14 @@ def get_args(argv=None):
 
 def scrub_cfg(args, out):
     """config.py:107-110 on top of what evaluate reads."""
-    return {"DATA_ROOT": "./data/synthetic/", "MULTI_GPU": False, "WORK_PATH": out, "BACKBONE_NAME": args.net, "lr_decay_rate": 0.1,
-            "lr_decay_epochs": args.scrub_decay_epoch, "sgda_learning_rate": args.lr}
+    return {**eval_cfg(out, args.net), "lr_decay_rate": 0.1, "lr_decay_epochs": args.scrub_decay_epoch, "sgda_learning_rate": args.lr}
 
 
 def make_teacher_and_average(model, dev):
     """:440-451"""
-    teacher = copy.deepcopy(model).to(dev).eval()
-    for p in teacher.parameters():
-        p.requires_grad_(False)
     # an exponential moving average: the new weights enter with BETA, the running average keeps the rest
     ema = lambda avg, new, n: avg * (1.0 - BETA) + new * BETA
-    return teacher, torch.optim.swa_utils.AveragedModel(model, avg_fn=ema).to(dev)
+    return frozen_copy(model, dev), torch.optim.swa_utils.AveragedModel(model, avg_fn=ema).to(dev)
 
 
 def run_tasks(model, args, task_data, dev, out):
@@ -104,14 +77,14 @@ def run_tasks(model, args, task_data, dev, out):
     from baselines.SCRUBtrain import train_one_superepoch_SCRUB
     criterion = torch.nn.CrossEntropyLoss()
     cfg = scrub_cfg(args, out)
+    evaluate = lambda loader, tag: engine_cl.eval_data(model, loader, dev, tag)
     report = []
     path = os.path.join(out, "scrub_report.jsonl")
     for task_i in range(args.num_tasks):
         td = task_data(task_i)
         teacher, swa_model = make_teacher_and_average(model, dev)
         optimizer = create_optimizer(args, model)
-        forget_before = engine_cl.eval_data(model, td["te_f"], dev, f"forget-{task_i}-before")
-        remain_before = engine_cl.eval_data(model, td["te_r"], dev, f"remain-{task_i}-before")
+        forget_before, remain_before = eval_task(evaluate, td, task_i, "before")
         model.train()
         batch, best_h = 0, 0.0
         m = dict(losses_CE=AverageMeter(), losses_total_forget=AverageMeter(), losses_total_remain=AverageMeter(), losses_kd_remain=AverageMeter(),
@@ -124,62 +97,27 @@ def run_tasks(model, args, task_data, dev, out):
                 criterion=criterion, optimizer=optimizer, device=dev, superepoch=epoch, batch=batch, task_i=task_i, testloader_forget=td["te_f"],
                 testloader_remain=td["te_r"], highest_H_mean=best_h, forget_acc_before=forget_before, cfg=cfg, kd_T=args.kd_T,
                 sgda_smoothing=args.sgda_smoothing, sgda_gamma=args.sgda_gamma, sgda_alpha=args.sgda_alpha, **m)
-            superepochs.append({k: (v.avg if v.count else None) for k, v in m.items()})
-        forget_after = engine_cl.eval_data(model, td["te_f"], dev, f"forget-{task_i}-after")
-        remain_after = engine_cl.eval_data(model, td["te_r"], dev, f"remain-{task_i}-after")
+            superepochs.append(meter_averages(m))
+        forget_after, remain_after = eval_task(evaluate, td, task_i, "after")
         model.train()
         rec = dict(task=task_i, steps=batch, superepochs=superepochs, kd_T=args.kd_T, sgda_smoothing=args.sgda_smoothing,
                    sgda_gamma=args.sgda_gamma, sgda_alpha=args.sgda_alpha, n_averaged=int(swa_model.n_averaged.item()),
                    forget_before=forget_before, forget_after=forget_after, remain_before=remain_before, remain_after=remain_after,
                    **td.get("info", {}))
-        report.append(rec)
-        with open(path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-        print(f"[task {task_i}] SCRUB steps={batch} forget {forget_before:.1f}->{forget_after:.1f}  remain {remain_before:.1f}->{remain_after:.1f}")
+        append_record(path, report, rec, f"SCRUB steps={batch}")
     return report
 
 
 def main(argv=None):
-    import driver_cl
-    from vit_pytorch_face import ViT_face, ViTs_face
     args = get_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError(NO_GPU)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
-    geo = (dict(image_size=48, patch_size=8, dim=128, depth=3, heads=2, mlp_dim=256) if args.small else
-           dict(image_size=112, patch_size=8, dim=512, depth=6, heads=8, mlp_dim=2048))
-    out = args.outdir or tempfile.mkdtemp(prefix="gslora_scrub_")
-    os.makedirs(out, exist_ok=True)
-    kw = dict(loss_type=args.head, GPU_ID=[0], num_class=args.num_class, dropout=args.dropout, emb_dropout=args.dropout, lora_rank=0, **geo)
-    model = ViTs_face(ac_patch_size=12, pad=4, **kw) if args.net == "VITs" else ViT_face(**kw)
-    names = mark_only_ffn_as_trainable(model, args.ffn_open)
-    print("trainable parameters:", count_trainable_parameters(model), f"({len(names)} tensors)")
-    model = model.to(dev).set_compute_dtype(args.dtype)
-    order = list(range(args.num_class))
-    random.seed(args.seed)
-    random.shuffle(order)
-    x_all, y_all = driver_cl.synthetic_dataset(args.num_class, args.samples_per_class, geo["image_size"], args.seed)
-    x_te, y_te = driver_cl.synthetic_dataset(args.num_class, 2, geo["image_size"], args.seed + 1)
-    x_all, y_all, x_te, y_te = x_all.to(dev), y_all.to(dev), x_te.to(dev), y_te.to(dev)      # device-resident: the loaders index on the GPU
-    num_first = args.num_class - args.per_forget_cls
-
-    def subset(x, y, classes):
-        m = torch.isin(y, torch.tensor(classes, device=y.device))
-        return torch.utils.data.TensorDataset(x[m], y[m])
-
-    def task_data(task_i):
-        en1 = num_first - task_i * args.per_forget_cls
-        en2 = en1 + args.per_forget_cls
-        remain_cls, forget_cls = order[:en1], order[en1:en2]
-        gen = torch.Generator().manual_seed(args.seed + task_i)
-        mk = lambda ds, bs, sh: DataLoader(ds, batch_size=bs, shuffle=sh, generator=gen if sh else None, drop_last=False)
-        return dict(loader_f=mk(subset(x_all, y_all, forget_cls), args.batch_size, True),
-                    loader_r=mk(subset(x_all, y_all, remain_cls), args.batch_size, True),
-                    te_f=mk(subset(x_te, y_te, forget_cls), 5 * args.batch_size, False),
-                    te_r=mk(subset(x_te, y_te, remain_cls), 5 * args.batch_size, False), info=dict(forget_cls=forget_cls))
-
-    report = run_tasks(model, args, task_data, dev, out)
+    geo = geometry(args.small)
+    out = outdir(args, "gslora_scrub_")
+    model = build_ffn_model(args, geo, dev)
+    report = run_tasks(model, args, synthetic_task_data(args, geo["image_size"], dev), dev, out)
     return report, out, model
 
 

@@ -9,6 +9,8 @@ import os
 
 import contextlib
 
+from ._cdll import LazyLib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSLORA_HIP_LIB: development override (A/B of kernel build variants, tools/probes/); the default is the in-tree PRODUCT build.
 # libgslora_hip_dev.so (python -m gslora_hip.build --dev) is the same ABI compiled with -DGSL_DEV: it additionally holds the GEMM
@@ -102,50 +104,27 @@ SIGNATURES = {
 _RESTYPES = {"gsl_last_error": C.c_char_p, "gsl_lora_grad_ws_elems": C.c_long, "gsl_gemm_mulgrad_ws_elems": C.c_long,
              "gsl_lora_grad_batch_ws_elems": C.c_long}
 
-_lib = None
-
-
-def _bind(path):
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"{os.path.basename(path)} not found at {path}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The GS-LoRA step has no CPU fallback.")
-    try:
-        lib = C.CDLL(path)
-    except OSError as e:  # missing libamdhip64 etc.
-        raise RuntimeError(f"cannot load {path}: {e}") from e
-    for name, argtypes in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise RuntimeError(f"{path} does not export {name}; rebuild the extension") from e
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
-    return lib
+_prod = LazyLib(lambda: LIB_PATH, SIGNATURES, _RESTYPES, "gsl_last_error", "The GS-LoRA step has no CPU fallback.")
+_dev = LazyLib(lambda: DEV_LIB_PATH, SIGNATURES, _RESTYPES, "gsl_last_error", "The GS-LoRA step has no CPU fallback.")
+_lib = None      # the library the calls go to: the product's once load() has opened it, the dev build's inside use_dev()
 
 
 def load():
     """Load the shared library (once). Raises RuntimeError — never falls back to a CPU path."""
     global _lib
     if _lib is None:
-        _lib = _bind(LIB_PATH)
+        _lib = _prod.load()
     return _lib
-
-
-_dev = None
 
 
 @contextlib.contextmanager
 def use_dev():
     """Route the calls made inside the block to the development build (tests that compare the product kernels with the
     variants / ablations only the dev build contains, tools/probes/). Raises RuntimeError if it has not been built."""
-    global _lib, _dev
-    if _dev is None:
-        _dev = _bind(DEV_LIB_PATH)
-    prev = _lib
-    _lib = _dev
+    global _lib
+    prev, _lib = _lib, _dev.load()
     try:
-        yield _dev
+        yield _lib
     finally:
         _lib = prev
 

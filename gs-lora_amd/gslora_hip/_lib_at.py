@@ -1,12 +1,14 @@
 """ctypes binding of libgslora_at.so (C ABI declared in include/gslora_at.h): the attention-transfer term of the LIRF baseline on the
 [B, T, D] stream between the two half networks — its value, the table that carries its gradient, and the in-place gradient at the boundary.
-The library is opened on first use: a process that takes no LIRF step never loads it. As for the other five libraries there is NO fallback:
+The library is opened on first use: a process that takes no LIRF step never loads it. As for every library here there is NO fallback:
 a missing library or a refused call raises RuntimeError.
 """
 import ctypes as C
 import os
 
 import torch
+
+from ._cdll import LazyLib, _ld, _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgslora_at.so")
@@ -27,43 +29,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"gsa_last_error": C.c_char_p, "gsa_at_ws_elems": C.c_long}
 
-_lib = None
-
-
-def load():
-    """Load the shared library (once). Raises RuntimeError — never falls back to another path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"libgslora_at.so not found at {LIB_PATH}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). The LIRF baseline has no fallback.")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, argtypes in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        _lib = lib
-    return _lib
-
-
-def loaded():
-    return _lib is not None
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().gsa_last_error()
-        raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+_L = LazyLib(lambda: LIB_PATH, SIGNATURES, _RESTYPES, "gsa_last_error", "The LIRF baseline has no fallback.")
+load, loaded, check = _L.load, _L.loaded, _L.check
 
 
 def at_plan(B, T, D):
@@ -74,10 +41,7 @@ def at_plan(B, T, D):
 
 
 def at_ws_elems(B, T, D):
-    n = load().gsa_at_ws_elems(B, T, D)
-    if n < 0:
-        raise RuntimeError(f"gsa_at_ws_elems({B}, {T}, {D}) refused: {load().gsa_last_error().decode()}")
-    return n
+    return _L.nonneg(load().gsa_at_ws_elems(B, T, D), f"gsa_at_ws_elems({B}, {T}, {D})")
 
 
 def _rows(t, what, dtypes=tuple(DTYPES)):
@@ -93,10 +57,6 @@ def _rows(t, what, dtypes=tuple(DTYPES)):
         raise RuntimeError(f"gslora_hip.at: {what} must be a [rows, D] or [B, T, D] {names} tensor on a ROCm GPU with unit column stride and "
                            "evenly spaced rows (the HIP path has no CPU fallback)")
     return t
-
-
-def _ld(t):
-    return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
 
 
 def _f32(t, what, n):

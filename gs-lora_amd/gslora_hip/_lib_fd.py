@@ -1,12 +1,14 @@
 """ctypes binding of libgslora_fd.so (C ABI declared in include/gslora_fd.h): the row distance between a student's and a frozen teacher's
 outputs — the regulariser of the DER / DER++ and FDR baselines — with its tensor-level wrappers. The library is opened on first use: a process
-that takes no DER or FDR step never loads it. As for the other four libraries there is NO fallback: a missing library or a refused call
+that takes no DER or FDR step never loads it. As for every library here there is NO fallback: a missing library or a refused call
 raises RuntimeError.
 """
 import ctypes as C
 import os
 
 import torch
+
+from ._cdll import LazyLib, _ld, _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgslora_fd.so")
@@ -28,43 +30,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"gsf_last_error": C.c_char_p, "gsf_rowdist_ws_elems": C.c_long}
 
-_lib = None
-
-
-def load():
-    """Load the shared library (once). Raises RuntimeError — never falls back to another path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"libgslora_fd.so not found at {LIB_PATH}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). The DER / FDR baselines have no fallback.")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, argtypes in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        _lib = lib
-    return _lib
-
-
-def loaded():
-    return _lib is not None
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().gsf_last_error()
-        raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+_L = LazyLib(lambda: LIB_PATH, SIGNATURES, _RESTYPES, "gsf_last_error", "The DER / FDR baselines have no fallback.")
+load, loaded, check = _L.load, _L.loaded, _L.check
 
 
 def rowdist_plan(B, W):
@@ -75,20 +42,13 @@ def rowdist_plan(B, W):
 
 
 def rowdist_ws_elems(B, W):
-    n = load().gsf_rowdist_ws_elems(B, W)
-    if n < 0:
-        raise RuntimeError(f"gsf_rowdist_ws_elems({B}, {W}) refused: {load().gsf_last_error().decode()}")
-    return n
+    return _L.nonneg(load().gsf_rowdist_ws_elems(B, W), f"gsf_rowdist_ws_elems({B}, {W})")
 
 
 def _rows(t, what):
     if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
         raise RuntimeError(f"gslora_hip.fd: {what} must be a [B, W] f32 tensor on a ROCm GPU with unit column stride (the HIP path has no CPU "
                            "fallback)")
-
-
-def _ld(t):
-    return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
 
 
 def rowdist_fwd(a, t, mode, out1, ws):

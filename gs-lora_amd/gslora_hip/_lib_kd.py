@@ -1,11 +1,13 @@
 """ctypes binding of libgslora_kd.so (C ABI declared in include/gslora_kd.h): the distillation + cross-entropy row loss and the batched
 parameter distance of the SCRUB baseline, with their tensor-level wrappers. The library is opened on first use: a process that runs no SCRUB
-step never loads it. As for the other three libraries there is NO fallback: a missing library or a refused call raises RuntimeError.
+step never loads it. As for every library here there is NO fallback: a missing library or a refused call raises RuntimeError.
 """
 import ctypes as C
 import os
 
 import torch
+
+from ._cdll import LazyLib, _ld, _ptr, _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgslora_kd.so")
@@ -35,47 +37,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"gsk_last_error": C.c_char_p, "gsk_kd_ws_elems": C.c_long}
 
-_lib = None
-
-
-def load():
-    """Load the shared library (once). Raises RuntimeError — never falls back to another path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"libgslora_kd.so not found at {LIB_PATH}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). The SCRUB baseline has no fallback.")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, argtypes in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        _lib = lib
-    return _lib
-
-
-def loaded():
-    return _lib is not None
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().gsk_last_error()
-        raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_L = LazyLib(lambda: LIB_PATH, SIGNATURES, _RESTYPES, "gsk_last_error", "The SCRUB baseline has no fallback.")
+load, loaded, check = _L.load, _L.loaded, _L.check
 
 
 def kd_plan(B, C_):
@@ -86,20 +49,13 @@ def kd_plan(B, C_):
 
 
 def kd_ws_elems(B, C_):
-    n = load().gsk_kd_ws_elems(B, C_)
-    if n < 0:
-        raise RuntimeError(f"gsk_kd_ws_elems({B}, {C_}) refused: {load().gsk_last_error().decode()}")
-    return n
+    return _L.nonneg(load().gsk_kd_ws_elems(B, C_), f"gsk_kd_ws_elems({B}, {C_})")
 
 
 def _logits(t, what):
     if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
         raise RuntimeError(f"gslora_hip.kd: {what} must be a [B, C] f32 tensor on a ROCm GPU with unit column stride (the HIP path has no CPU "
                            "fallback)")
-
-
-def _ld(t):
-    return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
 
 
 def kd_ce_fwd(ys, yt, labels, T, c_kd, c_ce, out3, ws):

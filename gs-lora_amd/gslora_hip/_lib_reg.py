@@ -1,12 +1,14 @@
 """ctypes binding of libgslora_reg.so (C ABI declared in include/gslora_reg.h): importance accumulation, MAS's mean-of-squares objective and
 the batched quadratic regulariser of the L2 / EWC / MAS baselines, with their tensor-level wrappers. The library is opened on first use: a
-process that trains LoRA only, or the head only, never loads it. As for the other two libraries there is NO fallback: a missing library or
+process that trains LoRA only, or the head only, never loads it. As for every library here there is NO fallback: a missing library or
 a refused call raises RuntimeError.
 """
 import ctypes as C
 import os
 
 import torch
+
+from ._cdll import LazyLib, _ptr, _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgslora_reg.so")
@@ -36,47 +38,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"gsr_last_error": C.c_char_p, "gsr_sq_mean_ws_elems": C.c_long}
 
-_lib = None
-
-
-def load():
-    """Load the shared library (once). Raises RuntimeError — never falls back to another path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"libgslora_reg.so not found at {LIB_PATH}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). The regularisation baselines have no fallback.")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, argtypes in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        _lib = lib
-    return _lib
-
-
-def loaded():
-    return _lib is not None
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().gsr_last_error()
-        raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_L = LazyLib(lambda: LIB_PATH, SIGNATURES, _RESTYPES, "gsr_last_error", "The regularisation baselines have no fallback.")
+load, loaded, check = _L.load, _L.loaded, _L.check
 
 
 def _flat_f32(t, what):
@@ -97,10 +60,7 @@ def importance_acc(omega, g, kind, a, b, guard=None, skipped=None):
 
 
 def sq_mean_ws_elems(B, C_):
-    n = load().gsr_sq_mean_ws_elems(B, C_)
-    if n < 0:
-        raise RuntimeError(f"gsr_sq_mean_ws_elems({B}, {C_}) refused: {load().gsr_last_error().decode()}")
-    return n
+    return _L.nonneg(load().gsr_sq_mean_ws_elems(B, C_), f"gsr_sq_mean_ws_elems({B}, {C_})")
 
 
 def sq_mean_fwd(x, out, ws=None):

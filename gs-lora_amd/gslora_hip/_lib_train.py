@@ -7,6 +7,7 @@ import os
 
 import torch
 
+from ._cdll import LazyLib, _ptr, _stream
 from ._lib import BF16, F16, F32
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -27,57 +28,14 @@ SIGNATURES = {
 }
 _RESTYPES = {"gst_last_error": C.c_char_p, "gst_wgrad_ws_elems": C.c_long, "gst_reg_quad_ws_elems": C.c_long}
 
-_lib = None
-
-
-def load():
-    """Load the shared library (once). Raises RuntimeError — never falls back to another path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"libgslora_train.so not found at {LIB_PATH}. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                               "(hipcc --offload-arch=gfx950). Training FFN weights has no fallback.")
-        try:
-            lib = C.CDLL(LIB_PATH)
-        except OSError as e:
-            raise RuntimeError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, argtypes in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise RuntimeError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        _lib = lib
-    return _lib
-
-
-def loaded():
-    return _lib is not None
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().gst_last_error()
-        raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
-
+_L = LazyLib(lambda: LIB_PATH, SIGNATURES, _RESTYPES, "gst_last_error", "Training FFN weights has no fallback.")
+load, loaded, check = _L.load, _L.loaded, _L.check
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def wgrad_ws_elems(M, N, K, dtype):
-    n = load().gst_wgrad_ws_elems(M, N, K, _DT[dtype])
-    if n < 0:
-        raise RuntimeError(f"gst_wgrad_ws_elems({M}, {N}, {K}) refused: {load().gst_last_error().decode()}")
-    return n
+    return _L.nonneg(load().gst_wgrad_ws_elems(M, N, K, _DT[dtype]), f"gst_wgrad_ws_elems({M}, {N}, {K})")
 
 
 def wgrad_plan(M, N, K, dtype):

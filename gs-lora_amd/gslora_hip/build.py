@@ -23,31 +23,17 @@ HEADERS = ["gsl_common.h", "gsl_h16.h", "exports.map", "gelu_g8_table.inc"]
 DEV_ONLY = ["gemm_dev_a.inc", "gemm_dev_b.inc", "gemm_dev_c.inc", "gemm_dev_launch.inc", "gemm_w4.inc", "gemm_o4.inc", "attention_dev_launch.inc"]
 OUT = os.path.join(HERE, "libgslora_hip.so")
 OUT_DEV = os.path.join(HERE, "libgslora_hip_dev.so")
-# the second product library (include/gslora_train.h, prefix gst_): the weight-gradient GEMM and the quadratic regulariser of the FFN-training
-# step. One translation unit, its own version script; built by build() with the first, opened only by a process that trains FFN weights.
-TRAIN_SOURCES = ["train.hip"]
-TRAIN_HEADERS = ["gsl_common.h", "exports_train.map"]
-OUT_TRAIN = os.path.join(HERE, "libgslora_train.so")
-# the third product library (include/gslora_reg.h, prefix gsr_): importance accumulation, MAS's objective and the batched quadratic regulariser
-# of the L2 / EWC / MAS baselines. Made the way the second one is; opened only by a process that runs those baselines.
-REG_SOURCES = ["reg.hip"]
-REG_HEADERS = ["gsl_common.h", "exports_reg.map"]
-OUT_REG = os.path.join(HERE, "libgslora_reg.so")
-# the fourth product library (include/gslora_kd.h, prefix gsk_): the distillation + cross-entropy row loss and the batched parameter distance
-# of the SCRUB baseline. Made the way the third one is; opened only by a process that runs a SCRUB step.
-KD_SOURCES = ["kd.hip"]
-KD_HEADERS = ["gsl_common.h", "exports_kd.map"]
-OUT_KD = os.path.join(HERE, "libgslora_kd.so")
-# the fifth product library (include/gslora_fd.h, prefix gsf_): the student-teacher row distance of the DER / DER++ and FDR baselines. Made the
-# way the fourth one is; opened only by a process that takes a DER or FDR step.
-FD_SOURCES = ["fd.hip"]
-FD_HEADERS = ["gsl_common.h", "exports_fd.map"]
-OUT_FD = os.path.join(HERE, "libgslora_fd.so")
-# the sixth product library (include/gslora_at.h, prefix gsa_): the attention-transfer term of the LIRF baseline on the stream between the two
-# half networks. Made the way the fifth one is; opened only by a process that takes a LIRF step.
-AT_SOURCES = ["at.hip"]
-AT_HEADERS = ["gsl_common.h", "exports_at.map"]
-OUT_AT = os.path.join(HERE, "libgslora_at.so")
+# The side libraries, in build order: tag -> sources. Each is libgslora_<tag>.so with the public header include/gslora_<tag>.h, the version
+# script csrc/exports_<tag>.map and the objects under build/<tag>; built by build() with the product library, same flags, and opened only by
+# a process that uses it (gslora_hip/_lib_<tag>.py). train (gst_): the weight-gradient GEMM and quadratic regulariser of the FFN-training
+# step; reg (gsr_): importance accumulation, MAS's objective and the batched regulariser of L2 / EWC / MAS; kd (gsk_): SCRUB's distillation
+# + cross-entropy row loss and batched parameter distance; fd (gsf_): the student-teacher row distance of DER / DER++ / FDR; at (gsa_): the
+# attention-transfer term of LIRF.
+SIDE_LIBS = {"train": ["train.hip"], "reg": ["reg.hip"], "kd": ["kd.hip"], "fd": ["fd.hip"], "at": ["at.hip"]}
+
+
+def side_out(tag):
+    return os.path.join(HERE, f"libgslora_{tag}.so")
 
 
 def needs_build(dev=False):
@@ -60,83 +46,34 @@ def needs_build(dev=False):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _needs_build_side(out, sources, headers, header):
+def needs_build_side(tag):
+    out = side_out(tag)
     if not os.path.exists(out):
         return True
     t = os.path.getmtime(out)
     inc = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
-    deps = [os.path.join(CSRC, s) for s in sources + headers] + [os.path.join(inc, h) for h in ("gslora_hip.h", header)]
+    deps = [os.path.join(CSRC, s) for s in SIDE_LIBS[tag] + ["gsl_common.h", f"exports_{tag}.map"]]
+    deps += [os.path.join(inc, h) for h in ("gslora_hip.h", f"gslora_{tag}.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def needs_build_train():
-    return _needs_build_side(OUT_TRAIN, TRAIN_SOURCES, TRAIN_HEADERS, "gslora_train.h")
-
-
-def needs_build_reg():
-    return _needs_build_side(OUT_REG, REG_SOURCES, REG_HEADERS, "gslora_reg.h")
-
-
-def needs_build_kd():
-    return _needs_build_side(OUT_KD, KD_SOURCES, KD_HEADERS, "gslora_kd.h")
-
-
-def needs_build_fd():
-    return _needs_build_side(OUT_FD, FD_SOURCES, FD_HEADERS, "gslora_fd.h")
-
-
-def needs_build_at():
-    return _needs_build_side(OUT_AT, AT_SOURCES, AT_HEADERS, "gslora_at.h")
-
-
-def build_train(force=False, verbose=True):
-    """libgslora_train.so: same flags as the product library, linked against csrc/exports_train.map."""
-    if not force and not needs_build_train():
-        return OUT_TRAIN
-    return _build_side(OUT_TRAIN, TRAIN_SOURCES, "exports_train.map", "train", verbose)
-
-
-def build_reg(force=False, verbose=True):
-    """libgslora_reg.so: same flags as the product library, linked against csrc/exports_reg.map."""
-    if not force and not needs_build_reg():
-        return OUT_REG
-    return _build_side(OUT_REG, REG_SOURCES, "exports_reg.map", "reg", verbose)
-
-
-def build_kd(force=False, verbose=True):
-    """libgslora_kd.so: same flags as the product library, linked against csrc/exports_kd.map."""
-    if not force and not needs_build_kd():
-        return OUT_KD
-    return _build_side(OUT_KD, KD_SOURCES, "exports_kd.map", "kd", verbose)
-
-
-def build_fd(force=False, verbose=True):
-    """libgslora_fd.so: same flags as the product library, linked against csrc/exports_fd.map."""
-    if not force and not needs_build_fd():
-        return OUT_FD
-    return _build_side(OUT_FD, FD_SOURCES, "exports_fd.map", "fd", verbose)
-
-
-def build_at(force=False, verbose=True):
-    """libgslora_at.so: same flags as the product library, linked against csrc/exports_at.map."""
-    if not force and not needs_build_at():
-        return OUT_AT
-    return _build_side(OUT_AT, AT_SOURCES, "exports_at.map", "at", verbose)
-
-
-def _build_side(out, sources, version_script, tag, verbose):
+def build_side(tag, force=False, verbose=True):
+    """libgslora_<tag>.so: same flags as the product library, linked against csrc/exports_<tag>.map."""
+    out = side_out(tag)
+    if not force and not needs_build_side(tag):
+        return out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build", tag)
     os.makedirs(objdir, exist_ok=True)
     objs = []
-    for src in sources:
+    for src in SIDE_LIBS[tag]:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(obj)
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print("[gslora_hip.build]", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, version_script), "-o", out] + objs
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, f"exports_{tag}.map"), "-o", out] + objs
     if verbose:
         print("[gslora_hip.build]", " ".join(cmd), flush=True)
     subprocess.check_call(cmd)
@@ -145,15 +82,11 @@ def _build_side(out, sources, version_script, tag, verbose):
 
 def build(force=False, verbose=True, dev=False, defines=(), out=None, tag=None):
     """defines / out / tag: an A/B build of the product sources with extra -D flags into another file (tools/probes/, never loaded by
-    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds libgslora_train.so,
-    libgslora_reg.so, libgslora_kd.so, libgslora_fd.so and libgslora_at.so."""
+    default: `GSLORA_HIP_LIB=<out> python bench.py`). The plain product build (no dev, no variant) also builds every side library."""
     variant = out is not None
     if not variant and not dev:
-        build_train(force=force, verbose=verbose)
-        build_reg(force=force, verbose=verbose)
-        build_kd(force=force, verbose=verbose)
-        build_fd(force=force, verbose=verbose)
-        build_at(force=force, verbose=verbose)
+        for side in SIDE_LIBS:
+            build_side(side, force=force, verbose=verbose)
     out = out or (OUT_DEV if dev else OUT)
     if not variant and not force and not needs_build(dev):
         return out

@@ -330,6 +330,23 @@ def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, r
     return torch.stack((loss_ce.detach(), loss_reg.detach(), total.detach(), hits * (100.0 / n)))
 
 
+def _refuse_group_and_graph(name, model, optimizer):
+    """The baseline steps run in one process, eager."""
+    if _world() > 1:
+        raise RuntimeError(f"gs-lora_amd: {name} runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    if isinstance(model, GraphedStep) or isinstance(optimizer, GraphedStep):
+        raise RuntimeError(f"gs-lora_amd: {name} is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+
+
+def _refuse_unless_ffn_trains_without_lora(name, net):
+    if not getattr(net, "trainable_ffn", ""):
+        raise RuntimeError(f"gs-lora_amd: {name} trains the FFN linears of a ViT_face / ViTs_face built with lora_rank = 0 (the reference's "
+                           f"--only_ffn rule); {type(net).__name__} has no FFN weights that train on the HIP path")
+    if getattr(net, "lora_rank", 0) > 0:
+        raise RuntimeError(f"gs-lora_amd: {name} trains the FFN linears of a model built with lora_rank = 0 (the reference's --only_ffn rule); "
+                           f"this {type(net).__name__} holds LoRA adapters (lora_rank = {net.lora_rank})")
+
+
 def scrub_step(student, teacher, optimizer, criterion, x, y, *, maximize, kd_T, sgda_gamma, sgda_alpha, dist=None):
     """One iteration of either loop of the reference's baselines/SCRUBtrain.py on trainable FFN weights: the student's forward in its
     current mode, the teacher's under torch.no_grad(), the distillation KL between the two (util/sgda_utils.py, DistillKL(kd_T)) and
@@ -343,19 +360,11 @@ def scrub_step(student, teacher, optimizer, criterion, x, y, *, maximize, kd_T, 
     keeps its semantics: CE comes from the criterion and kd_ce runs with c_ce = 0. One backward per optimizer step: the overflow guard the
     optimizer reads is this backward's. Returns a DEVICE tensor [kd, ce, total] (ce is 0 on a max step; no host sync).
     Single process, eager: a process group and GraphedStep are refused, as ffn_reg_step refuses them."""
-    if _world() > 1:
-        raise RuntimeError(f"gs-lora_amd: scrub_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
-    if isinstance(student, GraphedStep) or isinstance(optimizer, GraphedStep):
-        raise RuntimeError(f"gs-lora_amd: scrub_step is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+    _refuse_group_and_graph("scrub_step", student, optimizer)
     _check_not_replicated(student)
     net = student.module if isinstance(student, nn.DataParallel) else student
     tnet = teacher.module if isinstance(teacher, nn.DataParallel) else teacher
-    if not getattr(net, "trainable_ffn", ""):
-        raise RuntimeError(f"gs-lora_amd: scrub_step trains the FFN linears of a ViT_face / ViTs_face built with lora_rank = 0 (the reference's "
-                           f"--only_ffn rule); {type(net).__name__} has no FFN weights that train on the HIP path")
-    if getattr(net, "lora_rank", 0) > 0:
-        raise RuntimeError(f"gs-lora_amd: scrub_step trains the FFN linears of a model built with lora_rank = 0 (the reference's --only_ffn rule); "
-                           f"this {type(net).__name__} holds LoRA adapters (lora_rank = {net.lora_rank})")
+    _refuse_unless_ffn_trains_without_lora("scrub_step", net)
     from . import kd as kdm
     xin = _model_input(net, x)
     logits, _ = student(xin, y)
@@ -401,10 +410,7 @@ def distill_step(student, teacher, optimizer, criterion, x_f, y_f, x_r, y_r, *, 
     is not plain nn.CrossEntropyLoss keeps its semantics through torch on the segments. Then zero_grad, one backward, optimizer.step().
     Returns a DEVICE tensor [ce_f, reg, ce_aux, total] (no host sync): reg is the DER / FDR distance, an exact 0 for "lwf"; ce_aux is CE_r
     for "lwf", CE_n for DER++, 0 otherwise. Single process, eager: a process group and GraphedStep are refused, as scrub_step refuses them."""
-    if _world() > 1:
-        raise RuntimeError(f"gs-lora_amd: distill_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
-    if isinstance(student, GraphedStep) or isinstance(optimizer, GraphedStep):
-        raise RuntimeError(f"gs-lora_amd: distill_step is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+    _refuse_group_and_graph("distill_step", student, optimizer)
     if method not in DISTILL_METHODS:
         raise ValueError(f"distill_step: method must be one of {DISTILL_METHODS}, got {method!r}")
     if (x_n is None) != (y_n is None) or (x_n is not None and method != "der"):
@@ -412,12 +418,7 @@ def distill_step(student, teacher, optimizer, criterion, x_f, y_f, x_r, y_r, *, 
     _check_not_replicated(student)
     net = student.module if isinstance(student, nn.DataParallel) else student
     tnet = teacher.module if isinstance(teacher, nn.DataParallel) else teacher
-    if not getattr(net, "trainable_ffn", ""):
-        raise RuntimeError(f"gs-lora_amd: distill_step trains the FFN linears of a ViT_face / ViTs_face built with lora_rank = 0 (the reference's "
-                           f"--only_ffn rule); {type(net).__name__} has no FFN weights that train on the HIP path")
-    if getattr(net, "lora_rank", 0) > 0:
-        raise RuntimeError(f"gs-lora_amd: distill_step trains the FFN linears of a model built with lora_rank = 0 (the reference's --only_ffn rule); "
-                           f"this {type(net).__name__} holds LoRA adapters (lora_rank = {net.lora_rank})")
+    _refuse_unless_ffn_trains_without_lora("distill_step", net)
     parts = [(x_f, y_f), (x_r, y_r)] + ([(x_n, y_n)] if x_n is not None else [])
     sizes = [x.size(0) for x, _ in parts]
     nf, nr = sizes[0], sizes[1]
@@ -499,10 +500,7 @@ def lirf_step(student_low, deposit_low, teacher_low, teacher_up, optimizer, crit
 
     Returns a DEVICE tensor [CE, AT, KP, PT_RE, total, REPLAY], the order of the reference's meters (no host sync). Single process,
     eager: a process group, GraphedStep, nn.DataParallel over several devices and a student that holds LoRA are refused."""
-    if _world() > 1:
-        raise RuntimeError(f"gs-lora_amd: lirf_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
-    if isinstance(student_low, GraphedStep) or isinstance(optimizer, GraphedStep):
-        raise RuntimeError(f"gs-lora_amd: lirf_step is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
+    _refuse_group_and_graph("lirf_step", student_low, optimizer)
     nets = []
     for m in (student_low, deposit_low, teacher_low, teacher_up):
         _check_not_replicated(m)

@@ -1,5 +1,5 @@
 """CPU tests of the LwF / DER / DER++ / FDR baselines: the fifth product library's ABI (header, version script, bindings and exported symbols
-agree; the other four libraries are what they were), lazy loading, no spilled register in its kernels, the launch rule gsf_rowdist_plan, every
+agree), lazy loading, no spilled register in its kernels, the launch rule gsf_rowdist_plan, every
 refusal with its text, the three loops' signatures and remain-draw order against the reference's recorded ones, the exact zero of LwF's
 distillation term, and the refusals distill_step makes before any launch. The arithmetic is tested on the GPU (tests/test_hip_fd_kernels.py,
 tests/test_hip_distill.py)."""
@@ -7,31 +7,25 @@ import inspect
 import json
 import os
 import re
-import struct
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
+
+from product_libs import exported, kernel_notes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {"gsf_last_error", "gsf_rowdist_plan", "gsf_rowdist_ws_elems", "gsf_rowdist_fwd", "gsf_rowdist_bwd"}
 METHODS = ("lwf", "der", "derpp", "fdr")
 
 
-def exported(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    return {ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln}
-
-
 def test_header_version_script_bindings_and_exports_of_the_fifth_library_agree():
     from gslora_hip import _lib_fd, build
     header = open(os.path.join(ROOT, "include", "gslora_fd.h")).read()
     protos = dict(re.findall(r"GSL_API [a-z *]+\b(gsf_[a-z0-9_]+)\(([^;]*)\);", header))
-    assert set(protos) == set(_lib_fd.SIGNATURES) == exported(build.OUT_FD) == ENTRY_POINTS
+    assert set(protos) == set(_lib_fd.SIGNATURES) == exported(build.side_out("fd")) == ENTRY_POINTS
     for name, argtypes in _lib_fd.SIGNATURES.items():
         proto = protos[name]
         n = 0 if proto.strip() in ("", "void") else len(proto.split(","))
@@ -43,20 +37,6 @@ def test_header_version_script_bindings_and_exports_of_the_fifth_library_agree()
     enums = dict(re.findall(r"(GSF_[A-Z]+) = (\d)", header))
     assert enums == {"GSF_WAVE": str(_lib_fd.FD_WAVE), "GSF_BLOCK": str(_lib_fd.FD_BLOCK), "GSF_SQ": str(_lib_fd.FD_SQ),
                      "GSF_ROWNORM": str(_lib_fd.FD_ROWNORM)}
-
-
-def test_the_other_four_libraries_are_untouched():
-    from gslora_hip import _lib, _lib_kd, _lib_reg, _lib_train, build
-    first, second, third, fourth, fifth = (exported(p) for p in (build.OUT, build.OUT_TRAIN, build.OUT_REG, build.OUT_KD, build.OUT_FD))
-    assert first == set(_lib.SIGNATURES) and len(first) == 57
-    assert second == set(_lib_train.SIGNATURES) and len(second) == 7
-    assert third == set(_lib_reg.SIGNATURES) and len(third) == 8
-    assert fourth == set(_lib_kd.SIGNATURES) and len(fourth) == 8
-    assert all(n.startswith("gsf_") for n in fifth)
-    assert not any(n.startswith("gsf_") for n in first | second | third | fourth)
-    assert build.needs_build_fd() is False and callable(build.build_fd) and build.OUT_FD.endswith("libgslora_fd.so")
-    src = inspect.getsource(build.build)
-    assert "build_fd(force=force, verbose=verbose)" in src and "build_kd(force=force, verbose=verbose)" in src
 
 
 def test_importing_the_new_modules_and_collecting_the_gpu_tests_opens_no_library():
@@ -73,34 +53,11 @@ def test_importing_the_new_modules_and_collecting_the_gpu_tests_opens_no_library
 
 
 def test_no_kernel_of_the_fifth_library_spills_registers():
-    """The reading of tests/test_scrub_host.py's test of the fourth library: every gfx950 kernel of libgslora_fd.so declares
+    """Read from the code-object notes (product_libs.kernel_notes): every gfx950 kernel of libgslora_fd.so declares
     .vgpr_spill_count 0 and no private segment, and is bound by __launch_bounds__(256)."""
     from gslora_hip import build as B
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not in this image")
-    data = open(B.OUT_FD, "rb").read()
-    kernels, bad = [], []
-    with tempfile.TemporaryDirectory() as d:
-        for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data):
-            base = m.start()
-            off = base + 32
-            for _ in range(struct.unpack_from("<Q", data, base + 24)[0]):
-                o, sz, tl = struct.unpack_from("<QQQ", data, off); off += 24
-                triple = data[off:off + tl].decode(); off += tl
-                if "gfx950" not in triple or not sz:
-                    continue
-                fn = os.path.join(d, "co.elf")
-                open(fn, "wb").write(data[base + o:base + o + sz])
-                notes = subprocess.run([readelf, "--notes", fn], capture_output=True, text=True, check=True).stdout
-                for blk in notes.split("- .agpr_count")[1:]:
-                    name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                    kernels.append(name)
-                    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1))
-                    priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
-                    wg = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-                    if spill or priv or wg != 256:
-                        bad.append((name, spill, priv, wg))
+    notes = kernel_notes(B.side_out("fd"))
+    kernels, bad = [k[0] for k in notes], [k for k in notes if k[1] or k[2] or k[3] != 256]
     # rows (wave, block) x (16-byte, 4-byte), reduce, bwd (wave, block) x (16-byte, 4-byte)
     assert len(kernels) == 9 and sum("fd_rows" in k for k in kernels) == 4 and sum("fd_bwd" in k for k in kernels) == 4, kernels
     assert not bad, bad

@@ -3,10 +3,8 @@ what it was), no spilled register in its kernels, the trainability rule and its 
 generator. The arithmetic is tested on the GPU (tests/test_hip_wgrad_edges.py, test_hip_reg_quad.py, test_hip_ffn_train.py)."""
 import os
 import re
-import struct
 import subprocess
 import sys
-import tempfile
 from types import SimpleNamespace
 
 import numpy as np
@@ -14,16 +12,11 @@ import pytest
 import torch
 
 from oracle import recipe
+from product_libs import exported, kernel_notes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = ("ffn_train_small2_b3", "ffn_l2_small_engine")
 ARGS = SimpleNamespace(opt="adamw", lr=1e-2, weight_decay=0.05, opt_eps=1e-8, opt_betas=None)
-
-
-def exported(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    return {ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln}
 
 
 def make(lora_rank=0, cls=None, **kw):
@@ -48,7 +41,7 @@ def test_header_bindings_and_exports_of_the_second_library_agree():
     from gslora_hip import _lib_train, build
     header = open(os.path.join(ROOT, "include", "gslora_train.h")).read()
     declared = set(re.findall(r"\b(gst_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib_train.SIGNATURES) == exported(build.OUT_TRAIN)
+    assert declared == set(_lib_train.SIGNATURES) == exported(build.side_out("train"))
     assert {"gst_wgrad", "gst_wgrad_plan", "gst_wgrad_ws_elems", "gst_reg_quad_fwd", "gst_reg_quad_bwd"} <= declared
     for name, argtypes in _lib_train.SIGNATURES.items():
         proto = re.search(r"GSL_API [a-z *]+\b" + name + r"\(([^;]*)\);", header).group(1)
@@ -63,7 +56,7 @@ def test_the_first_library_keeps_its_abi():
     header = open(os.path.join(ROOT, "include", "gslora_hip.h")).read()
     declared = set(re.findall(r"\b(gsl_[a-z0-9_]+)\s*\(", header)) - {"gsl_dropout_keep"}
     assert declared == set(_lib.SIGNATURES) == exported(build.OUT) and len(declared) == 57
-    assert not any(n.startswith("gst_") for n in exported(build.OUT)) and not any(n.startswith("gsl_") for n in exported(build.OUT_TRAIN))
+    assert not any(n.startswith("gst_") for n in exported(build.OUT)) and not any(n.startswith("gsl_") for n in exported(build.side_out("train")))
 
 
 def test_the_second_library_is_opened_lazily():
@@ -76,34 +69,11 @@ def test_the_second_library_is_opened_lazily():
 
 
 def test_no_kernel_of_the_second_library_spills_registers():
-    """The reading of tests/test_host_logic.py's test of the first library: every gfx950 kernel of libgslora_train.so declares .vgpr_spill_count 0
+    """Read from the code-object notes (product_libs.kernel_notes): every gfx950 kernel of libgslora_train.so declares .vgpr_spill_count 0
     and no private segment; every kernel is bound by __launch_bounds__ (a .max_flat_workgroup_size of 256, not the default 1024)."""
     from gslora_hip import build as B
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not in this image")
-    data = open(B.OUT_TRAIN, "rb").read()
-    kernels, bad = [], []
-    with tempfile.TemporaryDirectory() as d:
-        for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data):
-            base = m.start()
-            off = base + 32
-            for _ in range(struct.unpack_from("<Q", data, base + 24)[0]):
-                o, sz, tl = struct.unpack_from("<QQQ", data, off); off += 24
-                triple = data[off:off + tl].decode(); off += tl
-                if "gfx950" not in triple or not sz:
-                    continue
-                fn = os.path.join(d, "co.elf")
-                open(fn, "wb").write(data[base + o:base + o + sz])
-                notes = subprocess.run([readelf, "--notes", fn], capture_output=True, text=True, check=True).stdout
-                for blk in notes.split("- .agpr_count")[1:]:
-                    name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                    kernels.append(name)
-                    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1))
-                    priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
-                    wg = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-                    if spill or priv or wg != 256:
-                        bad.append((name, spill, priv, wg))
+    notes = kernel_notes(B.side_out("train"))
+    kernels, bad = [k[0] for k in notes], [k for k in notes if k[1] or k[2] or k[3] != 256]
     assert len(kernels) == 7 and sum("wgrad_partial" in k for k in kernels) == 3, kernels      # three formats of the GEMM, its reduce, three of the regulariser
     assert not bad, bad
 

@@ -7,13 +7,13 @@ import inspect
 import json
 import os
 import re
-import struct
 import subprocess
 import sys
-import tempfile
 
 import pytest
 import torch
+
+from product_libs import exported, kernel_notes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {"gsa_last_error", "gsa_at_plan", "gsa_at_ws_elems", "gsa_at_fwd", "gsa_at_bwd"}
@@ -144,17 +144,11 @@ def test_lirf_step_signature_and_refusals_before_any_launch(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the library
-def exported(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    return {ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln}
-
-
 def test_header_version_script_bindings_and_exports_of_the_sixth_library_agree():
     from gslora_hip import _lib_at, build
     header = open(os.path.join(ROOT, "include", "gslora_at.h")).read()
     protos = dict(re.findall(r"GSL_API [a-z *]+\b(gsa_[a-z0-9_]+)\(([^;]*)\);", header))
-    assert set(protos) == set(_lib_at.SIGNATURES) == exported(build.OUT_AT) == ENTRY_POINTS
+    assert set(protos) == set(_lib_at.SIGNATURES) == exported(build.side_out("at")) == ENTRY_POINTS
     for name, argtypes in _lib_at.SIGNATURES.items():
         proto = protos[name]
         n = 0 if proto.strip() in ("", "void") else len(proto.split(","))
@@ -165,18 +159,6 @@ def test_header_version_script_bindings_and_exports_of_the_sixth_library_agree()
     assert (_lib_at.MAX_T, _lib_at.MAX_D) == tuple(int(re.search(rf"#define {k} (\d+)", header).group(1)) for k in ("GSA_MAX_T", "GSA_MAX_D"))
     src = open(os.path.join(ROOT, "gs-lora_amd", "csrc", "at.hip")).read()
     assert "getenv" not in src and "atomic" not in src.lower(), "no environment reads, no atomics"
-
-
-def test_the_build_knows_the_sixth_library_and_the_others_are_untouched():
-    from gslora_hip import _lib, _lib_fd, _lib_kd, _lib_reg, _lib_train, build
-    libs = [exported(p) for p in (build.OUT, build.OUT_TRAIN, build.OUT_REG, build.OUT_KD, build.OUT_FD)]
-    for got, mod, n in zip(libs, (_lib, _lib_train, _lib_reg, _lib_kd, _lib_fd), (57, 7, 8, 8, 5)):
-        assert got == set(mod.SIGNATURES) and len(got) == n
-        assert not any(s.startswith("gsa_") for s in got)
-    assert build.needs_build_at() is False and callable(build.build_at) and build.OUT_AT.endswith("libgslora_at.so")
-    assert build.AT_SOURCES == ["at.hip"] and "exports_at.map" in build.AT_HEADERS
-    src = inspect.getsource(build.build)
-    assert "build_at(force=force, verbose=verbose)" in src and "build_fd(force=force, verbose=verbose)" in src
 
 
 def test_the_sixth_library_cross_compiles_for_gfx950_without_spills(tmp_path):
@@ -190,31 +172,8 @@ def test_the_sixth_library_cross_compiles_for_gfx950_without_spills(tmp_path):
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-c",
                            os.path.join(B.CSRC, "at.hip"), "-o", obj])
     assert os.path.getsize(obj) > 0
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not in this image")
-    data = open(B.OUT_AT, "rb").read()
-    kernels, bad = [], []
-    with tempfile.TemporaryDirectory() as d:
-        for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data):
-            base = m.start()
-            off = base + 32
-            for _ in range(struct.unpack_from("<Q", data, base + 24)[0]):
-                o, sz, tl = struct.unpack_from("<QQQ", data, off); off += 24
-                triple = data[off:off + tl].decode(); off += tl
-                if "gfx950" not in triple or not sz:
-                    continue
-                fn = os.path.join(d, "co.elf")
-                open(fn, "wb").write(data[base + o:base + o + sz])
-                notes = subprocess.run([readelf, "--notes", fn], capture_output=True, text=True, check=True).stdout
-                for blk in notes.split("- .agpr_count")[1:]:
-                    name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                    kernels.append(name)
-                    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1))
-                    priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
-                    wg = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-                    if spill or priv or wg != 256:
-                        bad.append((name, spill, priv, wg))
+    notes = kernel_notes(B.side_out("at"))
+    kernels, bad = [k[0] for k in notes], [k for k in notes if k[1] or k[2] or k[3] != 256]
     # sums (f32, f16, bf16), images, value, backward (3 stream types x 3 gradient-stream types)
     assert len(kernels) == 14 and sum("at_sumsq" in k for k in kernels) == 3 and sum("at_bwd" in k for k in kernels) == 9, kernels
     assert not bad, bad

@@ -1,18 +1,18 @@
-"""CPU tests of the regularisation baselines (L2 / EWC / MAS): the third product library's ABI (header, bindings and exported symbols agree;
-the first two libraries are what they were), lazy loading, no spilled register in its kernels, the host-side layout of the batched
+"""CPU tests of the regularisation baselines (L2 / EWC / MAS): the third product library's ABI (header, bindings and exported symbols agree),
+lazy loading, no spilled register in its kernels, the host-side layout of the batched
 regulariser against the partition rule of gst_reg_quad_fwd, the epoch loop's signature, the fixtures and the driver's refusal without a GPU.
 The arithmetic is tested on the GPU (tests/test_hip_reg_kernels.py, tests/test_hip_reg_baselines.py)."""
 import inspect
 import os
 import re
-import struct
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
+
+from product_libs import exported, kernel_notes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = ("importance_small", "reg_epoch_small_engine")
@@ -21,17 +21,11 @@ REFERENCE_PARAMETERS = ["model", "criterion", "data_loader_cl_forget", "optimize
                         "forget_acc_before", "highest_H_mean", "cfg", "testloader_open"]      # reference engine_cl.py:463-483
 
 
-def exported(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    return {ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln}
-
-
 def test_header_bindings_and_exports_of_the_third_library_agree():
     from gslora_hip import _lib_reg, build
     header = open(os.path.join(ROOT, "include", "gslora_reg.h")).read()
     protos = dict(re.findall(r"GSL_API [a-z *]+\b(gsr_[a-z0-9_]+)\(([^;]*)\);", header))
-    assert set(protos) == set(_lib_reg.SIGNATURES) == exported(build.OUT_REG)
+    assert set(protos) == set(_lib_reg.SIGNATURES) == exported(build.side_out("reg"))
     assert {"gsr_importance_acc", "gsr_sq_mean_fwd", "gsr_sq_mean_bwd", "gsr_sq_mean_ws_elems", "gsr_reg_multi_layout", "gsr_reg_multi_fwd",
             "gsr_reg_multi_bwd", "gsr_last_error"} == set(protos)
     for name, argtypes in _lib_reg.SIGNATURES.items():
@@ -48,16 +42,6 @@ def test_header_bindings_and_exports_of_the_third_library_agree():
     assert ctypes.sizeof(_lib_reg.RegEntry) == 56
 
 
-def test_the_first_two_libraries_are_untouched():
-    from gslora_hip import _lib, _lib_train, build
-    first, second, third = exported(build.OUT), exported(build.OUT_TRAIN), exported(build.OUT_REG)
-    assert first == set(_lib.SIGNATURES) and len(first) == 57
-    assert second == set(_lib_train.SIGNATURES) and len(second) == 7
-    assert not any(n.startswith(("gsl_", "gst_")) for n in third) and all(n.startswith("gsr_") for n in third)
-    assert not any(n.startswith("gsr_") for n in first | second)
-    assert build.needs_build_reg() is False and callable(build.build_reg) and build.OUT_REG.endswith("libgslora_reg.so")
-
-
 def test_the_third_library_is_opened_lazily():
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "import gslora_hip._lib_reg as r, gslora_hip.reg, gslora_hip.step, engine_reg, engine_cl, driver_reg\n"
@@ -69,34 +53,11 @@ def test_the_third_library_is_opened_lazily():
 
 
 def test_no_kernel_of_the_third_library_spills_registers():
-    """The reading of tests/test_ffn_train_host.py's test of the second library: every gfx950 kernel of libgslora_reg.so declares
+    """Read from the code-object notes (product_libs.kernel_notes): every gfx950 kernel of libgslora_reg.so declares
     .vgpr_spill_count 0 and no private segment, and is bound by __launch_bounds__(256)."""
     from gslora_hip import build as B
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not in this image")
-    data = open(B.OUT_REG, "rb").read()
-    kernels, bad = [], []
-    with tempfile.TemporaryDirectory() as d:
-        for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data):
-            base = m.start()
-            off = base + 32
-            for _ in range(struct.unpack_from("<Q", data, base + 24)[0]):
-                o, sz, tl = struct.unpack_from("<QQQ", data, off); off += 24
-                triple = data[off:off + tl].decode(); off += tl
-                if "gfx950" not in triple or not sz:
-                    continue
-                fn = os.path.join(d, "co.elf")
-                open(fn, "wb").write(data[base + o:base + o + sz])
-                notes = subprocess.run([readelf, "--notes", fn], capture_output=True, text=True, check=True).stdout
-                for blk in notes.split("- .agpr_count")[1:]:
-                    name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                    kernels.append(name)
-                    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1))
-                    priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
-                    wg = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-                    if spill or priv or wg != 256:
-                        bad.append((name, spill, priv, wg))
+    notes = kernel_notes(B.side_out("reg"))
+    kernels, bad = [k[0] for k in notes], [k for k in notes if k[1] or k[2] or k[3] != 256]
     # importance_acc; sq_mean partial, reduce, bwd; reg_multi partial, reduce, bwd
     assert len(kernels) == 7 and sum("reg_multi" in k for k in kernels) == 3 and sum("sq_mean" in k for k in kernels) == 3, kernels
     assert not bad, bad

@@ -1,36 +1,30 @@
-"""CPU tests of the SCRUB loss side: the fourth product library's ABI (header, version script, bindings and exported symbols agree; the other
-three libraries are what they were), lazy loading, no spilled register in its kernels, the launch rule gsk_kd_plan, the host-side layout of
+"""CPU tests of the SCRUB loss side: the fourth product library's ABI (header, version script, bindings and exported symbols agree),
+lazy loading, no spilled register in its kernels, the launch rule gsk_kd_plan, the host-side layout of
 the batched parameter distance, every refusal with its text, the step schedule of util/sgda_utils.py against values worked by hand, and the
 refusals scrub_step makes before any launch. The arithmetic is tested on the GPU (tests/test_hip_kd_kernels.py, tests/test_hip_scrub.py)."""
 import ctypes
 import inspect
 import os
 import re
-import struct
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 import torch
+
+from product_libs import exported, kernel_notes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {"gsk_last_error", "gsk_kd_plan", "gsk_kd_ws_elems", "gsk_kd_ce_fwd", "gsk_kd_ce_bwd", "gsk_param_dist_layout",
                 "gsk_param_dist_fwd", "gsk_param_dist_bwd"}
 
 
-def exported(so):
-    nm = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True)
-    assert nm.returncode == 0, nm.stderr
-    return {ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln}
-
-
 def test_header_version_script_bindings_and_exports_of_the_fourth_library_agree():
     from gslora_hip import _lib_kd, build
     header = open(os.path.join(ROOT, "include", "gslora_kd.h")).read()
     protos = dict(re.findall(r"GSL_API [a-z *]+\b(gsk_[a-z0-9_]+)\(([^;]*)\);", header))
-    assert set(protos) == set(_lib_kd.SIGNATURES) == exported(build.OUT_KD) == ENTRY_POINTS
+    assert set(protos) == set(_lib_kd.SIGNATURES) == exported(build.side_out("kd")) == ENTRY_POINTS
     for name, argtypes in _lib_kd.SIGNATURES.items():
         proto = protos[name]
         n = 0 if proto.strip() in ("", "void") else len(proto.split(","))
@@ -43,19 +37,6 @@ def test_header_version_script_bindings_and_exports_of_the_fourth_library_agree(
     fields = re.findall(r"\b(\w+);", body)
     assert fields == [f[0] for f in _lib_kd.DistEntry._fields_]
     assert ctypes.sizeof(_lib_kd.DistEntry) == 56
-
-
-def test_the_other_three_libraries_are_untouched():
-    from gslora_hip import _lib, _lib_reg, _lib_train, build
-    first, second, third, fourth = (exported(p) for p in (build.OUT, build.OUT_TRAIN, build.OUT_REG, build.OUT_KD))
-    assert first == set(_lib.SIGNATURES) and len(first) == 57
-    assert second == set(_lib_train.SIGNATURES) and len(second) == 7
-    assert third == set(_lib_reg.SIGNATURES) and len(third) == 8
-    assert all(n.startswith("gsk_") for n in fourth)
-    assert not any(n.startswith("gsk_") for n in first | second | third)
-    assert build.needs_build_kd() is False and callable(build.build_kd) and build.OUT_KD.endswith("libgslora_kd.so")
-    src = inspect.getsource(build.build)
-    assert "build_kd(force=force, verbose=verbose)" in src and "build_reg(force=force, verbose=verbose)" in src
 
 
 def test_collecting_the_gpu_tests_opens_no_library():
@@ -84,34 +65,11 @@ def test_the_fourth_library_is_opened_lazily():
 
 
 def test_no_kernel_of_the_fourth_library_spills_registers():
-    """The reading of tests/test_reg_baselines_host.py's test of the third library: every gfx950 kernel of libgslora_kd.so declares
+    """Read from the code-object notes (product_libs.kernel_notes): every gfx950 kernel of libgslora_kd.so declares
     .vgpr_spill_count 0 and no private segment, and is bound by __launch_bounds__(256)."""
     from gslora_hip import build as B
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        pytest.skip("llvm-readelf not in this image")
-    data = open(B.OUT_KD, "rb").read()
-    kernels, bad = [], []
-    with tempfile.TemporaryDirectory() as d:
-        for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", data):
-            base = m.start()
-            off = base + 32
-            for _ in range(struct.unpack_from("<Q", data, base + 24)[0]):
-                o, sz, tl = struct.unpack_from("<QQQ", data, off); off += 24
-                triple = data[off:off + tl].decode(); off += tl
-                if "gfx950" not in triple or not sz:
-                    continue
-                fn = os.path.join(d, "co.elf")
-                open(fn, "wb").write(data[base + o:base + o + sz])
-                notes = subprocess.run([readelf, "--notes", fn], capture_output=True, text=True, check=True).stdout
-                for blk in notes.split("- .agpr_count")[1:]:
-                    name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                    kernels.append(name)
-                    spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1))
-                    priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
-                    wg = int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", blk).group(1))
-                    if spill or priv or wg != 256:
-                        bad.append((name, spill, priv, wg))
+    notes = kernel_notes(B.side_out("kd"))
+    kernels, bad = [k[0] for k in notes], [k for k in notes if k[1] or k[2] or k[3] != 256]
     # kd rows (wave, block), reduce, bwd (wave, block); param_dist partial, reduce, bwd
     assert len(kernels) == 8 and sum("kd_" in k for k in kernels) == 5 and sum("param_dist" in k for k in kernels) == 3, kernels
     assert not bad, bad
