@@ -73,6 +73,9 @@ LN_LORA = False
 # layout of the stashed qkv tensor in bf16 mode: head-major [B][H][3][T][64] (the QKV GEMM's store permutes, the attention kernels
 # read contiguous per-head panels); False = token-major [B*T, 3*H*64] as the reference's to_qkv output (always used in f32 mode)
 QKV_HEAD_MAJOR = True
+# ... from this many tokens per image on: the permuting copy-out of the head-major store walks 8 rows at a step and may cross one image
+# boundary in it (check_epilogue refuses STORE_QKV_HM below T = 8, csrc/gemm.hip); a shorter sequence takes the token-major layout
+QKV_HM_MIN_T = 8
 
 
 class BlockSpec:
@@ -675,9 +678,10 @@ class ViTRunner:
         else:
             w, cw, b, ln = self.w(f"qkv{i}", blk.qkv_w, dt), None, (None if blk.qkv_b is None else blk.qkv_b.detach()), {}
         if not qsplit:
-            hm = 1 if (QKV_HEAD_MAJOR and dt in OP16) else 0
+            hm = 1 if (QKV_HEAD_MAJOR and dt in OP16 and T >= QKV_HM_MIN_T) else 0
             epi = (L.EPI_STORE_QKV_HM_LN if hm else L.EPI_STORE_LN) if fold else (L.EPI_STORE_QKV_HM if hm else L.EPI_STORE)
-            self._lora_finish(c, st, w, qkv, dict(epilogue=epi, T=T, aux=cw, bias=b, **ln))
+            # (T is the head-major store's; the token-major STORE_LN would read it as the row stride of mean / rstd: 0 = one per row)
+            self._lora_finish(c, st, w, qkv, dict(epilogue=epi, T=0 if (fold and not hm) else T, aux=cw, bias=b, **ln))
             return qkv, None, st.u, hm
         # K and V for every token, Q for the cls rows only: rows inner .. 3*inner of the fused weight (and of W', c, d) are K | V
         rows = lambda t, s: None if t is None else t[s]

@@ -221,7 +221,7 @@ def test_backward_instantiations(ops, D, T, S, X):
 # ---------------------------------------------------------------------------------------------------------------- placements
 @pytest.mark.parametrize("dt", [F32, BF16, F16], ids=ident)
 @pytest.mark.parametrize("placement", ["colblock", "cls"])
-@pytest.mark.parametrize("D", [128, 256])
+@pytest.mark.parametrize("D", [128, 256, 512, 1024])
 def test_strided_placements_equal_the_contiguous_call(ops, D, placement, dt):
     """colblock: x a column block (rows of D + 64 elements, column offset 8). cls: x, dres and dx rows T D apart, dx updated in place
     (dres aliased to it), dy and dxb dense, dropout with drop_row_stride = T D."""
@@ -240,7 +240,7 @@ def test_strided_placements_equal_the_contiguous_call(ops, D, placement, dt):
 
 
 @pytest.mark.parametrize("dt", [F32, BF16, F16], ids=ident)
-@pytest.mark.parametrize("D", [128, 256])
+@pytest.mark.parametrize("D", [64, 128, 256, 768])
 def test_compact_dres_equals_the_dense_zero_filled_call(ops, D, dt):
     what = f"d{D} compact {NAME[dt]}"
     M = 37
@@ -255,9 +255,10 @@ def test_compact_dres_equals_the_dense_zero_filled_call(ops, D, dt):
 
 @pytest.mark.parametrize("dt", [F32, BF16, F16], ids=ident)
 @pytest.mark.parametrize("strided", [False, True])
-@pytest.mark.parametrize("D", [128, 512])
+@pytest.mark.parametrize("D", [128, 256, 512, 768, 1024])
 def test_dropout_copy(ops, D, strided, dt):
-    """p = 0.5 on the scalar (D = 128) and the 4-wide (D = 512) counter path: dropped elements of dxb exactly 0, kept ones within the bound
+    """p = 0.5 on the scalar (D = 128: one or two elements per lane) and the 4-wide counter path (D = 256 .. 1024: VEC = 4 from four
+    elements per lane on, at each of its row lengths): dropped elements of dxb exactly 0, kept ones within the bound
     of 2 dx, dx itself unmasked."""
     what = f"d{D} drop {'T D' if strided else 'D'} {NAME[dt]}"
     M = 37
