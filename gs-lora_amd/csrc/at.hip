@@ -1,8 +1,9 @@
 // at.hip — libgslora_at.so: the attention-transfer term of the LIRF baseline (include/gslora_at.h).
 //   gsa_at_fwd   at_loss of a student's and a teacher's [B, T, D] mid stream, with the table G that carries its gradient
 //   gsa_at_bwd   the gradient added in place to the stream gradient at the boundary between the two half networks
-// A sixth product library: its own error string, nothing shared with the other five but the headers.
-#include "gsl_common.h"
+// A sixth product library: its own error string; nothing shared with libgslora_hip.so but the headers (gsl_common.h and the public ones),
+// and with the other side libraries gsl_chunks.h: the alignment predicate and the one-workgroup sum of stage 3.
+#include "gsl_chunks.h"
 
 #include "../../include/gslora_at.h"
 
@@ -16,8 +17,6 @@ constexpr int AT_TARGET_GROUPS = 512;      // .. and the token axis is split unt
 constexpr int AT_MAX_SPLIT = 64;
 constexpr float AT_EPS = 1e-12f;           // F.normalize's eps
 constexpr float AT_THRESHOLD = 0.005f;
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // N consecutive elements as floats: one 16-byte access (N * sizeof(E) == 16) or one 8-byte access (N == 4 of a 16-bit type)
 template <typename E, int N> struct Vec;
@@ -156,9 +155,7 @@ __global__ __launch_bounds__(256) void at_image_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void at_value_kernel(const float* __restrict__ lossp, int B, int D, float* __restrict__ loss) {
 #pragma clang fp contract(off)
   __shared__ float sm[16];
-  float acc = 0.f;
-  for (int b = threadIdx.x; b < B; b += 256) acc += lossp[b];
-  const float tot = block_sum(acc, sm);
+  const float tot = strided_sum(lossp, B, sm);
   if (threadIdx.x == 0) loss[0] = tot / ((float)B * (float)D);
 }
 

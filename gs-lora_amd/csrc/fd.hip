@@ -1,7 +1,8 @@
 // fd.hip — libgslora_fd.so: the function-distance term of the DER / DER++ and FDR baselines (include/gslora_fd.h).
 //   gsf_rowdist_*   the distance between a student's and a frozen teacher's [B, W] rows (embeddings: DER; logits: FDR) and its gradient
-// A fifth product library: its own error string, nothing shared with the other four but the headers.
-#include "gsl_common.h"
+// A fifth product library: its own error string; nothing shared with libgslora_hip.so but the headers (gsl_common.h and the public ones),
+// and with the other side libraries gsl_chunks.h: the alignment predicate and the one-workgroup sum of the reduce kernel.
+#include "gsl_chunks.h"
 
 #include "../../include/gslora_fd.h"
 
@@ -12,7 +13,6 @@ extern "C" const char* gsf_last_error(void) { return gsl::g_err; }
 
 constexpr int FD_WAVE_MAX_W = 1024;      // the plan's threshold: up to it a wave serves a row (at most four groups per lane)
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // every row of a [B, .] tensor with row stride ld starts on a 16-byte boundary
 static inline bool rows_aligned16(const void* p, long ld, int B) { return aligned16(p) && (B == 1 || (ld & 3) == 0); }
 
@@ -66,12 +66,7 @@ __global__ __launch_bounds__(256) void fd_rows_block_kernel(const float* __restr
 __global__ __launch_bounds__(256) void fd_reduce_kernel(const float* __restrict__ ws, int B, int mode, float* __restrict__ out1) {
 #pragma clang fp contract(off)
   __shared__ float sm[16];
-  float acc = 0.f;
-  for (int r = threadIdx.x; r < B; r += 256) {
-    const float s = ws[r];
-    acc += mode == GSF_ROWNORM ? sqrtf(s) : s;
-  }
-  const float tot = block_sum(acc, sm);
+  const float tot = strided_sum(ws, B, sm, [&](float s) { return mode == GSF_ROWNORM ? sqrtf(s) : s; });
   if (threadIdx.x == 0) {
     if (mode == GSF_ROWNORM) {
       out1[0] = tot / (float)B;

@@ -2,8 +2,9 @@
 //   gsk_kd_ce_*       DistillKL (reference util/sgda_utils.py) fused with the student's mean cross-entropy, and the gradient of both in one
 //                     pass over the two logit matrices
 //   gsk_param_dist_*  param_dist (util/sgda_utils.py) over every parameter at once: two launches forward, one backward
-// A fourth product library: its own error string, nothing shared with the other three but the headers.
-#include "gsl_common.h"
+// A fourth product library: its own error string; nothing shared with libgslora_hip.so but the headers (gsl_common.h and the public ones),
+// and with the other side libraries gsl_chunks.h: gsk_param_dist_* are its chunked sum, owner search and chunk walk.
+#include "gsl_chunks.h"
 
 #include "../../include/gslora_kd.h"
 
@@ -13,8 +14,6 @@ namespace gsl { thread_local char g_err[512] = {0}; }
 extern "C" const char* gsk_last_error(void) { return gsl::g_err; }
 
 #define GSK_NAN __int_as_float(0x7fc00000)
-
-static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 // =====================================================================================
 // gsk_kd_ce_*. The row walk is that of loss.hip (element c of a row belongs to thread c mod STRIDE, a thread visits its elements in
@@ -125,6 +124,8 @@ __global__ __launch_bounds__(256) void kd_ce_reduce_kernel(const float* __restri
                                                            float* __restrict__ out3) {
 #pragma clang fp contract(off)
   __shared__ float sm[16];
+  // (not two strided_sum calls: one loop keeps both loads of a trip in flight — two loops cost 3.8 us of 13.5 at B = 4096,
+  //  profiles/side_kernels_dedupe.md)
   float a = 0.f, b = 0.f;
   for (int r = threadIdx.x; r < B; r += 256) { a += ws[3 * (size_t)B + r]; b += ws[4 * (size_t)B + r]; }
   const float kd = block_sum(a, sm), ce = block_sum(b, sm);
@@ -248,10 +249,6 @@ extern "C" int gsk_kd_ce_bwd(const float* ys, long ld_s, const float* yt, long l
 // =====================================================================================
 // gsk_param_dist_*: the table is built on the host (gsk_param_dist_layout), the kernels look their entry up by workgroup index.
 // =====================================================================================
-constexpr int PD_MAX_BLOCKS = 1024;      // the partition rule of gsr_reg_multi_layout (csrc/reg.hip), restated in gslora_kd.h
-constexpr long PD_MIN_CHUNK = 1024;
-static inline int pd_blocks(long n) { return (int)min((long)PD_MAX_BLOCKS, (n + PD_MIN_CHUNK - 1) / PD_MIN_CHUNK); }
-
 extern "C" int gsk_param_dist_layout(const void* const* p, const void* const* q, const long* n, const int* trainable, int n_entries,
                                      gsk_dist_entry* table, long* total_blocks, long* bwd_blocks, long* g_elems) {
   GSL_CHECK_ARG(p && q && n && trainable && table, "null host array");
@@ -266,8 +263,8 @@ extern "C" int gsk_param_dist_layout(const void* const* p, const void* const* q,
     o.p = static_cast<const float*>(p[e]);
     o.q = static_cast<const float*>(q[e]);
     o.n = n[e];
-    o.nblk = pd_blocks(n[e]);
-    o.chunk = (n[e] + o.nblk - 1) / o.nblk;
+    o.nblk = chunk_blocks(n[e]);
+    o.chunk = chunk_len(n[e], o.nblk);
     o.blk0 = (int)blk;
     o.bblk0 = (int)bblk;
     o.pad_ = 0;
@@ -287,38 +284,16 @@ extern "C" int gsk_param_dist_layout(const void* const* p, const void* const* q,
   return GSL_OK;
 }
 
-// the entry that owns forward workgroup b: the last one whose blk0 <= b
-__device__ __forceinline__ int pd_find_fwd(const gsk_dist_entry* __restrict__ tab, int count, int b) {
-  int lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// the entry that owns backward workgroup b: the last one whose bblk0 <= b (a frozen entry shares its bblk0 with the trainable entry behind
-// it, which is the later of the two; frozen entries at the end hold bwd_blocks, beyond every b) — always a trainable one for b < bwd_blocks
-__device__ __forceinline__ int pd_find_bwd(const gsk_dist_entry* __restrict__ tab, int count, int b) {
-  int lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].bblk0 <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
+// The forward's owner is the last entry whose blk0 <= b. The backward's is the last one whose bblk0 <= b: a frozen entry shares its bblk0
+// with the trainable entry behind it, which is the later of the two; frozen entries at the end hold bwd_blocks, beyond every b — always a
+// trainable one for b < bwd_blocks.
 __global__ __launch_bounds__(256) void param_dist_partial_kernel(const gsk_dist_entry* __restrict__ tab, int n_entries, float* __restrict__ ws) {
   __shared__ float sm[16];
-  const gsk_dist_entry e = tab[pd_find_fwd(tab, n_entries, blockIdx.x)];
+  const gsk_dist_entry e = tab[chunk_owner(tab, n_entries, blockIdx.x, &gsk_dist_entry::blk0)];
   const float* __restrict__ p = e.p;
   const float* __restrict__ q = e.q;
   const long i0 = (long)(blockIdx.x - e.blk0) * e.chunk, i1 = min(e.n, i0 + e.chunk);
-  double acc = 0.0;
-  for (long i = i0 + threadIdx.x; i < i1; i += 256) {
-    const double d = (double)p[i] - (double)q[i];
-    acc += d * d;
-  }
-  const float s = block_sum((float)acc, sm);
+  const float s = chunk_partial(i0, i1, sm, [&](long i) { return quad_term(p, q, nullptr, i); });
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 
@@ -328,10 +303,7 @@ __global__ __launch_bounds__(256) void param_dist_reduce_kernel(const gsk_dist_e
   __shared__ float sm[16];
   float total = 0.f;
   for (int e = 0; e < n_entries; ++e) {
-    const int blk0 = tab[e].blk0, nblk = tab[e].nblk;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) s += ws[blk0 + i];
-    s = block_sum(s, sm);      // every thread holds the result
+    const float s = strided_sum(ws + tab[e].blk0, tab[e].nblk, sm);      // every thread holds the result
     const float nrm = sqrtf(s);
     if (threadIdx.x == 0) norms[e] = nrm;
     total = total + nrm;
@@ -343,7 +315,7 @@ __global__ __launch_bounds__(256) void param_dist_bwd_kernel(const gsk_dist_entr
                                                              const float* __restrict__ gout, const float* __restrict__ norms,
                                                              float* __restrict__ gbase) {
 #pragma clang fp contract(off)
-  const int k = pd_find_bwd(tab, n_entries, blockIdx.x);
+  const int k = chunk_owner(tab, n_entries, blockIdx.x, &gsk_dist_entry::bblk0);
   const gsk_dist_entry e = tab[k];
   if (e.goff < 0) return;      // (not reached for a table gsk_param_dist_layout made)
   const float* __restrict__ a = e.p;
@@ -355,13 +327,7 @@ __global__ __launch_bounds__(256) void param_dist_bwd_kernel(const gsk_dist_entr
   const bool zero = nrm == 0.f;
   const float coef = zero ? 0.f : (gout[0] * p) / nrm;
   const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(g);
-  long v0 = i1, nvec = 0;      // the vector body [v0, v0 + 4 nvec) of this chunk: from the first multiple of 4 at or behind i0
-  if ((bits & 15) == 0) {
-    v0 = min(i1, (i0 + 3) & ~3L);
-    nvec = (i1 - v0) / 4;
-  }
-  for (long v = threadIdx.x; v < nvec; v += 256) {
-    const long i = v0 + 4 * v;
+  chunk_walk(i0, i1, (bits & 15) == 0, [&](long i) {
     const float4 x = *reinterpret_cast<const float4*>(a + i);
     const float4 y = *reinterpret_cast<const float4*>(b + i);
     float4 o;
@@ -370,12 +336,7 @@ __global__ __launch_bounds__(256) void param_dist_bwd_kernel(const gsk_dist_entr
     o.z = zero ? 0.f : (x.z - y.z) * coef;
     o.w = zero ? 0.f : (x.w - y.w) * coef;
     *reinterpret_cast<float4*>(g + i) = o;
-  }
-  const long body_end = v0 + 4 * nvec, head = v0 - i0, nscalar = (i1 - i0) - 4 * nvec;      // [i0, v0) and [body_end, i1)
-  for (long j = threadIdx.x; j < nscalar; j += 256) {
-    const long i = j < head ? i0 + j : body_end + (j - head);
-    g[i] = zero ? 0.f : (a[i] - b[i]) * coef;
-  }
+  }, [&](long i) { g[i] = zero ? 0.f : (a[i] - b[i]) * coef; });
 }
 
 extern "C" int gsk_param_dist_fwd(const gsk_dist_entry* table_dev, int n_entries, long total_blocks, float p, float* out, float* norms, float* ws,

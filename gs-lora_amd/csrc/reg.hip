@@ -4,8 +4,9 @@
 //   gsr_sq_mean_*       mean(logits^2) and its gradient, the objective MAS differentiates (train/train_own_forget_cl.py:1548-1549)
 //   gsr_reg_multi_*     get_reg_loss (engine_cl.py:449-459) over every term and tensor at once, bit for bit the sequence of gst_reg_quad_*
 //                       calls of libgslora_train.so
-// A third product library: its own error string, nothing shared with the other two but the headers.
-#include "gsl_common.h"
+// A third product library: its own error string; nothing shared with libgslora_hip.so but the headers (gsl_common.h and the public ones),
+// and with the other side libraries gsl_chunks.h: gsr_reg_multi_fwd and gst_reg_quad_fwd are the same partition rule, chunk sum and term.
+#include "gsl_chunks.h"
 
 #include "../../include/gslora_reg.h"
 
@@ -14,12 +15,11 @@ using namespace gsl;
 namespace gsl { thread_local char g_err[512] = {0}; }
 extern "C" const char* gsr_last_error(void) { return gsl::g_err; }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 // =====================================================================================
 // gsr_importance_acc. Memory-bound: 8 bytes read and 4 written per element. The vector body starts at the first element where omega is
-// 16-byte aligned (g is aligned there too, or there is no vector body); the elements in front of and behind it go one by one.
+// 16-byte aligned (g is aligned there too, or there is no vector body); the elements in front of and behind it go one by one. (Not
+// chunk_walk: the split is made on the host from the pointers' residue — the pointers themselves need not be aligned — and the loops are
+// grid-stride.)
 // =====================================================================================
 constexpr int IA_MAX_BLOCKS = 2048;      // 256 CUs eight times over; the loops are grid-stride
 
@@ -80,30 +80,22 @@ extern "C" int gsr_importance_acc(float* omega, const float* g, long n, int kind
 }
 
 // =====================================================================================
-// gsr_sq_mean_*. The forward has the shape of gst_reg_quad_fwd: fixed chunks, f64 per thread, one ascending reduce.
+// gsr_sq_mean_*. The forward is the chunked sum of gsl_chunks.h: fixed chunks, f64 per thread, one ascending reduce.
 // =====================================================================================
-constexpr int RQ_MAX_BLOCKS = 1024;      // the partition rule of gst_reg_quad_fwd (csrc/train.hip), restated in gslora_reg.h
-constexpr long RQ_MIN_CHUNK = 1024;
-static inline int rq_blocks(long n) { return (int)min((long)RQ_MAX_BLOCKS, (n + RQ_MIN_CHUNK - 1) / RQ_MIN_CHUNK); }
-
 __global__ __launch_bounds__(256) void sq_mean_partial_kernel(const float* __restrict__ x, long ldx, int C, long n, long chunk,
                                                               float* __restrict__ ws) {
   __shared__ float sm[16];
   const long i0 = (long)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-  double acc = 0.0;
-  for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+  const float s = chunk_partial(i0, i1, sm, [&](long i) {
     const long r = i / C;
     const double v = (double)x[r * ldx + (i - r * C)];
-    acc += v * v;      // exact in f64: the sum is rounded to f32 once
-  }
-  float s = block_sum((float)acc, sm);
+    return v * v;      // exact in f64
+  });
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void sq_mean_reduce_kernel(const float* __restrict__ ws, int nblk, float count, float* __restrict__ out) {
   __shared__ float sm[16];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += ws[i];
-  s = block_sum(s, sm);
+  const float s = strided_sum(ws, nblk, sm);
   if (threadIdx.x == 0) out[0] = s / count;
 }
 __global__ __launch_bounds__(256) void sq_mean_bwd_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ gout,
@@ -123,7 +115,7 @@ static int sq_mean_check(const char* who, int B, int C) {
   return GSL_OK;
 }
 
-extern "C" long gsr_sq_mean_ws_elems(int B, int C) { return sq_mean_check(__func__, B, C) == GSL_OK ? rq_blocks((long)B * C) : -1; }
+extern "C" long gsr_sq_mean_ws_elems(int B, int C) { return sq_mean_check(__func__, B, C) == GSL_OK ? chunk_blocks((long)B * C) : -1; }
 
 extern "C" int gsr_sq_mean_fwd(const float* x, long ldx, int B, int C, float* out, float* ws, gsl_stream_t s) {
   GSL_TRY(sq_mean_check(__func__, B, C));
@@ -131,8 +123,8 @@ extern "C" int gsr_sq_mean_fwd(const float* x, long ldx, int B, int C, float* ou
   GSL_CHECK_ARG(ws, "null ws");
   GSL_CHECK_ARG(ldx >= C, "ldx >= C");
   const long n = (long)B * C;
-  const int nblk = rq_blocks(n);
-  const long chunk = (n + nblk - 1) / nblk;
+  const int nblk = chunk_blocks(n);
+  const long chunk = chunk_len(n, nblk);
   hipLaunchKernelGGL(sq_mean_partial_kernel, dim3(nblk), dim3(256), 0, as_stream(s), x, ldx, C, n, chunk, ws);
   GSL_TRY(check_launch("gsr_sq_mean_fwd(partial)"));
   hipLaunchKernelGGL(sq_mean_reduce_kernel, dim3(1), dim3(256), 0, as_stream(s), ws, nblk, (float)n, out);
@@ -170,8 +162,8 @@ extern "C" int gsr_reg_multi_layout(const void* const* p, const void* const* p0,
       o.p0 = static_cast<const float*>(p0[e]);
       o.omega = static_cast<const float*>(omega[e]);
       o.n = n[e];
-      o.nblk = rq_blocks(n[e]);
-      o.chunk = (n[e] + o.nblk - 1) / o.nblk;
+      o.nblk = chunk_blocks(n[e]);
+      o.chunk = chunk_len(n[e], o.nblk);
       o.blk0 = (int)blk;
       if (k == 0) {
         o.goff = goff;
@@ -189,31 +181,15 @@ extern "C" int gsr_reg_multi_layout(const void* const* p, const void* const* p0,
   return GSL_OK;
 }
 
-// the entry (of the first `count`) that owns workgroup b: the last one whose blk0 <= b
-__device__ __forceinline__ int rm_find(const gsr_reg_entry* __restrict__ tab, int count, int b) {
-  int lo = 0, hi = count - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void reg_multi_partial_kernel(const gsr_reg_entry* __restrict__ tab, int n_entries, float* __restrict__ ws) {
   __shared__ float sm[16];
-  const gsr_reg_entry e = tab[rm_find(tab, n_entries, blockIdx.x)];
+  const gsr_reg_entry e = tab[chunk_owner(tab, n_entries, blockIdx.x, &gsr_reg_entry::blk0)];
   const float* __restrict__ p = e.p;
   const float* __restrict__ p0 = e.p0;
   const float* __restrict__ omega = e.omega;
-  const long n = e.n, chunk = e.chunk;
-  const long i0 = (long)(blockIdx.x - e.blk0) * chunk, i1 = min(n, i0 + chunk);
-  // the loop of reg_quad_partial_kernel (csrc/train.hip), statement for statement: the same elements per thread in the same order
-  double acc = 0.0;
-  for (long i = i0 + threadIdx.x; i < i1; i += 256) {
-    const double d = (double)p[i] - (double)p0[i];
-    acc += omega ? (double)omega[i] * (d * d) : d * d;
-  }
-  float s = block_sum((float)acc, sm);
+  const long i0 = (long)(blockIdx.x - e.blk0) * e.chunk, i1 = min(e.n, i0 + e.chunk);
+  // reg_quad_partial_kernel's sum (csrc/train.hip): the same helper over the same term
+  const float s = chunk_partial(i0, i1, sm, [&](long i) { return quad_term(p, p0, omega, i); });
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 
@@ -222,11 +198,8 @@ __global__ __launch_bounds__(256) void reg_multi_reduce_kernel(const gsr_reg_ent
   __shared__ float sm[16];
   float total = 0.f;
   for (int e = 0; e < n_entries; ++e) {
-    const int blk0 = tab[e].blk0, nblk = tab[e].nblk;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) s += ws[blk0 + i];      // reg_quad_reduce_kernel's strided sum ...
-    s = block_sum(s, sm);                                                  // ... and its block_sum (every thread holds the result)
-    total = e ? total + s : s;                                             // accumulate = e > 0
+    const float s = strided_sum(ws + tab[e].blk0, tab[e].nblk, sm);      // reg_quad_reduce_kernel's sum (every thread holds the result)
+    total = e ? total + s : s;                                           // accumulate = e > 0
   }
   if (threadIdx.x == 0) out[0] = total;
 }
@@ -248,7 +221,7 @@ __device__ __forceinline__ float rm_elem(float g, float p, const gsr_reg_entry* 
 __global__ __launch_bounds__(256) void reg_multi_bwd_kernel(const gsr_reg_entry* __restrict__ tab, int n_terms, int n_tensors,
                                                             const float* __restrict__ coef, float* __restrict__ gbase) {
 #pragma clang fp contract(off)
-  const int t = rm_find(tab, n_tensors, blockIdx.x);
+  const int t = chunk_owner(tab, n_tensors, blockIdx.x, &gsr_reg_entry::blk0);
   const gsr_reg_entry e0 = tab[t];
   const float* __restrict__ p = e0.p;
   float* __restrict__ g = gbase + e0.goff;
@@ -259,13 +232,7 @@ __global__ __launch_bounds__(256) void reg_multi_bwd_kernel(const gsr_reg_entry*
     const gsr_reg_entry* e = tab + (long)k * n_tensors + t;
     bits |= reinterpret_cast<uintptr_t>(e->p0) | reinterpret_cast<uintptr_t>(e->omega);
   }
-  long v0 = i1, nvec = 0;      // the vector body [v0, v0 + 4 nvec) of this chunk: from the first multiple of 4 at or behind i0
-  if ((bits & 15) == 0) {
-    v0 = min(i1, (i0 + 3) & ~3L);
-    nvec = (i1 - v0) / 4;
-  }
-  for (long v = threadIdx.x; v < nvec; v += 256) {
-    const long i = v0 + 4 * v;
+  chunk_walk(i0, i1, (bits & 15) == 0, [&](long i) {
     float4 gg = *reinterpret_cast<const float4*>(g + i);
     const float4 pp = *reinterpret_cast<const float4*>(p + i);
     for (int k = 0; k < n_terms; ++k) {
@@ -281,12 +248,7 @@ __global__ __launch_bounds__(256) void reg_multi_bwd_kernel(const gsr_reg_entry*
       gg.x = gg.x + wx; gg.y = gg.y + wy; gg.z = gg.z + wz; gg.w = gg.w + ww;
     }
     *reinterpret_cast<float4*>(g + i) = gg;
-  }
-  const long body_end = v0 + 4 * nvec, head = v0 - i0, nscalar = (i1 - i0) - 4 * nvec;      // [i0, v0) and [body_end, i1)
-  for (long j = threadIdx.x; j < nscalar; j += 256) {
-    const long i = j < head ? i0 + j : body_end + (j - head);
-    g[i] = rm_elem(g[i], p[i], tab, t, n_terms, n_tensors, i, c2);
-  }
+  }, [&](long i) { g[i] = rm_elem(g[i], p[i], tab, t, n_terms, n_tensors, i, c2); });
 }
 
 extern "C" int gsr_reg_multi_fwd(const gsr_reg_entry* table_dev, int n_entries, long total_blocks, float* out, float* ws, gsl_stream_t s) {

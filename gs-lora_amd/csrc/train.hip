@@ -3,8 +3,9 @@
 //                   and output gradient Y are both wide (the FFN linears, reference vit_pytorch_face/vit_face.py:330-333, trained by
 //                   train/train_own_forget_cl.py:432-439 --only_ffn)
 //   gst_reg_quad_*  sum(importance * (p - task_param) ** 2) and its gradient (reference engine_cl.py:455-457, get_reg_loss)
-// A second product library: its own error string, nothing shared with libgslora_hip.so but the headers.
-#include "gsl_common.h"
+// A second product library: its own error string; nothing shared with libgslora_hip.so but the headers (gsl_common.h and the public ones),
+// and with the other side libraries gsl_chunks.h: the chunked sum gst_reg_quad_fwd is written over.
+#include "gsl_chunks.h"
 
 #include "../../include/gslora_train.h"
 
@@ -276,32 +277,19 @@ extern "C" int gst_wgrad(const void* Y, long ldy, const void* X, long ldx, float
 }
 
 // =====================================================================================
-// gst_reg_quad_*: sum_i omega_i (p_i - p0_i)^2 and its gradient. Forward: a fixed partition of the tensor into at most RQ_MAX_BLOCKS
-// chunks, one partial per chunk in ws, one reduce launch in ascending chunk order.
+// gst_reg_quad_*: sum_i omega_i (p_i - p0_i)^2 and its gradient. Forward: the fixed partition of gsl_chunks.h, one partial per chunk in
+// ws, one reduce launch in ascending chunk order.
 // =====================================================================================
-constexpr int RQ_MAX_BLOCKS = 1024;
-constexpr long RQ_MIN_CHUNK = 1024;
-static inline int rq_blocks(long n) { return (int)min((long)RQ_MAX_BLOCKS, (n + RQ_MIN_CHUNK - 1) / RQ_MIN_CHUNK); }
-
 __global__ __launch_bounds__(256) void reg_quad_partial_kernel(const float* __restrict__ p, const float* __restrict__ p0, const float* __restrict__ omega,
                                                                long n, long chunk, float* __restrict__ ws) {
   __shared__ float sm[16];
   const long i0 = (long)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-  // a thread's terms are formed and summed in f64 (the difference of two f32 values and its square are then exact) and rounded to f32 once:
-  // a tensor of one element comes out correctly rounded, and the f32 sums behind it add at most one rounding per level
-  double acc = 0.0;
-  for (long i = i0 + threadIdx.x; i < i1; i += 256) {
-    const double d = (double)p[i] - (double)p0[i];
-    acc += omega ? (double)omega[i] * (d * d) : d * d;
-  }
-  float s = block_sum((float)acc, sm);
+  const float s = chunk_partial(i0, i1, sm, [&](long i) { return quad_term(p, p0, omega, i); });
   if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void reg_quad_reduce_kernel(const float* __restrict__ ws, int nblk, float* out, int accumulate) {
   __shared__ float sm[16];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += ws[i];
-  s = block_sum(s, sm);
+  const float s = strided_sum(ws, nblk, sm);
   if (threadIdx.x == 0) out[0] = accumulate ? out[0] + s : s;
 }
 // g += ((coef * 2) * omega) * (p - p0), every operation rounded on its own
@@ -317,15 +305,15 @@ __global__ __launch_bounds__(256) void reg_quad_bwd_kernel(const float* __restri
   g[i] = g[i] + t;
 }
 
-extern "C" long gst_reg_quad_ws_elems(long n) { return n >= 1 ? rq_blocks(n) : -1; }
+extern "C" long gst_reg_quad_ws_elems(long n) { return n >= 1 ? chunk_blocks(n) : -1; }
 
 extern "C" int gst_reg_quad_fwd(const float* p, const float* p0, const float* omega, long n, float* out, int accumulate, float* ws,
                                 gsl_stream_t s) {
   GSL_CHECK_ARG(p && p0 && out, "null tensor");
   GSL_CHECK_ARG(ws, "null ws");
   GSL_CHECK_ARG(n >= 1, "n >= 1");
-  const int nblk = rq_blocks(n);
-  const long chunk = (n + nblk - 1) / nblk;
+  const int nblk = chunk_blocks(n);
+  const long chunk = chunk_len(n, nblk);
   hipLaunchKernelGGL(reg_quad_partial_kernel, dim3(nblk), dim3(256), 0, as_stream(s), p, p0, omega, n, chunk, ws);
   GSL_TRY(check_launch("gst_reg_quad_fwd(partial)"));
   hipLaunchKernelGGL(reg_quad_reduce_kernel, dim3(1), dim3(256), 0, as_stream(s), ws, nblk, out, accumulate);

@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from ._cdll import LazyLib, _ld, _ptr, _stream
+from ._cdll import LazyLib, _ld, _ptr, _stream, columns, table_to_device      # (table_to_device: tests reach it through this binding)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgslora_kd.so")
@@ -80,20 +80,11 @@ def param_dist_layout(entries):
     """entries: (p_ptr, q_ptr, n, trainable) per tensor, in parameter order. -> (table: a ctypes array of DistEntry, total_blocks, bwd_blocks,
     g_elems). A host function: nothing is launched."""
     ne = len(entries)
-    P = (_vp * ne)(*[e[0] for e in entries])
-    Q = (_vp * ne)(*[e[1] for e in entries])
-    N = (C.c_long * ne)(*[e[2] for e in entries])
-    TR = (C.c_int * ne)(*[1 if e[3] else 0 for e in entries])
+    P, Q, N, TR = columns(entries, _vp, _vp, _l, _i)      # (a bool is a ctypes int of 0 or 1)
     table = (DistEntry * max(ne, 1))()
     tot, bwd, ge = C.c_long(), C.c_long(), C.c_long()
     check(load().gsk_param_dist_layout(P, Q, N, TR, ne, table, C.byref(tot), C.byref(bwd), C.byref(ge)), "gsk_param_dist_layout")
     return table, tot.value, bwd.value, ge.value
-
-
-def table_to_device(table, device):
-    """The host table as a device byte tensor, as it is."""
-    host = torch.frombuffer(bytearray(C.string_at(C.addressof(table), C.sizeof(table))), dtype=torch.uint8)
-    return host.to(device)
 
 
 def param_dist_fwd(table_dev, n_entries, total_blocks, p, out, norms, ws):

@@ -8,7 +8,7 @@ import os
 
 import torch
 
-from ._cdll import LazyLib, _ptr, _stream
+from ._cdll import LazyLib, _ptr, _stream, columns
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgslora_reg.so")
@@ -86,10 +86,7 @@ def reg_multi_layout(entries, n_terms, n_tensors):
     ne = n_terms * n_tensors
     if len(entries) != ne:
         raise ValueError(f"reg_multi_layout: {len(entries)} entries for {n_terms} terms of {n_tensors} tensors")
-    P = (_vp * ne)(*[e[0] for e in entries])
-    P0 = (_vp * ne)(*[e[1] for e in entries])
-    OM = (_vp * ne)(*[e[2] for e in entries])
-    N = (C.c_long * ne)(*[e[3] for e in entries])
+    P, P0, OM, N = columns(entries, _vp, _vp, _vp, _l)
     table = (RegEntry * ne)()
     tot, bwd, ge = C.c_long(), C.c_long(), C.c_long()
     check(load().gsr_reg_multi_layout(P, P0, OM, N, n_terms, n_tensors, table, C.byref(tot), C.byref(bwd), C.byref(ge)), "gsr_reg_multi_layout")

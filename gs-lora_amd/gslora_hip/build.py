@@ -52,7 +52,7 @@ def needs_build_side(tag):
         return True
     t = os.path.getmtime(out)
     inc = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
-    deps = [os.path.join(CSRC, s) for s in SIDE_LIBS[tag] + ["gsl_common.h", f"exports_{tag}.map"]]
+    deps = [os.path.join(CSRC, s) for s in SIDE_LIBS[tag] + ["gsl_common.h", "gsl_chunks.h", f"exports_{tag}.map"]]
     deps += [os.path.join(inc, h) for h in ("gslora_hip.h", f"gslora_{tag}.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

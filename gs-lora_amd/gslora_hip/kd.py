@@ -8,6 +8,8 @@ import weakref
 import torch
 import torch.nn as nn
 
+from ._cdll import DeviceTable
+
 
 class _KdCe(torch.autograd.Function):
     """(kd, ce, c_kd * kd + c_ce * ce) of [B, C] f32 logits over gsk_kd_ce_fwd / gsk_kd_ce_bwd. Only the third output carries a gradient, and
@@ -93,11 +95,10 @@ class _ParamDist(torch.autograd.Function):
         pd = ctx.pd
         g = torch.zeros(pd.g_elems, device=pd.table_dev.device, dtype=torch.float32)
         LK.param_dist_bwd(pd.table_dev, pd.n_entries, pd.bwd_blocks, pd.p, gout.detach().float().reshape(1).contiguous(), ctx.norms, g)
-        return (None,) + tuple(g[off:off + t.numel()].view(t.shape) if need else None
-                               for off, t, need in zip(pd.goffs, pd.trainable, ctx.needs_input_grad[1:]))
+        return (None,) + pd.grad_views(g, pd.trainable, ctx.needs_input_grad[1:])
 
 
-class ParamDist:
+class ParamDist(DeviceTable):
     """param_dist(model, swa_model, p) of the reference (util/sgda_utils.py) prepared once for the batched kernels: `.loss()` is
     p * sum over ALL of zip(model.parameters(), swa_model.parameters()) — the frozen ones included, as in the reference — of the Frobenius
     norm of the difference, in two launches forward and one backward whatever the number of tensors. The entry table
@@ -112,7 +113,6 @@ class ParamDist:
     def __init__(self, model, swa_model, p):
         self._model, self._swa_model, self.p = weakref.ref(model), weakref.ref(swa_model), float(p)      # (a cache may key on the model)
         self.rebuilds = 0
-        self.table_dev = None
         if self.p != 0.0:
             self._build()
 
@@ -142,20 +142,15 @@ class ParamDist:
         self.n_entries = len(entries)
         self.trainable = [a for a in ps if a.requires_grad]
         self.goffs = [table[k].goff for k, a in enumerate(ps) if a.requires_grad]
-        self._ptrs = [t.data_ptr() for t in ps + qs]
         self._req = [a.requires_grad for a in ps]
-        dev = ps[0].device
-        self.table_dev = LK.table_to_device(table, dev)
-        self.ws = torch.empty(self.total_blocks, device=dev, dtype=torch.float32)
+        self._upload(table, self.total_blocks, ps + qs, ps[0].device)
 
     def loss(self):
         if self.p == 0.0:
             dev = next(self._model().parameters()).device
             return torch.zeros((), device=dev, dtype=torch.float32)
         ps, qs = self._pairs()
-        now = ps + qs
-        if (self.table_dev is None or len(now) != len(self._ptrs) or any(t.data_ptr() != q for t, q in zip(now, self._ptrs))
-                or [a.requires_grad for a in ps] != self._req):
+        if self.table_dev is None or self._moved(ps + qs) or [a.requires_grad for a in ps] != self._req:
             self.rebuilds += self.table_dev is not None
             self._build()
         if not self.trainable:      # nothing trains: the value alone

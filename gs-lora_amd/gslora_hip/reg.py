@@ -4,13 +4,10 @@ regulariser of engine_cl.get_reg_loss over every term and tensor in two launches
 first use through gslora_hip._lib_reg). Scope is that of gslora_hip.step.ffn_reg_step: a ViT_face / ViTs_face built with lora_rank = 0 whose
 FFN linears (and, optionally, the `loss` head) require a gradient; one process, eager.
 """
-import ctypes as C
-
 import torch
-import torch.nn as nn
 
-from . import losses
-from .step import _model_input, _plain_ce
+from ._cdll import DeviceTable
+from .step import _ce_mean_and_hits, _model_input, _overflow_guard_of, _unwrap
 
 KINDS = ("l2", "ewc", "mas")
 
@@ -66,7 +63,7 @@ def calculate_importance(model, dataloader, kind, criterion=None, prior=None, de
     different loader over the same arithmetic."""
     if kind not in KINDS:
         raise ValueError(f"calculate_importance: kind {kind!r}; use one of {KINDS}")
-    net = model.module if isinstance(model, nn.DataParallel) else model
+    net = _unwrap(model)
     named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
     if kind == "l2":
         return Importance((n, p.clone().detach().fill_(1)) for n, p in named)
@@ -93,16 +90,10 @@ def calculate_importance(model, dataloader, kind, criterion=None, prior=None, de
         for samples, targets in dataloader:
             samples, targets = samples.to(device), targets.to(device)
             logits, _ = model(_model_input(net, samples), targets)
-            if kind == "mas":
-                loss = sq_mean(logits)
-            elif _plain_ce(criterion):
-                loss = losses.ce_sum_top1(logits, targets)[0] / float(samples.size(0))
-            else:
-                loss = criterion(logits, targets)
+            loss = sq_mean(logits) if kind == "mas" else _ce_mean_and_hits(criterion, logits, targets, samples.size(0), hits=False)[0]
             model.zero_grad()
             loss.backward()
-            runner = getattr(net, "_runner", None)
-            guard = runner.overflow_guard() if runner is not None and hasattr(runner, "overflow_guard") else None
+            guard = _overflow_guard_of(net)
             count = skipped      # a skipped batch counts once: the first launch of the batch carries the counter
             for (n, p), om in zip(named, importance.values()):
                 if p.grad is not None:      # (some parameters may not have a gradient, :1502-1504: their importance stays as it is)
@@ -114,9 +105,66 @@ def calculate_importance(model, dataloader, kind, criterion=None, prior=None, de
     return importance
 
 
+def _term_entries(model, regularization_terms):
+    """The walk of get_reg_loss (reference engine_cl.py:449-459), term-major: (p, task_param, importance or None) per term and trainable
+    tensor, the terms' tensors as contiguous f32 on the parameter's device. Raises what get_reg_loss on the HIP path refuses."""
+    named = [(n, p) for n, p in _unwrap(model).named_parameters() if p.requires_grad]
+    for term in regularization_terms.values():
+        imp, ref = term["importance"], term["task_param"]
+        for n, p in named:
+            om, p0 = imp[n], ref[n]
+            if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
+                raise RuntimeError(f"gs-lora_amd get_reg_loss: parameter {n!r} must be a contiguous f32 tensor on the GPU (no CPU fallback)")
+            if p0.shape != p.shape or (om is not None and om.shape != p.shape):
+                raise ValueError(f"get_reg_loss: importance / task_param of {n!r} do not have the parameter's shape")
+            yield (p, p0.detach().to(device=p.device, dtype=torch.float32).contiguous(),
+                   None if om is None else om.detach().to(device=p.device, dtype=torch.float32).contiguous())
+
+
+class _RegQuad(torch.autograd.Function):
+    """reg_lambda * sum over terms and tensors of sum(importance * (p - task_param) ** 2) (reference engine_cl.py:449-459) as ONE autograd
+    node over gst_reg_quad_fwd / gst_reg_quad_bwd. entries: what _term_entries yields."""
+
+    @staticmethod
+    def forward(ctx, entries, reg_lambda, *params):
+        from . import _lib_train as LT
+        dev = params[0].device
+        out = torch.zeros((), device=dev, dtype=torch.float32)
+        ws = torch.empty(max(LT.load().gst_reg_quad_ws_elems(p.numel()) for p in params), device=dev, dtype=torch.float32)
+        for k, (p, p0, om) in enumerate(entries):
+            LT.reg_quad_fwd(p.detach(), p0, om, out, accumulate=k > 0, ws=ws)
+        ctx.entries, ctx.reg_lambda, ctx.ids = entries, float(reg_lambda), [id(p) for p in params]
+        return out * float(reg_lambda)
+
+    @staticmethod
+    def backward(ctx, gout):
+        from . import _lib_train as LT
+        coef = (gout.detach().float() * ctx.reg_lambda).reshape(1).contiguous()      # a device float: upstream gradient times lambda
+        grads = {}
+        for p, p0, om in ctx.entries:
+            g = grads.get(id(p))
+            if g is None:
+                g = grads[id(p)] = torch.zeros(p.shape, device=p.device, dtype=torch.float32)
+            LT.reg_quad_bwd(p.detach(), p0, om, coef, g)
+        return (None, None) + tuple(grads.get(i) if need else None for i, need in zip(ctx.ids, ctx.needs_input_grad[2:]))
+
+
+def reg_loss(model, regularization_terms, reg_lambda, device):
+    """engine_cl.get_reg_loss (reference engine_cl.py:435-460): reg_lambda * sum_terms sum_{trainable p} sum(importance[n] * (p -
+    task_param[n]) ** 2), a 0-dim f32 tensor; a 0-dim zero when the terms are None. importance[n] may be None for the identity (L2).
+    Two launches forward and one backward per term and tensor (libgslora_train.so); RegTerms is the batched form."""
+    zero = torch.tensor(0.0, device=device)
+    if regularization_terms is None:
+        return zero
+    entries = list(_term_entries(model, regularization_terms))
+    if not entries:
+        return zero
+    return _RegQuad.apply(entries, reg_lambda, *[p for p in _unwrap(model).parameters() if p.requires_grad])
+
+
 class _RegMulti(torch.autograd.Function):
     """reg_lambda * sum over terms and tensors of sum(importance * (p - task_param) ** 2) as ONE autograd node over gsr_reg_multi_fwd /
-    gsr_reg_multi_bwd: the value and the gradients of step._RegQuad, bit for bit."""
+    gsr_reg_multi_bwd: the value and the gradients of _RegQuad, bit for bit."""
 
     @staticmethod
     def forward(ctx, rt, *params):
@@ -133,17 +181,16 @@ class _RegMulti(torch.autograd.Function):
         coef = (gout.detach().float() * rt.reg_lambda).reshape(1).contiguous()      # a device float: upstream gradient times lambda
         g = torch.zeros(rt.g_elems, device=rt.table_dev.device, dtype=torch.float32)
         LR.reg_multi_bwd(rt.table_dev, rt.n_terms, rt.n_tensors, rt.bwd_blocks, coef, g)
-        return (None,) + tuple(g[off:off + p.numel()].view(p.shape) if need else None
-                               for off, p, need in zip(rt.goffs, rt.params, ctx.needs_input_grad[1:]))
+        return (None,) + rt.grad_views(g, rt.params, ctx.needs_input_grad[1:])
 
 
-class RegTerms:
+class RegTerms(DeviceTable):
     """The regularisation terms of a run, prepared once for the batched kernels: `.loss()` has the meaning of
     engine_cl.get_reg_loss(model, regularization_terms, reg_lambda, device) and its bits, in two launches forward and one backward whatever
     the number of terms and tensors. The entry table (gsr_reg_multi_layout) is built and uploaded at construction: the parameters' device
     addresses are stable, FusedAdamW writes through raw pointers. Every `.loss()` compares the parameters' data_ptr() with the table's and
     rebuilds it when one moved. The terms' own tensors (task_param, importance) are converted once and held here: terms added or changed
-    afterwards need a new RegTerms. Validation and its messages are those of step.reg_loss."""
+    afterwards need a new RegTerms. The walk over the terms and its refusals are reg_loss's own (_term_entries)."""
 
     def __init__(self, model, regularization_terms, reg_lambda):
         self.model, self.terms, self.reg_lambda = model, regularization_terms, float(reg_lambda)
@@ -152,41 +199,24 @@ class RegTerms:
 
     def _build(self):
         from . import _lib_reg as LR
-        net = self.model.module if isinstance(self.model, nn.DataParallel) else self.model
-        named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
-        self.params = [p for _, p in named]
+        self.params = [p for p in _unwrap(self.model).parameters() if p.requires_grad]
         self.n_terms = 0 if self.terms is None else len(self.terms)
-        self.n_tensors = len(named)
+        self.n_tensors = len(self.params)
         self.table_dev = None
         if not self.n_terms or not self.n_tensors:
             return
-        entries, keep = [], []
-        for term in self.terms.values():
-            imp, ref = term["importance"], term["task_param"]
-            for n, p in named:
-                om, p0 = imp[n], ref[n]
-                if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
-                    raise RuntimeError(f"gs-lora_amd get_reg_loss: parameter {n!r} must be a contiguous f32 tensor on the GPU (no CPU fallback)")
-                if p0.shape != p.shape or (om is not None and om.shape != p.shape):
-                    raise ValueError(f"get_reg_loss: importance / task_param of {n!r} do not have the parameter's shape")
-                p0 = p0.detach().to(device=p.device, dtype=torch.float32).contiguous()
-                om = None if om is None else om.detach().to(device=p.device, dtype=torch.float32).contiguous()
-                keep.append((p0, om))
-                entries.append((p.data_ptr(), p0.data_ptr(), None if om is None else om.data_ptr(), p.numel()))
+        self._keep = list(_term_entries(self.model, self.terms))      # (holds the converted tensors the table points at)
+        entries = [(p.data_ptr(), p0.data_ptr(), None if om is None else om.data_ptr(), p.numel()) for p, p0, om in self._keep]
         table, self.total_blocks, self.bwd_blocks, self.g_elems = LR.reg_multi_layout(entries, self.n_terms, self.n_tensors)
         self.goffs = [table[t].goff for t in range(self.n_tensors)]
-        self._keep, self._ptrs = keep, [p.data_ptr() for p in self.params]
-        dev = self.params[0].device
-        host = torch.frombuffer(bytearray(C.string_at(C.addressof(table), C.sizeof(table))), dtype=torch.uint8)
-        self.table_dev = host.to(dev)
-        self.ws = torch.empty(self.total_blocks, device=dev, dtype=torch.float32)
+        self._upload(table, self.total_blocks, self.params, self.params[0].device)
 
     def loss(self, device=None):
         """reg_lambda * sum_terms sum_{trainable p} sum(importance[n] * (p - task_param[n]) ** 2): a 0-dim f32 tensor with a gradient; a 0-dim
         zero when there are no terms or no trainable parameters."""
         if self.table_dev is None:
             return torch.tensor(0.0, device=device if device is not None else (self.params[0].device if self.params else "cuda"))
-        if any(p.data_ptr() != q for p, q in zip(self.params, self._ptrs)):
+        if self._moved(self.params):
             self.rebuilds += 1
             self._build()
         return _RegMulti.apply(self, *self.params)

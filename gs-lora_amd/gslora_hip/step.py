@@ -46,9 +46,23 @@ def _cat_labels(y_r, y_f):
     return torch.cat((y_r, y_f), 0)
 
 
+def _unwrap(model):
+    """The module behind nn.DataParallel (over one device: _check_not_replicated), or the model itself."""
+    return model.module if isinstance(model, nn.DataParallel) else model
+
+
 def _plain_ce(criterion):
     return (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.reduction == "mean"
             and getattr(criterion, "label_smoothing", 0.0) == 0.0 and criterion.ignore_index == -100)
+
+
+def _ce_mean_and_hits(criterion, logits, y, n, hits=True):
+    """-> (mean cross-entropy, top-1 hit count) of one batch of n images: both from losses.ce_sum_top1 under plain nn.CrossEntropyLoss; any
+    other criterion keeps its semantics, with top-1 from the HIP kernel (hits=False: not launched, None)."""
+    if _plain_ce(criterion):
+        ce_sum, h = losses.ce_sum_top1(logits, y)
+        return ce_sum / float(n), h
+    return criterion(logits, y), (losses.ce_sum_top1(logits.detach(), y)[1] if hits else None)
 
 
 def _globalize(local_sum, global_sum_detached):
@@ -101,14 +115,21 @@ def _bucket_messages(net, backend):
     return [flat[split:], flat[:split]]      # blocks 1 .. L-1 (final once the backward reaches block 0), then block 0
 
 
+def _overflow_guard_of(net, runner=None):
+    """The overflow guard of the backward that just ran on the net's runner (or on `runner`): ViTRunner.overflow_guard(), one device float,
+    None when that backward did not run on loss-scaled gradients — or None without a runner."""
+    if runner is None:
+        runner = getattr(net, "_runner", None)
+    return runner.overflow_guard() if runner is not None and hasattr(runner, "overflow_guard") else None
+
+
 def _guard_message(net):
     """fp16 operands under data parallelism: the overflow guard of the backward that just ran (ViTRunner.overflow_guard(), one device float)
     as the int32 word every rank MAX-reduces after its gradient messages — non-negative floats, +inf and NaN order as their bit patterns, so
     an integer MAX agrees on "some rank saturated" whatever the backend does with a floating NaN. All ranks then skip (or take) the update
     together and settle the same next loss-scale exponent from the same value. None when the backward did not run on loss-scaled gradients
     (every rank of a job computes in the same format, so either all ranks post this message or none does)."""
-    runner = getattr(net, "_runner", None)
-    g = runner.overflow_guard() if runner is not None and hasattr(runner, "overflow_guard") else None
+    g = _overflow_guard_of(net)
     return None if g is None else g[:1].view(torch.int32)
 
 
@@ -201,24 +222,24 @@ class _EagerComm:
         return _OverlappedBucketReduce(net, backend, overlap)
 
 
-def _arm_overflow_guard(net, optimizer):
+def _arm_overflow_guard(net, optimizer, runner=None, guarded=True):
     """fp16 operands: hand the optimizer the overflow guard of the backward that just ran (ViTRunner.overflow_guard(): the device float the
     LayerNorm backwards raised to the largest scaled gradient they saw) — FusedAdamW then skips the update of a step in which a 16-bit gradient
     store saturated (torch.cuda.amp.GradScaler.step semantics, no host sync); the next backward lowers its loss scale on the device. Under
     data parallelism the ranks have agreed on the guard by then (one 4-byte MAX all-reduce behind the gradient messages, _guard_message):
-    they skip together, and they lower their scales together."""
-    if not hasattr(optimizer, "overflow_guard"):
-        return
-    runner = getattr(net, "_runner", None)
-    g = runner.overflow_guard() if runner is not None and hasattr(runner, "overflow_guard") else None
-    optimizer.overflow_guard = g
+    they skip together, and they lower their scales together.
+    runner: the runner whose backward it was, where that is not the net's own (lirf_step: the pair's). guarded=False: nothing that trains
+    went through a loss-scaled backward (head_probe_step with the head alone: f32 arithmetic) — the optimizer's guard is cleared."""
+    if hasattr(optimizer, "overflow_guard"):
+        optimizer.overflow_guard = _overflow_guard_of(net, runner) if guarded else None
 
 
-def _backward_and_update(net, optimizer, roots, grads=None):
-    """The end of a single-process step: gradients from the loss (or from several roots with their upstream gradients), then the update."""
+def _backward_and_update(net, optimizer, roots, grads=None, **guard):
+    """The end of a single-process step: gradients from the loss (or from several roots with their upstream gradients), then the update.
+    One backward per optimizer step: the overflow guard the optimizer reads is this backward's (guard: _arm_overflow_guard's keywords)."""
     optimizer.zero_grad()
     torch.autograd.backward(roots, grads)
-    _arm_overflow_guard(net, optimizer)
+    _arm_overflow_guard(net, optimizer, **guard)
     optimizer.step()
 
 
@@ -226,6 +247,15 @@ def _model_input(net, x):
     """The reference's inputs.float() — except for a uint8 batch of a model that normalises bytes itself (set_input_norm): that one
     stays uint8 up to the patch gather (a cast here would change its values and put four bytes per sub-pixel back on the bus)."""
     return x if (x.dtype == torch.uint8 and getattr(net, "input_norm", None) is not None) else x.float()
+
+
+def _fused_input(net, xs, ask=True):
+    """Several image batches (each through _model_input) as the argument of ONE forward: the tuple itself when the batches agree in shape
+    and dtype — and, with ask, the model says it takes one (accepts_batch_tuple) — else their float concatenation. lirf_step does not ask:
+    its student is a ViT_face_low by then, and low_up_forward takes the tuple."""
+    if (not ask or getattr(net, "accepts_batch_tuple", False)) and all(x.shape[1:] == xs[0].shape[1:] and x.dtype == xs[0].dtype for x in xs):
+        return xs
+    return torch.cat([x.float() for x in xs], 0)
 
 
 def _head_trains(net):
@@ -246,56 +276,11 @@ _FFN_ONE_PROCESS = ("trainable FFN weights (fn.fn.net, the --only_ffn baselines)
                     "gradients are not reduced across ranks and their step is not captured")
 
 
-class _RegQuad(torch.autograd.Function):
-    """reg_lambda * sum over terms and tensors of sum(importance * (p - task_param) ** 2) (reference engine_cl.py:449-459) as ONE autograd
-    node over gst_reg_quad_fwd / gst_reg_quad_bwd. entries: (p, task_param, importance or None) per term and trainable tensor."""
-
-    @staticmethod
-    def forward(ctx, entries, reg_lambda, *params):
-        from . import _lib_train as LT
-        dev = params[0].device
-        out = torch.zeros((), device=dev, dtype=torch.float32)
-        ws = torch.empty(max(LT.load().gst_reg_quad_ws_elems(p.numel()) for p in params), device=dev, dtype=torch.float32)
-        for k, (p, p0, om) in enumerate(entries):
-            LT.reg_quad_fwd(p.detach(), p0, om, out, accumulate=k > 0, ws=ws)
-        ctx.entries, ctx.reg_lambda, ctx.ids = entries, float(reg_lambda), [id(p) for p in params]
-        return out * float(reg_lambda)
-
-    @staticmethod
-    def backward(ctx, gout):
-        from . import _lib_train as LT
-        coef = (gout.detach().float() * ctx.reg_lambda).reshape(1).contiguous()      # a device float: upstream gradient times lambda
-        grads = {}
-        for p, p0, om in ctx.entries:
-            g = grads.get(id(p))
-            if g is None:
-                g = grads[id(p)] = torch.zeros(p.shape, device=p.device, dtype=torch.float32)
-            LT.reg_quad_bwd(p.detach(), p0, om, coef, g)
-        return (None, None) + tuple(grads.get(i) if need else None for i, need in zip(ctx.ids, ctx.needs_input_grad[2:]))
-
-
 def reg_loss(model, regularization_terms, reg_lambda, device):
-    """engine_cl.get_reg_loss (reference engine_cl.py:435-460): reg_lambda * sum_terms sum_{trainable p} sum(importance[n] * (p -
-    task_param[n]) ** 2), a 0-dim f32 tensor; a 0-dim zero when the terms are None. importance[n] may be None for the identity (L2)."""
-    zero = torch.tensor(0.0, device=device)
-    if regularization_terms is None:
-        return zero
-    net = model.module if isinstance(model, nn.DataParallel) else model
-    named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
-    entries = []
-    for term in regularization_terms.values():
-        imp, ref = term["importance"], term["task_param"]
-        for n, p in named:
-            om, p0 = imp[n], ref[n]
-            if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
-                raise RuntimeError(f"gs-lora_amd get_reg_loss: parameter {n!r} must be a contiguous f32 tensor on the GPU (no CPU fallback)")
-            if p0.shape != p.shape or (om is not None and om.shape != p.shape):
-                raise ValueError(f"get_reg_loss: importance / task_param of {n!r} do not have the parameter's shape")
-            entries.append((p, p0.detach().to(device=p.device, dtype=torch.float32).contiguous(),
-                            None if om is None else om.detach().to(device=p.device, dtype=torch.float32).contiguous()))
-    if not entries:
-        return zero
-    return _RegQuad.apply(entries, reg_lambda, *[p for _, p in named])
+    """engine_cl.get_reg_loss on the HIP path: gslora_hip.reg.reg_loss under the name engine_cl and the tests import (reg.py imports this
+    module, so the name is bound at call time)."""
+    from .reg import reg_loss as impl
+    return impl(model, regularization_terms, reg_lambda, device)
 
 
 def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, reg_lambda=0.0):
@@ -305,35 +290,30 @@ def ffn_reg_step(model, optimizer, criterion, x, y, regularization_terms=None, r
     regularization_terms: the reference's dict (get_reg_loss: two launches forward and one backward per term and tensor), None, or a
     gslora_hip.reg.RegTerms prepared from such a dict (two launches forward and one backward in all, the same bits).
     Returns a DEVICE tensor [loss_ce, loss_reg, loss_total, prec1 %] (no host sync). Single process, eager."""
-    if _world() > 1:
-        raise RuntimeError(f"gs-lora_amd: ffn_reg_step runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    _refuse_group("ffn_reg_step")
     _check_not_replicated(model)
-    net = model.module if isinstance(model, nn.DataParallel) else model
+    net = _unwrap(model)
     logits, _ = model(_model_input(net, x), y)
     n = float(x.size(0))
-    if _plain_ce(criterion):
-        ce_sum, hits = losses.ce_sum_top1(logits, y)
-        loss_ce = ce_sum / n
-    else:
-        loss_ce = criterion(logits, y)
-        hits = losses.ce_sum_top1(logits.detach(), y)[1]
+    loss_ce, hits = _ce_mean_and_hits(criterion, logits, y, n)
     if hasattr(regularization_terms, "loss") and not isinstance(regularization_terms, dict):
         # a gslora_hip.reg.RegTerms: the same value and gradients from the batched kernels (its own reg_lambda; the argument is not read)
         loss_reg = regularization_terms.loss(logits.device)
     else:
         loss_reg = reg_loss(model, regularization_terms, reg_lambda, logits.device)
     total = loss_reg + loss_ce
-    optimizer.zero_grad()
-    total.backward()
-    _arm_overflow_guard(net, optimizer)      # fp16: the FFN gradients came out of a loss-scaled backward
-    optimizer.step()
+    _backward_and_update(net, optimizer, total)      # (fp16: the FFN gradients came out of a loss-scaled backward)
     return torch.stack((loss_ce.detach(), loss_reg.detach(), total.detach(), hits * (100.0 / n)))
+
+
+def _refuse_group(name):
+    if _world() > 1:
+        raise RuntimeError(f"gs-lora_amd: {name} runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
 
 
 def _refuse_group_and_graph(name, model, optimizer):
     """The baseline steps run in one process, eager."""
-    if _world() > 1:
-        raise RuntimeError(f"gs-lora_amd: {name} runs in one process; {_FFN_ONE_PROCESS} (a process group of {_world()} ranks is active)")
+    _refuse_group(name)
     if isinstance(model, GraphedStep) or isinstance(optimizer, GraphedStep):
         raise RuntimeError(f"gs-lora_amd: {name} is eager; GraphedStep captures the LoRA-only step, and {_FFN_ONE_PROCESS}")
 
@@ -362,8 +342,7 @@ def scrub_step(student, teacher, optimizer, criterion, x, y, *, maximize, kd_T, 
     Single process, eager: a process group and GraphedStep are refused, as ffn_reg_step refuses them."""
     _refuse_group_and_graph("scrub_step", student, optimizer)
     _check_not_replicated(student)
-    net = student.module if isinstance(student, nn.DataParallel) else student
-    tnet = teacher.module if isinstance(teacher, nn.DataParallel) else teacher
+    net, tnet = _unwrap(student), _unwrap(teacher)
     _refuse_unless_ffn_trains_without_lora("scrub_step", net)
     from . import kd as kdm
     xin = _model_input(net, x)
@@ -380,10 +359,7 @@ def scrub_step(student, teacher, optimizer, criterion, x, y, *, maximize, kd_T, 
         total = sgda_gamma * ce + part
     if dist is not None and dist.p != 0.0:      # (smoothing 0, the reference's default: the term and its gradient are 0 — not one launch)
         total = total + dist.loss()
-    optimizer.zero_grad()
-    total.backward()
-    _arm_overflow_guard(net, optimizer)      # fp16: the FFN gradients came out of a loss-scaled backward
-    optimizer.step()
+    _backward_and_update(net, optimizer, total)      # (fp16: the FFN gradients came out of a loss-scaled backward)
     return torch.stack((kd.detach(), ce.detach(), total.detach()))
 
 
@@ -416,15 +392,12 @@ def distill_step(student, teacher, optimizer, criterion, x_f, y_f, x_r, y_r, *, 
     if (x_n is None) != (y_n is None) or (x_n is not None and method != "der"):
         raise ValueError("distill_step: x_n and y_n (the second remain batch of DER++) are given together, and only with method 'der'")
     _check_not_replicated(student)
-    net = student.module if isinstance(student, nn.DataParallel) else student
-    tnet = teacher.module if isinstance(teacher, nn.DataParallel) else teacher
+    net, tnet = _unwrap(student), _unwrap(teacher)
     _refuse_unless_ffn_trains_without_lora("distill_step", net)
     parts = [(x_f, y_f), (x_r, y_r)] + ([(x_n, y_n)] if x_n is not None else [])
     sizes = [x.size(0) for x, _ in parts]
     nf, nr = sizes[0], sizes[1]
-    xs = tuple(_model_input(net, x) for x, _ in parts)
-    if not (getattr(net, "accepts_batch_tuple", False) and all(x.shape[1:] == xs[0].shape[1:] and x.dtype == xs[0].dtype for x in xs)):
-        xs = torch.cat([x.float() for x in xs], 0)
+    xs = _fused_input(net, tuple(_model_input(net, x) for x, _ in parts))
     y_all = torch.cat([y for _, y in parts], 0)
     logits, emb = student(xs, y_all)
     if method == "lwf" and logits.shape[1] < 2:
@@ -463,10 +436,7 @@ def distill_step(student, teacher, optimizer, criterion, x_f, y_f, x_r, y_r, *, 
         if ce_n is not None:
             ce_aux = ce_n
             total = total + lam_aux * ce_n
-    optimizer.zero_grad()
-    total.backward()
-    _arm_overflow_guard(net, optimizer)      # fp16: the FFN gradients came out of a loss-scaled backward
-    optimizer.step()
+    _backward_and_update(net, optimizer, total)      # (fp16: the FFN gradients came out of a loss-scaled backward)
     return torch.stack((ce_f.detach(), reg.detach(), ce_aux.detach(), total.detach()))
 
 
@@ -504,7 +474,7 @@ def lirf_step(student_low, deposit_low, teacher_low, teacher_up, optimizer, crit
     nets = []
     for m in (student_low, deposit_low, teacher_low, teacher_up):
         _check_not_replicated(m)
-        nets.append(m.module if isinstance(m, nn.DataParallel) else m)
+        nets.append(_unwrap(m))
     s, d, t, U = nets
     from vit_pytorch_face.vit_face import ViT_face_low, ViT_face_up, low_up_forward, low_up_pair
     for m, cls, what in ((s, ViT_face_low, "student_low"), (d, ViT_face_low, "deposit_low"), (t, ViT_face_low, "teacher_low"),
@@ -529,9 +499,7 @@ def lirf_step(student_low, deposit_low, teacher_low, teacher_up, optimizer, crit
         Tt, Dp = Tt.float(), Dp.float()
         kd_d = kdm.kd_ce(Dp[:, :split], Tt[:, :split], None, T, 1.0, 0.0)[0]
         pt_re = alpha * kd_d + (1.0 - alpha) * (losses.ce_sum_top1(Dp, y_f)[0] / float(nf))
-    xs = (xf_in, _model_input(s, x_r))
-    if not all(x.shape[1:] == xs[0].shape[1:] and x.dtype == xs[0].dtype for x in xs):
-        xs = torch.cat([x.float() for x in xs], 0)
+    xs = _fused_input(s, (xf_in, _model_input(s, x_r)), ask=False)
     y_all = torch.cat((y_f, y_r), 0)
     logits, _, at_value = low_up_forward(s, U, xs, y_all, at_images=nf, at_teacher=mid_t)
     if _plain_ce(criterion):
@@ -543,11 +511,7 @@ def lirf_step(student_low, deposit_low, teacher_low, teacher_up, optimizer, crit
     # kd_ce's kd is KL * T^2 / B: KP = alpha * kd, and its part of the total, 10 * KP, is formed on the device with the gradient
     kd_s, _, kp_part = kdm.kd_ce(logits[:nf, split:], Tt[:, split:], None, T, LIRF_KP_WEIGHT * alpha, 0.0)
     total = ce + float(_at_weight) * at_value + kp_part + LIRF_PT_RE_WEIGHT * pt_re + LIRF_REPLAY_WEIGHT * replay
-    optimizer.zero_grad()
-    total.backward()
-    if hasattr(optimizer, "overflow_guard"):      # fp16: the FFN gradients came out of the pair's loss-scaled backward
-        optimizer.overflow_guard = low_up_pair(s, U).runner().overflow_guard()
-    optimizer.step()
+    _backward_and_update(s, optimizer, total, runner=low_up_pair(s, U).runner())      # (fp16: the pair's loss-scaled backward)
     return torch.stack((ce.detach(), at_value.detach(), alpha * kd_s.detach(), pt_re, total.detach(), replay.detach()))
 
 
@@ -562,23 +526,15 @@ def head_probe_step(model, optimizer, criterion, x, y):
         raise RuntimeError("gs-lora_amd: head_probe_step runs in one process (the head gradient is not reduced across ranks); "
                            f"a process group of {_world()} ranks is active")
     _check_not_replicated(model)
-    net = model.module if isinstance(model, nn.DataParallel) else model
+    net = _unwrap(model)
     logits, _ = model(_model_input(net, x), y)
     n = float(x.size(0))
-    if _plain_ce(criterion):
-        ce_sum, hits = losses.ce_sum_top1(logits, y)
-        loss = ce_sum / n
-    else:      # exotic criterion: keep its semantics, top-1 from the HIP kernel
-        loss = criterion(logits, y)
-        hits = losses.ce_sum_top1(logits.detach(), y)[1]
-    optimizer.zero_grad()
-    loss.backward()
-    bucket = net.runner().bucket if hasattr(net, "runner") else None
-    if (bucket is not None and any(p.requires_grad for p in bucket.params)) or _ffn_trains(net):
-        _arm_overflow_guard(net, optimizer)      # LoRA (or the FFN weights) train too: their fp16 backward ran on loss-scaled gradients
-    elif hasattr(optimizer, "overflow_guard"):
-        optimizer.overflow_guard = None          # head alone: f32 arithmetic, no loss scale, nothing to guard
-    optimizer.step()
+    loss, hits = _ce_mean_and_hits(criterion, logits, y, n)
+    # LoRA (or the FFN weights) train too: their fp16 backward runs on loss-scaled gradients and the optimizer reads its guard; the head
+    # alone: f32 arithmetic, no loss scale, nothing to guard — the optimizer's guard is cleared
+    bucket = net.runner().bucket if hasattr(net, "runner") else None      # (the forward made it)
+    guarded = (bucket is not None and any(p.requires_grad for p in bucket.params)) or _ffn_trains(net)
+    _backward_and_update(net, optimizer, loss, guarded=guarded)
     return torch.stack((loss.detach(), hits * (100.0 / n)))
 
 
@@ -595,7 +551,7 @@ def gs_lora_step(model, optimizer, criterion, x_r, y_r, x_f, y_f, *, beta, alpha
     if l2 and not hasattr(backend, "proto_l2_sum"):
         raise RuntimeError("gs_lora_step: this backend has no l2 prototype distance")
     _check_not_replicated(model)
-    net = model.module if isinstance(model, nn.DataParallel) else model
+    net = _unwrap(model)
     world = _world()
     if _dp_active() and _ffn_trains(net):      # (before any launch)
         raise RuntimeError(f"gs-lora_amd: the data-parallel gs_lora_step all-reduces the flat LoRA gradient bucket only; {_FFN_ONE_PROCESS}")
@@ -764,7 +720,7 @@ class GraphedStep:
 
     def __init__(self, model, optimizer, criterion):
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
-        self.net = model.module if isinstance(model, nn.DataParallel) else model
+        self.net = _unwrap(model)
         self._frozen = [p for n, p in self.net.named_parameters() if "lora_" not in n]
         self.graphs = {}            # key -> dict(graph, static, nfwd), insertion-ordered (oldest evicted)
         self.pending = None         # key seen once (ran eagerly); captured at its second sighting

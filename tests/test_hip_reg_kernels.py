@@ -156,27 +156,50 @@ def test_sq_mean_autograd_node_matches_torch():
 
 
 # ---------------------------------------------------------------------------------------------------------------- batched regulariser
+def on_gpu(values, off=None):
+    """values on the GPU: its own allocation, or (off given) a view `off` floats behind a 16-byte boundary of a larger one."""
+    if off is None:
+        return values.cuda()
+    buf = torch.zeros(values.numel() + 8, device="cuda")
+    view = buf[4 + off:4 + off + values.numel()].view(values.shape)
+    view.copy_(values)
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4 * off and view.is_contiguous()
+    return view
+
+
 class Bag(torch.nn.Module):
-    def __init__(self, sizes, seed):
+    """offsets: per tensor, how many floats behind a 16-byte boundary it starts (None: every parameter is its own allocation)."""
+
+    def __init__(self, sizes, seed, offsets=None):
         super().__init__()
         g = torch.Generator().manual_seed(seed)
-        self.w = torch.nn.ParameterList([torch.nn.Parameter(torch.randn(n, generator=g)) for n in sizes])
+        self.offsets = dict(zip((f"w.{i}" for i in range(len(sizes))), offsets or [None] * len(sizes)))
+        self.w = torch.nn.ParameterList([torch.nn.Parameter(on_gpu(torch.randn(n, generator=g), off) if off is not None else torch.randn(n, generator=g))
+                                         for n, off in zip(sizes, self.offsets.values())])
 
 
 def make_terms(model, n_terms, seed):
+    """importance and task_param sit where their parameter sits relative to a 16-byte boundary (Bag.offsets)."""
     g = torch.Generator().manual_seed(seed)
     terms = {}
     for k in range(n_terms):
-        terms[k] = {"importance": {n: (None if (n_terms > 1 and k == 1) else (torch.rand(p.shape, generator=g) * 3.0).cuda()) for n, p in model.named_parameters()},
-                    "task_param": {n: (p.detach().cpu() + 0.1 * torch.randn(p.shape, generator=g)).cuda() for n, p in model.named_parameters()}}
+        terms[k] = {"importance": {n: (None if (n_terms > 1 and k == 1) else on_gpu(torch.rand(p.shape, generator=g) * 3.0, model.offsets[n]))
+                                   for n, p in model.named_parameters()},
+                    "task_param": {n: on_gpu(p.detach().cpu() + 0.1 * torch.randn(p.shape, generator=g), model.offsets[n])
+                                   for n, p in model.named_parameters()}}
     return terms
 
 
-@pytest.mark.parametrize("sizes,n_terms", [((1,), 1), ((1, 1023, 1024, 1025, 2 ** 20 + 5), 3)], ids=["one-element", "five-tensors-three-terms"])
-def test_batched_regulariser_is_reg_loss_bit_for_bit(sizes, n_terms):
+# misaligned: no tensor of an entry is 16-byte aligned, so gsr_reg_multi_bwd walks every chunk element by element (its scalar branch; 4099
+# elements are five chunks with an odd tail); step.reg_loss's gst_reg_quad_bwd has no vector branch at all
+@pytest.mark.parametrize("sizes,n_terms,offsets", [((1,), 1, None), ((1, 1023, 1024, 1025, 2 ** 20 + 5), 3, None), ((5, 1025, 4099), 3, (1, 2, 3))],
+                         ids=["one-element", "five-tensors-three-terms", "misaligned"])
+def test_batched_regulariser_is_reg_loss_bit_for_bit(sizes, n_terms, offsets):
     from gslora_hip import reg, step
     lam = 0.37
-    a, b = Bag(sizes, 1).cuda(), Bag(sizes, 1).cuda()
+    a, b = Bag(sizes, 1, offsets).cuda(), Bag(sizes, 1, offsets).cuda()
+    for m in (a, b):
+        assert all(p.data_ptr() % 16 == 4 * (off or 0) for p, off in zip(m.parameters(), m.offsets.values()))
     terms = make_terms(a, n_terms, 2)
     rt = reg.RegTerms(b, terms, lam)
     for rnd in range(2):      # the second round accumulates into the non-zero gradients of the first
