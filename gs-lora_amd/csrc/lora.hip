@@ -393,7 +393,8 @@ __global__ __launch_bounds__(256) void lora_grad_reduce_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------ host side of gsl_lora_grad
-// One reduction as the host side passes it around (gsl_lora_grad fills it by name after its argument checks).
+// One reduction as the host side passes it around: lg_check fills the operand fields once they passed its checks (what the plan rule
+// reads), gsl_lora_grad adds the output, workspace, scale and stream by name.
 struct LgCall {
   const void *Y, *U; float* G; long ldy, gsn, gsj; int ldu, M, N, r, dtype, accumulate;
   float* ws; const float* gscale; hipStream_t st;
@@ -503,22 +504,46 @@ static int lg_launch(const LgCall& c, const LgPlan& p) {
 static inline int lg_vec(int dtype) { return dtype != GSL_F32 ? 8 : 4; }
 
 // The largest workspace a call with this (M, N, r) can need: either vector width, and the matrix-core form where N allows it.
+// Only the widths a call can have (gsl_lora_grad takes N % width == 0): the plan of a width above N has no column group, and its split
+// rule would divide by zero column blocks (N = 4, legal in f32, did). 0 for sizes and ranks every call is refused with.
 extern "C" long gsl_lora_grad_ws_elems(int M, int N, int r) {
-  long best = max(lg_plan(LG_VALU, M, N, r, 4).ws_elems, lg_plan(LG_VALU, M, N, r, 8).ws_elems);
+  if (M <= 0 || N <= 0 || r < 1 || r > 64) return 0;
+  long best = 0;
+  if ((N % 4) == 0) best = max(best, lg_plan(LG_VALU, M, N, r, 4).ws_elems);
+  if ((N % 8) == 0) best = max(best, lg_plan(LG_VALU, M, N, r, 8).ws_elems);
   if ((N % LGM_CN) == 0) best = max(best, lg_plan(LG_MFMA, M, N, r, 8).ws_elems);
   return best;
 }
 
+// The operand checks of a single reduction, shared by the launch and by gsl_lora_grad_plan; c receives what the plan rule reads.
+static int lg_check(const char* who, const void* Y, long ldy, const void* U, int ldu, int M, int N, int r, int dtype, LgCall* c) {
+  GSL_CHECK_ARG_AS(who, Y && U && M > 0 && N > 0 && ldy >= N, "null/size");
+  GSL_CHECK_ARG_AS(who, r >= 1 && r <= 64 && ldu >= 16 && ldu >= r && (ldu % 8) == 0, "r in [1,64], ldu >= max(16, r) (zero-padded), ldu % 8 == 0");
+  GSL_CHECK_ARG_AS(who, dtype == GSL_F32 || dtype == GSL_BF16 || dtype == GSL_F16, "dtype");
+  GSL_CHECK_ARG_AS(who, (N % lg_vec(dtype)) == 0, "N must be a multiple of the vector width");
+  c->Y = Y; c->ldy = ldy; c->U = U; c->ldu = ldu; c->M = M; c->N = N; c->r = r; c->dtype = dtype;
+  return GSL_OK;
+}
+
 extern "C" int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, float* G, long gsn, long gsj, int M, int N, int r,
                              int dtype, int accumulate, float* ws, const float* gscale, gsl_stream_t s) {
-  GSL_CHECK_ARG(Y && U && G && ws && M > 0 && N > 0 && ldy >= N, "null/size");
-  GSL_CHECK_ARG(r >= 1 && r <= 64 && ldu >= 16 && ldu >= r && (ldu % 8) == 0, "r in [1,64], ldu >= max(16, r) (zero-padded), ldu % 8 == 0");
-  GSL_CHECK_ARG(dtype == GSL_F32 || dtype == GSL_BF16 || dtype == GSL_F16, "dtype");
-  GSL_CHECK_ARG((N % lg_vec(dtype)) == 0, "N must be a multiple of the vector width");
   LgCall c{};
-  c.Y = Y; c.ldy = ldy; c.U = U; c.ldu = ldu; c.G = G; c.gsn = gsn; c.gsj = gsj; c.M = M; c.N = N; c.r = r; c.dtype = dtype;
-  c.accumulate = accumulate; c.ws = ws; c.gscale = gscale; c.st = as_stream(s);
+  GSL_TRY(lg_check(__func__, Y, ldy, U, ldu, M, N, r, dtype, &c));
+  GSL_CHECK_ARG(G && ws, "null/size");
+  c.G = G; c.gsn = gsn; c.gsj = gsj; c.accumulate = accumulate; c.ws = ws; c.gscale = gscale; c.st = as_stream(s);
   return lg_launch(c, lg_plan(lg_form(c), M, N, r, lg_vec(dtype)));
+}
+
+// The plan of that call, for tests and tools: the same lg_check / lg_form / lg_plan, no pointer dereferenced, no HIP call.
+extern "C" int gsl_lora_grad_plan(const void* Y, long ldy, const void* U, int ldu, int M, int N, int r, int dtype, gsl_lgrad_plan* out) {
+  GSL_CHECK_ARG(out, "null");
+  LgCall c{};
+  GSL_TRY(lg_check(__func__, Y, ldy, U, ldu, M, N, r, dtype, &c));
+  const LgPlan p = lg_plan(lg_form(c), M, N, r, lg_vec(dtype));
+  out->form = p.form == LG_MFMA ? GSL_LGRAD_MFMA : GSL_LGRAD_VALU;
+  out->R = p.R; out->bx = p.bx; out->nsplit = p.nsplit; out->rps = p.rps; out->CG = p.CG;
+  out->reduce = p.one_launch ? GSL_LGRAD_REDUCE_ONE_LAUNCH : (p.part2 ? GSL_LGRAD_REDUCE_TWO_LEVEL : GSL_LGRAD_REDUCE_DIRECT);
+  return GSL_OK;
 }
 
 // =====================================================================================
@@ -625,6 +650,20 @@ extern "C" long gsl_lora_grad_batch_ws_elems(const gsl_lgrad_desc* descs, int n)
     if (ws > total) total = ws;
   }
   return total;
+}
+
+// The plan of every entry of gsl_lora_grad_batch(descs, n, ...), 24 descriptors at a time as the launches take them: the same lgb_plan.
+extern "C" int gsl_lora_grad_batch_plan(const gsl_lgrad_desc* descs, int n, gsl_lgrad_batch_plan* out) {
+  GSL_CHECK_ARG(descs && n > 0 && out, "null/size");
+  for (int k0 = 0; k0 < n; k0 += LGB_MAX) {
+    LgbArgs a;
+    GSL_TRY(lgb_plan(descs + k0, min(LGB_MAX, n - k0), &a, nullptr, nullptr, nullptr));
+    for (int k = 0; k < a.n; ++k) {
+      gsl_lgrad_batch_plan& o = out[k0 + k];
+      o.R = a.e[k].R; o.bx = a.e[k].bx; o.nsplit = a.e[k].nsplit; o.rps = a.e[k].rps;
+    }
+  }
+  return GSL_OK;
 }
 
 // n LoRA-gradient reductions G_k (+)= Y_k^T U_k (bf16 operands, see gsl_lora_grad) in two launches per 24 descriptors. descs is a HOST

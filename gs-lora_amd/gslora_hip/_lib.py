@@ -32,6 +32,9 @@ U8_NCHW, U8_NHWC = 0, 1        # source layout of the uint8 gathers (gsl_patchif
  ATTN_BWD_MERGED, ATTN_BWD_FUSED_1024, ATTN_BWD_FUSED_512, ATTN_BWD_F32_LONG, ATTN_BWD_F32, ATTN_FWD_CLS, ATTN_FWD_CLS_LONG,
  ATTN_BWD_CLS) = range(17)
 ATTN_DIRECTIONS = {"fwd": 0, "bwd": 1, "cls_fwd": 2, "cls_bwd": 3}
+# gsl_lgrad_form / gsl_lgrad_reduce: the `form` and `reduce` of a gsl_lgrad_plan (gsl_lora_grad_plan)
+LGRAD_MFMA, LGRAD_VALU = 0, 1
+LGRAD_REDUCE_DIRECT, LGRAD_REDUCE_TWO_LEVEL, LGRAD_REDUCE_ONE_LAUNCH = 0, 1, 2
 NORM_SPLIT = 8
 SEED_ON_DEVICE = 0x80000000   # flag bit of a `site` argument: `seed` is a device pointer to a uint64 (HIP-graph replays)
 
@@ -65,6 +68,8 @@ SIGNATURES = {
     "gsl_lora_grad": [_vp, _l, _vp, _i, _vp, _l, _l, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "gsl_lora_grad_batch_ws_elems": [_vp, _i],
     "gsl_lora_grad_batch": [_vp, _i, _vp, _i, _vp, _vp],
+    "gsl_lora_grad_plan": [_vp, _l, _vp, _i, _i, _i, _i, _i, _vp],
+    "gsl_lora_grad_batch_plan": [_vp, _i, _vp],
     "gsl_cosface_prep": [_vp, _vp, _i, _i, _vp],
     "gsl_head_fwd": [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _i, _i, _vp],
     "gsl_head_bwd": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _f, _u64, _u32, _i, _i, _i, _vp, _vp, _i, _vp],

@@ -1,5 +1,6 @@
 """Thin torch-tensor wrappers over the C ABI (include/gslora_hip.h). PyTorch supplies device
 memory and the stream; every FLOP of the step runs in libgslora_hip.so. No fallbacks."""
+import collections
 import ctypes
 
 import torch
@@ -483,6 +484,54 @@ class _LgradDesc(ctypes.Structure):      # mirrors struct gsl_lgrad_desc (includ
                 ("gsn", ctypes.c_long), ("gsj", ctypes.c_long)]
 
 
+class _LgradPlan(ctypes.Structure):      # mirrors struct gsl_lgrad_plan
+    _fields_ = [(n, ctypes.c_int) for n in ("form", "R", "bx", "nsplit", "rps", "CG", "reduce")]
+
+
+class _LgradBatchPlan(ctypes.Structure):      # mirrors struct gsl_lgrad_batch_plan
+    _fields_ = [(n, ctypes.c_int) for n in ("R", "bx", "nsplit", "rps")]
+
+
+LgradPlan = collections.namedtuple("LgradPlan", "form R bx nsplit rps CG reduce")
+LgradBatchPlan = collections.namedtuple("LgradBatchPlan", "R bx nsplit rps")
+_PLAN_ADDR = 1 << 20      # the made-up, 16-byte aligned operand address of a plan asked for by shape
+
+
+def lora_grad_plan_args(M, N, r, dtype, ldy=None, ldu=64, y_addr=_PLAN_ADDR, u_addr=_PLAN_ADDR):
+    """How gsl_lora_grad runs a call with these operand arguments (gsl_lora_grad_plan: host code, no device needed, nothing is dereferenced):
+    form / reduce are _lib.LGRAD_*. Raises RuntimeError where the launch refuses, with the launch's message."""
+    out = _LgradPlan()
+    L.check(L.load().gsl_lora_grad_plan(y_addr, N if ldy is None else ldy, u_addr, ldu, M, N, r, code(dtype), ctypes.byref(out)), "gsl_lora_grad_plan")
+    return LgradPlan(*(getattr(out, n) for n in LgradPlan._fields))
+
+
+def lora_grad_plan(Y, U, r):
+    """The plan of lora_grad(Y, U, G, ..., r) on these very tensors (their strides and addresses count)."""
+    return lora_grad_plan_args(Y.shape[0], Y.shape[1], r, Y.dtype, Y.stride(0), U.stride(0), Y.data_ptr(), U.data_ptr())
+
+
+def _lgrad_descs(entries):
+    """entries as for lora_grad_batch — or (M, N, r) shapes, placed at made-up aligned addresses with dense Y and a 64-wide U."""
+    arr = (_LgradDesc * len(entries))()
+    for k, e in enumerate(entries):
+        if isinstance(e[0], int):
+            M, N, r = e
+            arr[k] = _LgradDesc(_PLAN_ADDR, N, _PLAN_ADDR, 64, M, N, r, 0, 0, _PLAN_ADDR, r, 1)
+        else:
+            Y, U, G, gsn, gsj, r, acc = e
+            arr[k] = _LgradDesc(Y.data_ptr(), Y.stride(0), U.data_ptr(), U.stride(0), Y.shape[0], Y.shape[1], r, 1 if acc else 0, 0,
+                                G.data_ptr(), gsn, gsj)
+    return arr
+
+
+def lora_grad_batch_plan(entries):
+    """Per entry of lora_grad_batch(entries): (R, bx, nsplit, rps) of its aligned MFMA body (gsl_lora_grad_batch_plan, host code)."""
+    arr = _lgrad_descs(entries)
+    out = (_LgradBatchPlan * len(entries))()
+    L.check(L.load().gsl_lora_grad_batch_plan(arr, len(entries), out), "gsl_lora_grad_batch_plan")
+    return [LgradBatchPlan(o.R, o.bx, o.nsplit, o.rps) for o in out]
+
+
 def lora_grad_batchable(Y, U, r):
     """Can this reduction ride in gsl_lora_grad_batch (16-bit MFMA form: 256-column blocks, 16-byte rows)? The form reads columns 0..15
     of U up to rank 16 and the 8-column chunks [0, 8 * ceil(r / 8)) above: a row of U must be at least that long."""
@@ -498,10 +547,7 @@ def lora_grad_batch(entries, gscale=None):
     if not entries:
         return
     assert ctypes.sizeof(_LgradDesc) == 72
-    arr = (_LgradDesc * len(entries))()
-    for k, (Y, U, G, gsn, gsj, r, acc) in enumerate(entries):
-        arr[k] = _LgradDesc(Y.data_ptr(), Y.stride(0), U.data_ptr(), U.stride(0), Y.shape[0], Y.shape[1], r, 1 if acc else 0, 0,
-                            G.data_ptr(), gsn, gsj)
+    arr = _lgrad_descs(entries)
     lib = L.load()
     need = lib.gsl_lora_grad_batch_ws_elems(arr, len(entries))
     if need < 0:

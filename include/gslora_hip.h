@@ -276,8 +276,9 @@ GSL_API int gsl_attention_kernel_choice(int B, int T, int H, int dtype, int qkv_
  *            depends on a column outside [0, r). An aligned block at column offset c of a 64-wide tensor has c % 8 == 0, so
  *            c + r <= 64 gives c + 8 * ceil(r / 8) <= 64: the block may end at the row end.
  * The partial sums are laid out part[split][n][R] with the padded rank R in {8, 16, 32, 64}; the sums keep a fixed order (no atomics).
- * ws f32 >= gsl_lora_grad_ws_elems(). gscale (nullable): device {S, 1/S} of a loss-scaled backward (see gsl_head_bwd): the sums are
- * multiplied by 1/S before they are stored / accumulated. */
+ * ws f32 >= gsl_lora_grad_ws_elems(): the largest need of any call with this (M, N, r), 0 where every call is refused (M, N <= 0, r outside
+ * [1, 64], N % 4 != 0). gscale (nullable): device {S, 1/S} of a loss-scaled backward (see gsl_head_bwd): the sums are multiplied by 1/S
+ * before they are stored / accumulated. */
 GSL_API long gsl_lora_grad_ws_elems(int M, int N, int r);
 GSL_API int gsl_lora_grad(const void* Y, long ldy, const void* U, int ldu, float* G, long gsn, long gsj,
                   int M, int N, int r, int dtype, int accumulate, float* ws, const float* gscale, gsl_stream_t s);
@@ -290,6 +291,30 @@ typedef struct gsl_lgrad_desc {
 } gsl_lgrad_desc;
 GSL_API long gsl_lora_grad_batch_ws_elems(const gsl_lgrad_desc* descs, int n);
 GSL_API int gsl_lora_grad_batch(const gsl_lgrad_desc* descs, int n, float* ws, int dtype, const float* gscale, gsl_stream_t s);
+
+/* The launch plan: how gsl_lora_grad runs a call — a function of the shape, the dtype, the row strides and the 16-byte alignment of Y and
+ * U, the same one the launch calls. Takes the operand arguments of gsl_lora_grad with the same checks (GSL_ERR_ARG and the same message
+ * where the launch refuses) and dereferences no pointer: it runs without a device, on made-up addresses. The development build's
+ * GSL_LORA_GRAD_MFMA knob applies to it as to the launch.
+ *   form    the partial kernel: the matrix-core form (16-bit operands, N % 256 == 0, M >= 64, 16-byte aligned U / Y and rows,
+ *           ldu >= the columns it reads) or the VALU form (everything else)
+ *   R       padded rank of the partial layout part[split][n][R]: 8, 16, 32 or 64
+ *   bx      column blocks of the partial grid: N / 256 (MFMA), ceil(N / vector width / CG) (VALU)
+ *   nsplit  row splits of the partial grid; split k owns the rows [k * rps, min(M, (k + 1) * rps))
+ *   rps     rows per split (MFMA: a multiple of its 32-row slab)
+ *   CG      VALU form: column groups of a workgroup, 64, 128 or 256 (its 256 threads walk 256 / CG interleaved row phases); MFMA: 0
+ *   reduce  what sums the splits: one kernel over all of them (DIRECT, at most 32 splits), a first level over slabs of 32 consecutive
+ *           splits and a second over the slabs (TWO_LEVEL), or the single launch whose four waves each own every fourth split (ONE_LAUNCH:
+ *           MFMA form, at most 160 splits, N * R >= 8192) */
+enum gsl_lgrad_form { GSL_LGRAD_MFMA = 0, GSL_LGRAD_VALU = 1 };
+enum gsl_lgrad_reduce { GSL_LGRAD_REDUCE_DIRECT = 0, GSL_LGRAD_REDUCE_TWO_LEVEL = 1, GSL_LGRAD_REDUCE_ONE_LAUNCH = 2 };
+typedef struct gsl_lgrad_plan { int form, R, bx, nsplit, rps, CG, reduce; } gsl_lgrad_plan;
+GSL_API int gsl_lora_grad_plan(const void* Y, long ldy, const void* U, int ldu, int M, int N, int r, int dtype, gsl_lgrad_plan* out);
+/* The same for gsl_lora_grad_batch(descs, n, ...): out[k] is the plan of entry k (always the aligned matrix-core body, summed by the batch
+ * reducer in split order). The row splits of an entry depend on the other entries of its group of 24 descriptors. GSL_ERR_ARG, with the
+ * message of the launch, for a descriptor the launch refuses. */
+typedef struct gsl_lgrad_batch_plan { int R, bx, nsplit, rps; } gsl_lgrad_batch_plan;
+GSL_API int gsl_lora_grad_batch_plan(const gsl_lgrad_desc* descs, int n, gsl_lgrad_batch_plan* out);
 
 
 /* ---- K10 head: cls pool + LayerNorm + CosFace (vit_face.py:540-546, 171-208; s=64, m=0.35); ArcFace through the margin pair below.

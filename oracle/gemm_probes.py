@@ -16,6 +16,10 @@ Largest magnitudes (tests/test_gemm_probes_host.py checks the round trip of ever
 (64 + 4 + 4) * 2 + 8 = 152 — integers below 256 —, MUL 0.5 * 64 * 2 = 64 in halves; LoRA |acc| <= 4 + 16 * 0.5 = 12 in eighths, (12 + 4) + 8 = 24
 without and 40 in quarters with dropout. The sums over m of the reductions stay below 1300 * 24 * 8 < 2^24 eighths: exact in f32 in any order.
 
+LGRAD_EDGES is the table of gsl_lora_grad at ranks 1 - 16, one row per path of its launch plan (tests/test_lora_grad_plan_host.py,
+tests/test_hip_lora_grad_edges.py); its operands come from make(..., edge_rows=...), which takes the zeros out of the first and last row of
+every row split so that a dropped or doubled boundary row moves every element of the result.
+
 Every builder is deterministic (its own torch.Generator) and returns float32 CPU tensors; the references take tensors on any device and
 return float64 on that device."""
 import collections
@@ -54,6 +58,55 @@ TABLE = (
 BY_NAME = {c.name: c for c in TABLE}
 LGRAD_BATCH = ((333, 256, 4), (700, 768, 16))      # (M, N, r) of the two entries of the lora_grad_batch case
 
+# gsl_lora_grad at ranks 1 - 16, one row per launch-plan path (tests/test_lora_grad_plan_host.py holds every claim to gsl_lora_grad_plan,
+# tests/test_hip_lora_grad_edges.py runs the rows): name, shape, rank, operand kind ("16": bf16 and fp16, "f32"), then the path the row is
+# named for — form, reduce form, row splits, rows per split, column groups of the VALU form — and ystep: Y's rows are ystep * N elements
+# apart (the compact cls rows of a 197-token model). |sums| <= 4 * 16385 + 4 < 2^24: exact in f32 in any order.
+LgCase = collections.namedtuple("LgCase", "name M N r kind form reduce nsplit rps CG ystep")
+LGRAD_EDGES = tuple(LgCase(*row) for row in (
+    ("mfma_first_m", 64, 256, 8, "16", "MFMA", "DIRECT", 2, 32, 0, 1),                      # the form's first M: two full splits
+    ("mfma_one_row_tail", 65, 256, 1, "16", "MFMA", "DIRECT", 3, 32, 0, 1),                 # last split of one row; R = 8 ...
+    ("mfma_one_row_tail", 65, 256, 3, "16", "MFMA", "DIRECT", 3, 32, 0, 1),
+    ("mfma_one_row_tail", 65, 256, 8, "16", "MFMA", "DIRECT", 3, 32, 0, 1),
+    ("mfma_one_row_tail", 65, 256, 9, "16", "MFMA", "DIRECT", 3, 32, 0, 1),                 # ... and R = 16
+    ("mfma_one_row_tail", 65, 256, 16, "16", "MFMA", "DIRECT", 3, 32, 0, 1),
+    ("mfma_two_row_tail_one_launch", 130, 2048, 8, "16", "MFMA", "ONE_LAUNCH", 5, 32, 0, 1),    # 8 column blocks
+    ("mfma_one_launch_boundary", 65, 1024, 8, "16", "MFMA", "ONE_LAUNCH", 3, 32, 0, 1),     # N * R == 8192 exactly
+    ("mfma_capped_splits", 1057, 256, 5, "16", "MFMA", "DIRECT", 17, 64, 0, 1),             # 34 slabs, cap 32: two slabs per split, last split 33 rows
+    ("mfma_two_level", 2049, 256, 8, "16", "MFMA", "TWO_LEVEL", 65, 32, 0, 1),              # level-1 slabs of 32 / 32 / 1 splits
+    ("mfma_two_level", 2049, 256, 16, "16", "MFMA", "TWO_LEVEL", 65, 32, 0, 1),             # (R = 16 on the two levels: N * R = 4096)
+    ("mfma_two_level", 2049, 768, 7, "16", "MFMA", "TWO_LEVEL", 65, 32, 0, 1),
+    ("mfma_two_level", 2049, 768, 8, "16", "MFMA", "TWO_LEVEL", 65, 32, 0, 1),
+    ("mfma_one_launch_many_splits", 2081, 512, 16, "16", "MFMA", "ONE_LAUNCH", 66, 32, 0, 1),   # the four waves own 17 / 17 / 16 / 16 splits
+    ("mfma_over_160_splits", 5153, 1024, 8, "16", "MFMA", "TWO_LEVEL", 162, 32, 0, 1),      # although N * R >= 8192
+    ("valu_smallest", 1, 8, 1, "16", "VALU", "DIRECT", 1, 1, 64, 1),                        # one column group, four row phases, one row
+    ("valu_smallest", 1, 4, 1, "f32", "VALU", "DIRECT", 1, 1, 64, 1),
+    ("valu_smallest", 5, 4, 2, "f32", "VALU", "DIRECT", 1, 5, 64, 1),                       # fewer rows than a batch of loads (4 x 4 phases)
+    ("valu_unaligned_block", 259, 72, 8, "16", "VALU", "DIRECT", 3, 87, 64, 1),             # rows 64 + 23 per LDS fill
+    ("valu_cg128", 63, 256, 16, "16", "VALU", "DIRECT", 1, 63, 128, 1),                     # M < 64 on an MFMA-shaped N; two row phases
+    ("valu_cg128", 300, 520, 9, "16", "VALU", "DIRECT", 3, 100, 128, 1),
+    ("valu_cg256", 130, 1024, 7, "f32", "VALU", "DIRECT", 2, 65, 256, 1),                   # one row phase: no phase combine
+    ("valu_cg256", 70, 2056, 8, "16", "VALU", "DIRECT", 1, 70, 256, 1),                     # a second column block with one active group
+    ("valu_two_level", 4225, 8, 3, "16", "VALU", "TWO_LEVEL", 34, 125, 64, 1),              # level-1 slabs of 32 / 2 splits
+    ("valu_two_level", 4225, 8, 9, "16", "VALU", "TWO_LEVEL", 34, 125, 128, 1),             # (R = 16 on the VALU form's two levels)
+    ("valu_two_level", 4225, 4, 3, "f32", "VALU", "TWO_LEVEL", 34, 125, 64, 1),
+    ("valu_two_level", 16385, 8, 3, "16", "VALU", "TWO_LEVEL", 129, 128, 64, 1),            # last split and last level-1 slab of ONE row
+    ("cls_rows", 8, 512, 8, "16", "VALU", "DIRECT", 1, 8, 64, 197),                         # the 8 cls rows through the single call
+    ("cls_rows", 8, 2048, 8, "16", "VALU", "DIRECT", 1, 8, 256, 197),
+))
+LGRAD_EDGE_IDS = tuple(f"{c.name}-{c.M}x{c.N}-r{c.r}-{c.kind}" for c in LGRAD_EDGES)
+
+
+def padded_rank(r):
+    """R of the partial layout part[split][n][R] of gsl_lora_grad."""
+    return 8 if r <= 8 else 16 if r <= 16 else 32 if r <= 32 else 64
+
+
+def make_lgrad_edges(M, N, edge_rows):
+    """Y [M, N], U [M, 64] and G0 [N, 16] (rank r uses G0[:, :r]) of an LGRAD_EDGES shape, with the edge_rows option of make()."""
+    return make(Case(f"lgrad_edges_{M}x{N}", "lgrad", M, N, 0, 0, 16, None, True), edge_rows=edge_rows)
+
+
 # epilogues with an exact reference, by the name the tests use
 EXACT_GEMM = ("store", "store_f32", "bias_res_f32", "bias_res_16", "bias_res_f32_drop", "bias_res_16_drop", "mul", "patch", "patch_16", "qkv_hm")
 EXACT_LORA = ("store", "bias_res_f32", "bias_res_16", "bias_res_16_drop", "mul")
@@ -87,14 +140,32 @@ def ternary_rows(g, M, K, c):
     return torch.zeros(M, nt, 64).scatter_(2, idx, sign).view(M, K)
 
 
-def make(case):
-    """The operands of one table row: a dict of float32 CPU tensors."""
+def split_edge_rows(M, *rps):
+    """The first and the last row of every row split of an M-row reduction, for each rows-per-split in rps (a launch plan's `rps`: split k
+    owns the rows [k rps, min(M, (k + 1) rps)); the slabs of a two-level reduce begin and end at split edges). Sorted, unique."""
+    rows = set()
+    for p in rps:
+        for r0 in range(0, M, p):
+            rows.update((r0, min(M, r0 + p) - 1))
+    return tuple(sorted(rows))
+
+
+def make(case, edge_rows=None):
+    """The operands of one table row: a dict of float32 CPU tensors. edge_rows (lgrad rows only; default off, and the other rows keep
+    the values they have without it): on these rows Y has no zero — it is in +-{1..4} — and U is +-1 in all of its 64 columns, so that
+    Y[m, n] U[m, j] != 0 for every n and j: such a row dropped from the sum, or counted twice, moves every element of the result."""
     g = _gen(case)
     M, N, r = case.M, case.N, case.r
     d = {}
     if case.kind == "lgrad":
         d["Y"], d["U"] = small_int(g, 4, M, N), ternary(g, M, 64)
         d["G0"] = small_int(g, 4, N, r)
+        if edge_rows is not None:
+            rows = torch.tensor(edge_rows, dtype=torch.long)
+            ge = _gen(case, salt=101)
+            y = torch.randint(1, 5, (len(rows), N), generator=ge).float() * (torch.randint(0, 2, (len(rows), N), generator=ge).float() * 2 - 1)
+            u = torch.randint(0, 2, (len(rows), 64), generator=ge).float() * 2 - 1
+            d["Y"][rows], d["U"][rows] = torch.where(d["Y"][rows] != 0, d["Y"][rows], y), torch.where(d["U"][rows] != 0, d["U"][rows], u)
         return d
     c = per_tile(case)
     d["A1"], d["W1"] = ternary_rows(g, M, case.K1, c), ternary(g, N, case.K1)

@@ -25,7 +25,7 @@ def test_header_states_the_workspace_contract_and_the_class_range():
 def test_no_entry_point_was_added_or_changed():
     from gslora_hip import _lib
     declared = set(re.findall(r"\b(gsl_[a-z0-9_]+)\s*\(", header())) - {"gsl_dropout_keep"}
-    assert declared == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 57      # (56 + gsl_attention_kernel_choice)
+    assert declared == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 59      # (56 + gsl_attention_kernel_choice + the two LoRA-gradient plan queries)
     assert len(_lib.SIGNATURES["gsl_head_fwd"]) == 21 and len(_lib.SIGNATURES["gsl_head_fwd_margin"]) == 25
     assert len(_lib.SIGNATURES["gsl_head_bwd"]) == 28 and len(_lib.SIGNATURES["gsl_head_bwd_margin"]) == 33
 

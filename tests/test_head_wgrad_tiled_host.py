@@ -30,7 +30,7 @@ def test_no_entry_point_was_added_or_changed():
     from gslora_hip import _lib
     hdr = header()
     declared = set(re.findall(r"\b(gsl_[a-z0-9_]+)\s*\(", hdr)) - {"gsl_dropout_keep"}
-    assert declared == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 57
+    assert declared == set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 59      # (57 + the two LoRA-gradient plan queries)
     proto = re.search(r"GSL_API int gsl_head_wgrad\(([^;]*)\);", hdr).group(1)
     assert len(proto.split(",")) == len(_lib.SIGNATURES["gsl_head_wgrad"]) == 15
 

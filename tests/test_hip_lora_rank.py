@@ -2,10 +2,13 @@
 VALU form, the reducers), exact: the small-integer operands of oracle/gemm_probes.py make every sum exact in f32, so every comparison is
 torch.equal against the float64 reference G.lora_grad. Every tensor sits in guard bands (tests/guard_bands.py).
 
-Shapes, the smallest that reach each form:
-  MFMA form (16-bit operands, N % 256 == 0, M >= 64, 16-byte aligned U): (65, 256) a last slab of one row, (700, 768) several row splits
-  and the two-level reduction, (1300, 2048) the single-launch reduction (N * R >= 8192 outputs).
-  VALU form: (333, 132) f32 vector width 4, (333, 136) 16-bit vector width 8, (5, 256) M < 64, (700, 768) f32 with several splits.
+Shapes, the smallest that reach each form (every note is what gsl_lora_grad_plan answers: tests/test_lora_grad_plan_host.py,
+test_shape_notes_of_the_rank_tests):
+  MFMA form (16-bit operands, N % 256 == 0, M >= 64, 16-byte aligned U): (65, 256) a last split of one row, (700, 768) 22 row splits,
+  (1300, 2048) 21 splits of two slabs — all three on the single-launch reduction (N * R >= 8192 outputs from R = 32 on) —, and
+  (5153, 256) 162 splits, more than the single launch takes: the two-level reduction, level-1 slabs of 32 x 5 + 2 splits (r = 17 and 64).
+  VALU form: (333, 132) f32 vector width 4, (333, 136) 16-bit vector width 8, (5, 256) M < 64, (700, 768) f32 with six splits — one
+  reduce launch each —, and (4225, 8) 34 splits: the chunked form in front of the two-level reduction (r = 17).
 The read rule of include/gslora_hip.h: above rank 16 the aligned MFMA form reads the 8-column chunks [0, 8 * ceil(r / 8)) of U, every
 other form the columns [0, r), and no result depends on a column outside [0, r): U is a column block of a 64-wide tensor whose other
 columns are NaN in one variant, up to the row end."""
@@ -77,6 +80,20 @@ MFMA_RANKS = [17, 24, 32, 33, 48, 63, 64]
 @pytest.mark.parametrize("dt", [BF16, F16], ids=ident)
 @pytest.mark.parametrize("M,N", MFMA_SHAPES)
 def test_mfma_form(ops, M, N, dt, r):
+    mfma_form(ops, M, N, dt, r)
+
+
+@pytest.mark.parametrize("r", [17, 64])
+@pytest.mark.parametrize("dt", [BF16, F16], ids=ident)
+def test_mfma_form_two_level_reduce(ops, dt, r):
+    """162 row splits: lora_grad_reduce1_kernel over slabs of 32 splits, then lora_grad_reduce2_kernel, at R = 32 and R = 64."""
+    from gslora_hip import _lib as L
+    p = ops.lora_grad_plan_args(5153, 256, r, dt)
+    assert (p.form, p.reduce, p.nsplit) == (L.LGRAD_MFMA, L.LGRAD_REDUCE_TWO_LEVEL, 162)
+    mfma_form(ops, 5153, 256, dt, r)
+
+
+def mfma_form(ops, M, N, dt, r):
     d = for_rank(operands(M, N), r)
     what = f"mfma {M}x{N} {NAME[dt]} r={r}"
     Y, U = Banded((M, N), dt, d["Y"].to(dt)), Banded((M, 64), dt, d["U"].to(dt))
@@ -91,6 +108,19 @@ VALU_PARAMS = [(333, 132, F32), (333, 136, BF16), (333, 136, F16), (5, 256, BF16
 @pytest.mark.parametrize("r", [17, 32, 64])
 @pytest.mark.parametrize("M,N,dt", VALU_PARAMS, ids=ident)
 def test_valu_form(ops, M, N, dt, r):
+    valu_form(ops, M, N, dt, r)
+
+
+@pytest.mark.parametrize("dt", [BF16, F16], ids=ident)
+def test_valu_form_two_level_reduce(ops, dt):
+    """34 row splits of the chunked VALU form (two 16-column chunks): level-1 slabs of 32 and 2 splits."""
+    from gslora_hip import _lib as L
+    p = ops.lora_grad_plan_args(4225, 8, 17, dt)
+    assert (p.form, p.reduce, p.nsplit, p.R) == (L.LGRAD_VALU, L.LGRAD_REDUCE_TWO_LEVEL, 34, 32)
+    valu_form(ops, 4225, 8, dt, 17)
+
+
+def valu_form(ops, M, N, dt, r):
     d = for_rank(operands(M, N), r)
     what = f"valu {M}x{N} {NAME[dt]} r={r}"
     Y, U = Banded((M, N), dt, d["Y"].to(dt)), Banded((M, 64), dt, d["U"].to(dt))
